@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- peeled edges/sec of the k-truss hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full pass of the k-truss path over the synthetic power-law unitig graph, from the resident simple graph
 (the symmetric CSR igraph_simplify would leave) to per-edge trussness in canonical order -- what igraph_trussness does
@@ -27,6 +27,13 @@ beside the headline under `alternatives`: --c4-allreduce (the support all-reduce
 default), --replicas-sliced (round 4's default: nothing exchanged, every rank runs the whole path and materialises its slice
 of the canonical results), --replicas (nothing sliced), --batch (one graph per rank, seed + rank: weak scaling, its own
 metric name).
+
+A plain run does what the headline needs and nothing more: build check, graph, W warm-up steps, the K timed steps, the
+outputs of the last step (--dump-outputs), the result line (`value`, `ms_per_step`, the phases of the timed steps).
+--full adds everything else this benchmark measures or checks, after the timed region: the resident-preparation figure,
+the other N > 1 flows and the slice check, k-core of the same graph, the roofline, results fetch, CoreA, the
+runTruss-faithful variant, first-call figures, the C2 block and the CPU baseline (the options --no-cpu-baseline,
+--no-extras and --no-alternatives thin that out).
 """
 import argparse
 import json
@@ -46,6 +53,9 @@ CONFIGS = {
     "tiny": (100_000, 245_000, 2.6, 42, "tiny: |V|=100k |E|~1M (debug)"),
 }
 CPU_SAMPLE = "c2"              # the single-thread CPU figure is timed on the C2 graph (~25 s); the all-cores one on the workload itself
+DUMP_SAMPLE = 1 << 20         # --dump-outputs: per-edge results of at most this many canonical edges (a seeded sample)
+DUMP_SEED = 20240611
+DUMP_LIMIT = 64 << 20          # bytes, all files together
 PHASES = ("ms_prepare", "ms_prep_vertex", "ms_prep_edges", "ms_prep_rows", "ms_orient", "ms_tri_count", "ms_allreduce", "ms_tri_fill", "ms_sort", "ms_compact", "ms_peel", "ms_tail",
           "ms_truss_local", "ms_gather", "ms_exchange")
 
@@ -136,6 +146,27 @@ def cpu_baseline(workload_csr, workload_ne):
     return out
 
 
+def dump_outputs(acc, outdir):
+    """--dump-outputs: the k-truss results of the last timed step as komb_truss_fetch hands them to a caller (canonical
+    edge order, original vertex ids), as float arrays.  Per-edge arrays hold a seeded sample of at most DUMP_SAMPLE edges
+    (every edge when there are fewer): the same positions for the same graph, so two builds compare value for value;
+    edge_index says which canonical edges they are.  truss_histogram counts the edges of every trussness over all edges.
+    N > 1: rank 0's results (in the sliced flow, zeros outside its slice)."""
+    import numpy as np
+    eu, ev, tr = acc.truss_fetch()
+    n = len(tr)
+    if n > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+    else:
+        idx = np.arange(n)
+    arrays = {"edge_index": idx.astype(np.float64), "edge_u": eu[idx].astype(np.float64), "edge_v": ev[idx].astype(np.float64),
+              "trussness": tr[idx].astype(np.float32), "truss_histogram": np.bincount(tr).astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -165,7 +196,15 @@ def main():
                     help="only the timed workload (+ the k-core of the same graph): no runTruss-faithful variant, no first-call "
                          "figures, no C2 block, no CoreA -- for rocprofv3 runs, whose per-kernel averages should see the timed launches only")
     ap.add_argument("--faithful", action="store_true", help="(accepted for older command lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline (resident-preparation figure, "
+                         "other N > 1 flows, k-core, roofline, fetch, CoreA, runTruss-faithful, first call, C2, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed, as its caller receives it (canonical edge endpoints and trussness), "
+                         "to DIR/<name>.npy in float64 / float32: a fixed, seeded sample of the edges plus the trussness histogram of all of them")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     picked = [n for n in ("batch", "replicas", "replicas_sliced", "shard") if getattr(args, n)]
     if args.batch and (args.replicas or args.same_graph or args.shard or args.replicas_sliced or args.shard_peel):
         raise SystemExit("--batch runs one graph per rank: it cannot be combined with --replicas / --replicas-sliced / --same-graph / --shard")
@@ -265,7 +304,8 @@ def main():
     acc.from_edges(nv, uv)                       # a1 on the device; the symmetric CSR stays resident in HBM (nothing else does)
     t_build = time.perf_counter() - t0
     build_stats = acc.stats()
-    extras = rank == 0 and world == 1 and not args.no_extras
+    full = args.full
+    extras = full and rank == 0 and world == 1 and not args.no_extras
     if not extras:
         del uv
     ne = acc.ne
@@ -319,10 +359,15 @@ def main():
         t = torch.tensor([ne], dtype=torch.int64)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         ne_total = int(t.item())
-    # the same step on a graph whose preparation is resident (what rounds 1-4 reported as the headline)
-    dt_res, phase_res = timed(flow, False, args.steps, with_phases=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(acc, args.dump_outputs)
+    # everything below up to the result line runs with --full only
+    dt_res = phase_res = None
+    if full:
+        # the same step on a graph whose preparation is resident (what rounds 1-4 reported as the headline)
+        dt_res, phase_res = timed(flow, False, args.steps, with_phases=True)
     alternatives = None
-    if world > 1 and mode in ("sharded", "c4", "sliced") and not args.no_alternatives:
+    if full and world > 1 and mode in ("sharded", "c4", "sliced") and not args.no_alternatives:
         alternatives = {}
         for name, f in (("shard_peel_and_support_allreduce", "sharded"), ("support_allreduce_only", "c4"), ("replicas_sliced", "sliced")):
             if f == flow:
@@ -332,7 +377,7 @@ def main():
             alternatives[name] = {"ms_per_step": d_alt / args.steps * 1e3, "value": ne * args.steps / d_alt}
         acc.set_shard_peel(flow == "sharded")
     slices_ok = None
-    if flow == "sliced":
+    if full and flow == "sliced":
         # outside the timed region: this rank's slice against a whole run of its own (values in the slice, zeros elsewhere)
         kd.truss_run_slice(acc)
         _, _, tr_s, sup_s = acc.truss_fetch(with_support=True)
@@ -345,27 +390,27 @@ def main():
         slices_ok = bool(int(t.item()))
         del tr_s, sup_s, tr_w, sup_w
 
-    # the roofline model's graph statistics (sum d^2, oriented items, max degree): a measurement-only call
-    acc.graph_moments()
-    gm = acc.stats()
-    for k in ("sum_deg_sq", "wedge_items", "oriented_items", "max_degree"):
-        st[k] = gm[k]
+    core_first_ms = core_stats = core_ms = None
+    if full:
+        # the roofline model's graph statistics (sum d^2, oriented items, max degree): a measurement-only call
+        acc.graph_moments()
+        gm = acc.stats()
+        for k in ("sum_deg_sq", "wedge_items", "oriented_items", "max_degree"):
+            st[k] = gm[k]
 
-    # k-core of the same graph, reported alongside (BASELINE config C2's op)
-    # (three calls, the fastest reported: the first one of a context allocates its scratch -- 0.2-0.5 ms of hipMalloc between kernels)
-    core_first_ms = None
-    core_stats = None
-    for _ in range(3):
-        if flow == "sharded":
-            kd.core_run_sharded(acc, group=data_group)
-        else:
-            acc.core_run()
-        cs = acc.stats()
-        if core_first_ms is None:
-            core_first_ms = cs["ms_core"]
-        if core_stats is None or cs["ms_core"] < core_stats["ms_core"]:
-            core_stats = cs
-    core_ms = core_stats["ms_core"]
+        # k-core of the same graph, reported alongside (BASELINE config C2's op)
+        # (three calls, the fastest reported: the first one of a context allocates its scratch -- 0.2-0.5 ms of hipMalloc between kernels)
+        for _ in range(3):
+            if flow == "sharded":
+                kd.core_run_sharded(acc, group=data_group)
+            else:
+                acc.core_run()
+            cs = acc.stats()
+            if core_first_ms is None:
+                core_first_ms = cs["ms_core"]
+            if core_stats is None or cs["ms_core"] < core_stats["ms_core"]:
+                core_stats = cs
+        core_ms = core_stats["ms_core"]
 
     faithful = first_call = c2_block = corea = fetch_block = None
     workload_csr = None
@@ -380,6 +425,8 @@ def main():
         fetch_block = {"truss_only_ms": min(tf[0], tf[3]), "eu_ev_truss_first_ms": tf[1], "eu_ev_truss_again_ms": tf[2], "bytes_d2h_all": 12 * ne,
                        "note": "komb_truss_fetch after the timed steps, into touched host arrays, through the pinned staging buffers; the first fetch "
                                "that asks for endpoints makes the canonical edge list on the device (a pass over the symmetric CSR) and keeps it with the graph"}
+        if args.dump_outputs:
+            fetch_block["note"] += " (here after --dump-outputs' fetch, which made that list: eu_ev_truss_first_ms is not a first fetch)"
         del bufs3
         deg_h, core_h = acc.core_fetch()
         # CoreA on the workload's own degrees / coreness (a9 + a10: komb_corea_scores): device time of the rank kernels, wall time of the call
@@ -481,7 +528,8 @@ def main():
                                        "max_trussness": s2["max_trussness"],
                                        "phases_ms": {k: s2[k] for k in ("ms_prepare", "ms_tri_fill", "ms_sort", "ms_compact", "ms_peel", "ms_truss_local", "ms_gather")}}}
 
-    if rank == 0:
+    roofline = None
+    if rank == 0 and full:
         ab = algorithmic_bytes(st)
         shard = mode in ("sharded", "c4")
         sliced = mode == "sliced"
@@ -557,12 +605,13 @@ def main():
                 "kcore_launches": core_stats["core_launches"], "kcore_ms": core_ms,
             },
         }
+    if rank == 0:
         par = {
             "single": "single",
             "batch": f"batch: {world} independent graphs (seed + rank), one per GPU, no exchange on the data path",
             "replicas": f"same graph on {world} ranks, replicas: every rank runs the whole single-GPU path, no exchange",
             "sliced": (f"same graph on {world} ranks: preparation, support, index and peel on every rank, the canonical results gathered in "
-                       f"{world} slices, one per rank; no exchange on the data path (slices verified after the timed region: {slices_ok})"),
+                       f"{world} slices, one per rank; no exchange on the data path (slices verified after the timed region: {slices_ok if full else 'with --full only'})"),
             "c4": (f"same graph on {world} ranks: triangle-support counting sharded by task range + one all-reduce of the per-edge support "
                    f"vector ({exchange}); preparation, incidence fill, peel and gather replicated on every rank"),
             "sharded": (f"same graph on {world} ranks, edge-range partition: triangle-support counting sharded by task range + one all-reduce of "
@@ -584,15 +633,13 @@ def main():
             "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak" if mode == "batch" else "strong", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
-            # the same step with the graph's preparation resident (rounds 1-4's headline definition)
-            "value_resident": ne_total * args.steps / dt_res, "ms_per_step_resident": dt_res / args.steps * 1e3,
+            "full": full,
             "step_definition": "komb_truss_unprepare + komb_truss_run per step: preparation ((degree,id) renumbering, orientation, canonical "
-                               "map, lines, tasks) + support + index + peel + gather, from the resident symmetric CSR; *_resident: "
+                               "map, lines, tasks) + support + index + peel + gather, from the resident symmetric CSR; *_resident (--full): "
                                "komb_truss_run on a graph that kept its preparation",
             "config": {"workload": workload,
                        "nv": nv, "ne": ne, "triangles": st["triangles"], "alpha": alpha, "seed": seed,
-                       "max_degree": st["max_degree"], "max_trussness": st["max_trussness"],
-                       "max_coreness": core_stats["max_coreness"],
+                       "max_trussness": st["max_trussness"],
                        "truss_levels": st["truss_levels"], "truss_subrounds": st["truss_subrounds"],
                        "truss_scans": st["truss_scans"], "truss_launches": st["truss_launches"],
                        "index_layout": {0: "record stream", 2: "exact two-pass"}[st["index_layout"]],
@@ -601,35 +648,43 @@ def main():
                        "truss_local": {"edges": st["truss_local_units"], "index_entries": st["truss_local_items"],
                                        "sweeps": st["truss_local_sweeps"]},
                        "parallelism": par},
-            "phases_ms": phase, "phases_ms_resident": phase_res,
-            **({"alternatives": alternatives,
-                "multi_gpu_note": "never measured on more than one GPU by the builder (the pool grants one); DESIGN.md section 6 has the predicted N = 2/4/8 times"}
+            "phases_ms": phase,
+            **({"multi_gpu_note": "never measured on more than one GPU by the builder (the pool grants one); DESIGN.md section 6 has the predicted N = 2/4/8 times"}
                if world > 1 else {}),
-            "kcore": {"ms": core_ms, "first_call_ms": core_first_ms, "edges_per_s": ne / (core_ms * 1e-3) if core_ms > 0 else None,
-                      "levels": core_stats["core_levels"], "launches": core_stats["core_launches"],
-                      **({"sharded": {"exchanges": core_stats["shard_exchanges"], "ms_exchange": core_stats["ms_exchange"],
-                                      "exchange_words": core_stats["exchange_words"]}} if mode == "sharded" else {}),
-                      "local": {"vertices": core_stats["core_local_units"], "index_entries": core_stats["core_local_items"],
-                                "sweeps": core_stats["core_local_sweeps"], "ms": core_stats["ms_core_local"]},
-                      "alg_bytes": 16 * nv + 24 * ne,
-                      "GBps": (16 * nv + 24 * ne) / (core_ms * 1e-3) / 1e9 if core_ms > 0 else None,
-                      "frac_of_hbm_peak": (16 * nv + 24 * ne) / (core_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if core_ms > 0 else None},
-            "corea": corea,
             # the library reads no environment variable (ABI 7): its switches are per-context options nobody sets here
             "library_options_set": [],
-            "runtruss_faithful": faithful,
-            "results_fetch": fetch_block,
-            "first_call": first_call,
-            "c2": c2_block,
             "setup_s": {"generate": t_gen, "graph_build_incl_h2d": t_build, "device_build_ms": build_stats["ms_build"],
                         "h2d_ms": build_stats["ms_build_h2d"],
                         "note": "first graph build of the process: includes the HIP runtime's first large allocations and first launches of "
-                                "every build kernel (komb_create has loaded the code object); first_call.graph_build_ms is a second build in the "
-                                "same process.  The graph object holds the symmetric CSR only; the k-truss preparation is made inside the first "
+                                "every build kernel (komb_create has loaded the code object); first_call.graph_build_ms (--full) is a second build in "
+                                "the same process.  The graph object holds the symmetric CSR only; the k-truss preparation is made inside the first "
                                 "k-truss call (and inside every timed step here)"},
-            "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed at N=1 only
+        if full:
+            out["config"]["max_degree"] = st["max_degree"]
+            out["config"]["max_coreness"] = core_stats["max_coreness"]
+            out.update({
+                # the same step with the graph's preparation resident (rounds 1-4's headline definition)
+                "value_resident": ne_total * args.steps / dt_res, "ms_per_step_resident": dt_res / args.steps * 1e3,
+                "phases_ms_resident": phase_res,
+                **({"alternatives": alternatives} if world > 1 else {}),
+                "kcore": {"ms": core_ms, "first_call_ms": core_first_ms, "edges_per_s": ne / (core_ms * 1e-3) if core_ms > 0 else None,
+                          "levels": core_stats["core_levels"], "launches": core_stats["core_launches"],
+                          **({"sharded": {"exchanges": core_stats["shard_exchanges"], "ms_exchange": core_stats["ms_exchange"],
+                                          "exchange_words": core_stats["exchange_words"]}} if mode == "sharded" else {}),
+                          "local": {"vertices": core_stats["core_local_units"], "index_entries": core_stats["core_local_items"],
+                                    "sweeps": core_stats["core_local_sweeps"], "ms": core_stats["ms_core_local"]},
+                          "alg_bytes": 16 * nv + 24 * ne,
+                          "GBps": (16 * nv + 24 * ne) / (core_ms * 1e-3) / 1e9 if core_ms > 0 else None,
+                          "frac_of_hbm_peak": (16 * nv + 24 * ne) / (core_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if core_ms > 0 else None},
+                "corea": corea,
+                "runtruss_faithful": faithful,
+                "results_fetch": fetch_block,
+                "first_call": first_call,
+                "c2": c2_block,
+                "roofline": roofline,
+            })
+        if full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed at N=1 only
             out["cpu_baseline"] = cb = cpu_baseline(workload_csr, ne)
             # context, not credit: the GPU figure over the CPU port's, edges/s against edges/s (north_star asks for >= 10x)
             cb["gpu_over_cpu"] = {"1_thread": out["value"] / cb["value"],

@@ -89,7 +89,8 @@ def test_processes_sharing_one_gpu(built):
 @pytest.mark.parametrize("extra", [[], ["--c4-allreduce"], ["--same-graph", "--shard"], ["--replicas-sliced"], ["--replicas"], ["--batch"], ["--shard-peel"]])
 def test_bench_two_ranks_on_one_gpu(built, extra):
     """`python bench.py --gpus 2` started plainly: it spawns its two ranks itself (before anything has touched the GPU) and
-    rank 0 prints the one JSON line.  Both ranks share GPU 0 here (KOMB_BENCH_ONE_DEVICE=1, exchange over gloo).  Default
+    rank 0 prints the one JSON line (--full: with the resident figure, the other flows and k-core).  Both ranks share GPU 0
+    here (KOMB_BENCH_ONE_DEVICE=1, exchange over gloo).  Default
     (= --shard-peel): BASELINE configs[3] / north_star's partition -- the same graph on both ranks, the support count sharded +
     all-reduce, the peel sharded by edge range with one frontier exchange per sub-round, the other flows timed beside it;
     --c4-allreduce (--same-graph --shard is the older spelling): the support all-reduce only; --replicas-sliced: round 4's
@@ -98,7 +99,7 @@ def test_bench_two_ranks_on_one_gpu(built, extra):
     import json
     env = dict(os.environ, KOMB_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "tiny", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-build"] + extra
+           "--no-cpu-baseline", "--no-build", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

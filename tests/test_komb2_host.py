@@ -28,7 +28,7 @@ def run(args, env=None, **kw):
     return subprocess.run([KOMB2] + args, capture_output=True, text=True, env=e, **kw)
 
 
-def test_cli_contract(built):
+def test_cli_contract(built, tmp_path):
     r = run(["--version"])
     assert r.returncode == 0 and "2.0" in r.stdout
     r = run(["--help"])
@@ -40,7 +40,7 @@ def test_cli_contract(built):
     r = run(["-i", "a", "-j", "b", "-u", "c", "-t", "x"])
     assert r.returncode == 1 and "PARSE ERROR" in r.stderr
     # KOMB.py passes "-l -1" (KOMB.py:436-442): must parse as a value; then the missing file is reported
-    r = run(["-t", "2", "-l", "-1", "-o", "/tmp/komb2_cli_test", "-i", "/nonexistent/a.sam", "-j", "b", "-u", "c"])
+    r = run(["-t", "2", "-l", "-1", "-o", str(tmp_path / "out"), "-i", "/nonexistent/a.sam", "-j", "b", "-u", "c"])
     assert r.returncode == 1 and "File /nonexistent/a.sam could not be opened. Exiting..." in r.stderr
 
 

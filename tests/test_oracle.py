@@ -16,6 +16,14 @@ def O(built):
     return oracle
 
 
+@pytest.fixture(scope="module")
+def reference_runs():
+    """The reference binaries' answers on the inputs of the tests below (tests/golden/make_reference_runs.py)."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_runs.json")) as f:
+        return json.load(f)
+
+
 def _arr(x, dt=np.int32):
     return np.asarray(x, dtype=dt)
 
@@ -70,34 +78,36 @@ def test_kat_survey_appendix_d(O, golden):
     assert g["trussness"].count(4) == 6 and g["trussness"].count(2) == 6
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "corea_ref")),
-                    reason="oracle/_ref/corea_ref not built (reference absent)")
-def test_live_reference_corea_binary(O):
-    """Random (degree, coreness) vectors through the reference's CoreA.h, live."""
-    rng = np.random.default_rng(5)
-    for n in (1, 2, 17, 400):
-        core = rng.integers(0, 9, n).astype(np.int32)
-        deg = (core + rng.integers(0, 30, n)).astype(np.int32)
-        want = O.ref_corea_scores(deg, core)
+def test_live_reference_corea_binary(O, reference_runs):
+    """Random (degree, coreness) vectors through the reference's CoreA.h: its answers as recorded in
+    tests/golden/reference_runs.json (tests/golden/make_reference_runs.py), and live where oracle/_ref/corea_ref is built."""
+    live = O.ref_corea_path() is not None
+    for case in reference_runs["corea"]:
+        deg, core = _arr(case["degree"]), _arr(case["coreness"])
+        want = np.array([float.fromhex(h) for h in case["ref_scores_hex"]])
+        if live:
+            assert np.array_equal(O.ref_corea_scores(deg, core), want), len(deg)
         assert np.array_equal(O.corea_scores(deg, core, faithful=True), want)
         assert np.array_equal(O.corea_scores(deg, core, faithful=False), want)
 
 
-def test_reference_tsv_reader(O, tmp_path):
+def test_reference_tsv_reader(O, reference_runs, tmp_path):
     """a8: kcore.tsv written in the reference's format (src/graph.cpp:467,474) is
-    parsed by the reference's readKOMBOutput (src/CoreA.h:24-56) to the same scores."""
+    parsed by the reference's readKOMBOutput (src/CoreA.h:24-56) to the same scores
+    (its answer recorded in tests/golden/reference_runs.json; live where the binary is built)."""
+    rec = reference_runs["tsv"]
+    deg, core = rec["degree"], rec["coreness"]
+    want = np.array([float.fromhex(h) for h in rec["ref_scores_hex"]])
     exe = O.ref_corea_path()
-    if exe is None:
-        pytest.skip("reference binary absent")
-    deg = [4, 3, 3, 3, 6, 1, 1, 1, 1, 1, 0]
-    core = [3, 3, 3, 3, 1, 1, 1, 1, 1, 1, 0]
-    p = tmp_path / "kcore.tsv"
-    with open(p, "w") as f:
-        f.write("#VID\tName\tCoreness\tDegree\n")
-        for i, (d, c) in enumerate(zip(deg, core)):
-            f.write("%d\t%s\t%d\t%d\n" % (i, "u%d" % i, c, d))
-    out = subprocess.run([exe, "tsv", str(p)], capture_output=True, text=True, check=True).stdout.split()
-    assert np.array_equal(np.array([float(x) for x in out]), O.corea_scores(deg, core, faithful=True))
+    if exe is not None:
+        p = tmp_path / "kcore.tsv"
+        with open(p, "w") as f:
+            f.write("#VID\tName\tCoreness\tDegree\n")
+            for i, (d, c) in enumerate(zip(deg, core)):
+                f.write("%d\t%s\t%d\t%d\n" % (i, "u%d" % i, c, d))
+        out = subprocess.run([exe, "tsv", str(p)], capture_output=True, text=True, check=True).stdout.split()
+        assert np.array_equal(np.array([float(x) for x in out]), want)
+    assert np.array_equal(want, O.corea_scores(deg, core, faithful=True))
 
 
 def test_rankers_agree(O):
@@ -178,28 +188,23 @@ def test_all_cores_variant_matches(built):
             assert np.array_equal(O.trussness_native(rowptr, col, threads), want)
 
 
-def _merge_cases():
-    rng = np.random.default_rng(77)
-    cases = [(1, np.zeros((0, 2), np.int64)), (5, np.zeros((0, 2), np.int64)), (2, np.array([[0, 1]], np.int64)),
-             (6, np.stack(np.triu_indices(6, 1), axis=1).astype(np.int64))]
-    for _ in range(25):
-        nv = int(rng.integers(2, 250))
-        cases.append((nv, rng.integers(0, nv, (int(rng.integers(0, 8 * nv)), 2)).astype(np.int64)))
-    return cases
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "merge_ref")),
-                    reason="oracle/_ref/merge_ref not built (reference absent)")
-def test_run_merge_matches_reference_heap(O):
+def test_run_merge_matches_reference_heap(O, reference_runs):
     """a12 + a13: the oracle's restated indexed min-heap + runMerge loop against the REFERENCE's own HashIndexedMinHeap.h
-    compiled in place (oracle/_ref/merge_ref), unweighted and weighted with CoreA scores: removal order, sides, block size
-    and density bit for bit -- ties between equal priorities are decided by the heap's layout on both sides."""
-    for nv, uv in _merge_cases():
-        rowptr, col = O.simplify(nv, uv)
+    (oracle/_ref/merge_ref), unweighted and weighted with CoreA scores: removal order, sides, block size and density bit
+    for bit -- ties between equal priorities are decided by the heap's layout on both sides.  The reference's answers are
+    recorded in tests/golden/reference_runs.json; where oracle/_ref/merge_ref is built it is also run live."""
+    live = O.ref_merge_path() is not None
+    for case in reference_runs["merge"]:
+        nv = case["nv"]
+        rowptr, col = O.simplify(nv, np.asarray(case["raw"], dtype=np.int64).reshape(-1, 2))
         deg = O.degree(rowptr)
-        for susp in (None, O.corea_scores(deg, O.coreness(rowptr, col))):
-            a, b = O.run_merge(rowptr, col, susp), O.ref_run_merge(rowptr, col, susp)
-            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3], nv
+        for tag, susp in (("", None), ("w_", O.corea_scores(deg, O.coreness(rowptr, col)))):
+            want = (case[tag + "order"], case[tag + "side"], case[tag + "n_block"], float.fromhex(case[tag + "density_hex"]))
+            a = O.run_merge(rowptr, col, susp)
+            assert a[0].tolist() == want[0] and a[1].tolist() == want[1] and a[2] == want[2] and a[3] == want[3], (nv, tag)
+            if live:
+                b = O.ref_run_merge(rowptr, col, susp)
+                assert b[0].tolist() == want[0] and b[1].tolist() == want[1] and b[2] == want[2] and b[3] == want[3], (nv, tag)
 
 
 def test_golden_run_merge(O, golden):
