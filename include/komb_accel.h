@@ -115,7 +115,9 @@ int         komb_abi_version(void);
  * longer reads: ambient environment cannot change which engine a drop-in runs).  None changes a result.  name: FINISH
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
- * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG.  value NULL unsets. */
+ * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, and POISON ("0xWWWWWWWW": every device
+ * allocation the context hands out is filled with that 32-bit word first -- tests of reads of memory nothing wrote)
+ * (DESIGN.md section 8).  value NULL unsets. */
 int         komb_set_option(komb_ctx *ctx, const char *name, const char *value);
 
 /* ---- graph construction ------------------------------------------------ */

@@ -41,7 +41,19 @@ def gen_hug_edges(nv, n_cliques, alpha=2.6, seed=42):
 FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
-                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG")
+                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "POISON")
+
+# Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
+# instead of passing wherever 0 is the expected value.
+SENTINEL_I32 = -0x5A5A5A5B              # 0xA5A5A5A5
+
+
+def _out_i32(n):
+    return np.full(n, SENTINEL_I32, dtype=np.int32)
+
+
+def _out_f64(n):
+    return np.full(n, np.nan, dtype=np.float64)
 
 
 class KombAccel:
@@ -96,6 +108,7 @@ class KombAccel:
     # ---- graph (a1)
     def from_edges(self, nv, uv):
         uv = as_c(np.asarray(uv).reshape(-1, 2), np.int64)
+        self._sync_env_options()                         # (the build's own buffers come from the context too: POISON)
         self._check(self._lib.komb_graph_from_edges(self._ctx, nv, uv.shape[0], ptr(uv)))
         self._info()
         return self
@@ -103,6 +116,7 @@ class KombAccel:
     def from_csr(self, rowptr, col):
         rowptr = as_c(rowptr, np.int64)
         col = as_c(col, np.int32)
+        self._sync_env_options()
         self._check(self._lib.komb_graph_from_csr(self._ctx, len(rowptr) - 1, ptr(rowptr), ptr(col)))
         self._info()
         return self
@@ -113,8 +127,8 @@ class KombAccel:
         self.nv, self.ne = nv.value, ne.value
 
     def get_csr(self):
-        rowptr = np.zeros(self.nv + 1, dtype=np.int64)
-        col = np.zeros(2 * self.ne, dtype=np.int32)
+        rowptr = np.full(self.nv + 1, SENTINEL_I32, dtype=np.int64)
+        col = _out_i32(2 * self.ne)
         self._check(self._lib.komb_graph_get_csr(self._ctx, ptr(rowptr), ptr(col)))
         return rowptr, col
 
@@ -128,8 +142,8 @@ class KombAccel:
         self._check(self._lib.komb_set_shard_peel(self._ctx, 1 if on else 0))
 
     def core_fetch(self):
-        deg = np.zeros(self.nv, dtype=np.int32)
-        core = np.zeros(self.nv, dtype=np.int32)
+        deg = _out_i32(self.nv)
+        core = _out_i32(self.nv)
         self._check(self._lib.komb_core_fetch(self._ctx, ptr(deg), ptr(core)))
         return deg, core
 
@@ -177,13 +191,13 @@ class KombAccel:
     def truss_fetch(self, with_support=False):
         n = ctypes.c_int64()
         self._check(self._lib.komb_truss_count(self._ctx, ctypes.byref(n)))
-        eu = np.zeros(n.value, dtype=np.int32)
-        ev = np.zeros(n.value, dtype=np.int32)
-        tr = np.zeros(n.value, dtype=np.int32)
+        eu = _out_i32(n.value)
+        ev = _out_i32(n.value)
+        tr = _out_i32(n.value)
         self._check(self._lib.komb_truss_fetch(self._ctx, ptr(eu), ptr(ev), ptr(tr)))
         if not with_support:
             return eu, ev, tr
-        sup = np.zeros(n.value, dtype=np.int32)
+        sup = _out_i32(n.value)
         self._check(self._lib.komb_truss_fetch_support(self._ctx, ptr(sup)))
         return eu, ev, tr, sup
 
@@ -196,23 +210,27 @@ class KombAccel:
     def get_anomaly_score(self, degree, coreness):
         degree = as_c(degree, np.int32)
         coreness = as_c(coreness, np.int32)
-        score = np.zeros(len(degree), dtype=np.float64)
+        score = _out_f64(len(degree))
+        self._sync_env_options()
         self._check(self._lib.komb_corea_scores(self._ctx, ptr(degree), ptr(coreness), len(degree), ptr(score)))
         return score
 
     def fractional_ranks(self, degree, coreness):
         degree = as_c(degree, np.int32)
         coreness = as_c(coreness, np.int32)
-        rd = np.zeros(len(degree), dtype=np.float64)
-        rk = np.zeros(len(degree), dtype=np.float64)
+        rd = _out_f64(len(degree))
+        rk = _out_f64(len(degree))
+        self._sync_env_options()
         self._check(self._lib.komb_corea_ranks(self._ctx, ptr(degree), ptr(coreness), len(degree), ptr(rd), ptr(rk)))
         return rd, rk
 
     def densest_block(self, suspiciousness=None):
         """komb_densest_block: (order int32[2*nv], side int32[2*nv], n_block, max_density) of the resident graph."""
         n = int(self.nv)
-        order = np.zeros(max(2 * n, 1), dtype=np.int32)
-        side = np.zeros(max(2 * n, 1), dtype=np.int32)
+        # (every one of the 2*nv entries is written: the peel removes every row and every column node once)
+        order = _out_i32(max(2 * n, 1))
+        side = _out_i32(max(2 * n, 1))
+        self._sync_env_options()
         nb = ctypes.c_int64(0)
         dens = ctypes.c_double(0.0)
         susp = None if suspiciousness is None else as_c(suspiciousness, np.float64)

@@ -4,6 +4,7 @@
 // there is no CPU fallback (a missing device is KOMB_ERR_DEVICE).
 #include "common.h"
 
+#include <cerrno>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -170,6 +171,17 @@ int komb_degree_coreness(komb_ctx *ctx, int32_t *degree, int32_t *coreness)
 int komb_set_option(komb_ctx *ctx, const char *name, const char *value)
 {
     if (!ctx || !name || !*name) return KOMB_ERR_ARG;
+    if (!strcmp(name, "POISON")) {                   // every device allocation is filled with this word first (common.h: Poison)
+        Poison &p = ctx->pool.poison;
+        if (!value) { p.on = false; p.word = 0; }
+        else {
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long w = strtoull(value, &end, 0);
+            if (!*value || *end || errno || w > 0xFFFFFFFFull) KOMB_FAIL(ctx, KOMB_ERR_ARG, "option POISON=%s: expected a 32-bit word", value);
+            p.on = true; p.word = (uint32_t)w; p.stream = ctx->stream;
+        }
+    }
     if (value) ctx->options[name] = value; else ctx->options.erase(name);
     return KOMB_OK;
 }

@@ -137,6 +137,36 @@ struct EventSet {
 
 } // namespace komb
 
+// Option POISON (komb_set_option(ctx, "POISON", "0xWWWWWWWW")): while it is set, every device allocation the context hands
+// out -- new and reused pool blocks, the resident graph, the k-core results, the graph build's scratch -- is filled with that
+// 32-bit word before it is returned, so a kernel or host step that reads memory it never wrote sees garbage instead of the
+// zeros of a fresh page or the previous run's values (tests only; off, it costs one branch per allocation).  The fill is
+// waited for: the graph upload writes on the staging streams, not on the context's.
+struct Poison {
+    bool on = false;
+    uint32_t word = 0;
+    hipStream_t stream = nullptr;                    // the context's stream
+    hipError_t fill(void *p, size_t bytes) const
+    {
+        if (!on || !p || !bytes) return hipSuccess;
+        const size_t words = bytes / 4, rest = bytes % 4;
+        hipError_t e = hipSuccess;
+        if (words) e = hipMemsetD32Async((hipDeviceptr_t)p, (int)word, words, stream);
+        if (e == hipSuccess && rest) e = hipMemsetAsync((char *)p + 4 * words, (int)(word & 0xFFu), rest, stream);
+        return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+    }
+    hipError_t malloc(void **out, size_t bytes) const  // hipMalloc, then the fill (the one allocation path outside the pool)
+    {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return e;
+        e = fill(q, bytes);
+        if (e != hipSuccess) { (void)hipFree(q); return e; }
+        *out = q;
+        return hipSuccess;
+    }
+};
+
 // Caching device allocator: a step's scratch buffers are returned to the pool,
 // not to the driver, so steady-state steps perform no hipMalloc / hipFree.
 struct DevPool {
@@ -144,6 +174,7 @@ struct DevPool {
     std::vector<Block> blocks;
     size_t n_malloc = 0, n_trim = 0;                 // statistics (KOMB_POOL_DEBUG)
     double ms_malloc = 0.0;                          // host time inside hipMalloc
+    Poison poison;                                   // option POISON (above); also what the allocations outside the pool use
     hipError_t get(void **out, size_t bytes)
     {
         if (bytes == 0) bytes = 16;
@@ -151,7 +182,10 @@ struct DevPool {
         for (int i = 0; i < (int)blocks.size(); ++i)
             if (!blocks[i].used && blocks[i].bytes >= bytes && blocks[i].bytes <= bytes + bytes / 4 + 4096 &&
                 (best < 0 || blocks[i].bytes < blocks[best].bytes)) best = i;
-        if (best >= 0) { blocks[best].used = true; *out = blocks[best].p; return hipSuccess; }
+        if (best >= 0) {
+            if (poison.on) { const hipError_t e = poison.fill(blocks[best].p, blocks[best].bytes); if (e != hipSuccess) return e; }
+            blocks[best].used = true; *out = blocks[best].p; return hipSuccess;
+        }
         void *q = nullptr;
         ++n_malloc;
         const auto t0 = std::chrono::steady_clock::now();
@@ -164,6 +198,7 @@ struct DevPool {
             if (e != hipSuccess) return e;
         }
         blocks.push_back({q, bytes, true});
+        if (poison.on) { e = poison.fill(q, bytes); if (e != hipSuccess) { put(q); return e; } }
         *out = q;
         return hipSuccess;
     }
@@ -258,6 +293,10 @@ struct komb_ctx {
 
     komb_stats stats{};
 };
+
+// every device allocation outside the pool (the resident graph, the k-core results, the graph build's scratch): hipMalloc,
+// then the POISON fill when that option is set
+inline hipError_t dev_malloc(komb_ctx *ctx, void **out, size_t bytes) { return ctx->pool.poison.malloc(out, bytes); }
 
 // ---- options (komb_set_option): what the library used to read from KOMB_* environment variables.  The drop-in never sets
 // any; tests and measurements do, explicitly, per context.

@@ -225,11 +225,13 @@ __global__ __launch_bounds__(kBlock) void k_validate_csr(const uint32_t *__restr
 }
 
 struct Scratch {                                   // device scratch of one build: freed on every way out
+    komb_ctx *ctx;
     std::vector<void *> v;
+    explicit Scratch(komb_ctx *c) : ctx(c) {}
     template <class T> hipError_t get(T **out, size_t count)
     {
         void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
+        const hipError_t e = dev_malloc(ctx, &q, (count ? count : 1) * sizeof(T));
         if (e == hipSuccess) { v.push_back(q); *out = (T *)q; }
         return e;
     }
@@ -237,7 +239,7 @@ struct Scratch {                                   // device scratch of one buil
     ~Scratch() { for (void *q : v) if (q) (void)hipFree(q); }
 };
 
-template <class T> hipError_t resident(T **out, size_t count) { return hipMalloc((void **)out, (count ? count : 1) * sizeof(T)); }
+template <class T> hipError_t resident(komb_ctx *ctx, T **out, size_t count) { return dev_malloc(ctx, (void **)out, (count ? count : 1) * sizeof(T)); }
 
 inline int id_bits(int64_t nv)
 {
@@ -266,7 +268,7 @@ void warm_up(komb_ctx *ctx)
     const bool dbg = ctx->opts.verbosity > 1;
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t *d = nullptr;
-    if (hipMalloc(&d, 256) == hipSuccess) {
+    if (dev_malloc(ctx, (void **)&d, 256) == hipSuccess) {
         k_fill_u32<<<1, kBlock, 0, ctx->stream>>>(d, 64, 0u);        // the library's code object is loaded by its first launch
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipFree(d);
@@ -311,8 +313,8 @@ int graph_from_edges(komb_ctx *ctx, int64_t nv, int64_t n_raw, const int64_t *uv
     double ms_h2d = 0.0;
     struct Fail { komb_ctx *c; bool armed = true; ~Fail() { if (armed) graph_free(c); } } fail{ctx};   // nothing half-built stays behind
 
-    Scratch sc;
-    KOMB_HIP(ctx, resident(&ctx->d_o_rowptr, (size_t)nv + 1));
+    Scratch sc(ctx);
+    KOMB_HIP(ctx, resident(ctx, &ctx->d_o_rowptr, (size_t)nv + 1));
     int64_t ns = 0;
     uint64_t *d_k0 = nullptr, *d_k1 = nullptr;
     const bool dbg = ctx->opts.verbosity > 1 || ctx_flag(ctx, "BUILD_DEBUG");
@@ -352,11 +354,11 @@ int graph_from_edges(komb_ctx *ctx, int64_t nv, int64_t n_raw, const int64_t *uv
         ns = nu;
         if (ns > 0xFFFFFFF0ll) KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "graph has %lld slots; limit is 2^32-16", (long long)ns);
         if (ns / 2 > INT32_MAX - 16) KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "graph has %lld edges; limit is 2^31-16", (long long)(ns / 2));
-        KOMB_HIP(ctx, resident(&ctx->d_o_col, (size_t)ns));
+        KOMB_HIP(ctx, resident(ctx, &ctx->d_o_col, (size_t)ns));
         if (ns > 0) k_keys_to_csr<<<grid_for(ns), kBlock, 0, s>>>(other, ns, nv, vb, ctx->d_o_rowptr, ctx->d_o_col);
         else k_fill_u32<<<grid_for(nv + 1), kBlock, 0, s>>>(ctx->d_o_rowptr, nv + 1, 0u);
     } else {
-        KOMB_HIP(ctx, resident(&ctx->d_o_col, 1));
+        KOMB_HIP(ctx, resident(ctx, &ctx->d_o_col, 1));
         k_fill_u32<<<grid_for(nv + 1), kBlock, 0, s>>>(ctx->d_o_rowptr, nv + 1, 0u);
     }
     KOMB_HIP(ctx, hipStreamSynchronize(s));
@@ -382,10 +384,10 @@ int graph_from_csr(komb_ctx *ctx, int64_t nv, const int64_t *rowptr, const int32
     hipStream_t s = ctx->stream;
     const auto t_all = std::chrono::steady_clock::now();
     struct Fail { komb_ctx *c; bool armed = true; ~Fail() { if (armed) graph_free(c); } } fail{ctx};
-    Scratch sc;
+    Scratch sc(ctx);
     int64_t *d_rp64 = nullptr; int *d_bad = nullptr;
-    KOMB_HIP(ctx, resident(&ctx->d_o_rowptr, (size_t)nv + 1));
-    KOMB_HIP(ctx, resident(&ctx->d_o_col, (size_t)ns));
+    KOMB_HIP(ctx, resident(ctx, &ctx->d_o_rowptr, (size_t)nv + 1));
+    KOMB_HIP(ctx, resident(ctx, &ctx->d_o_col, (size_t)ns));
     KOMB_HIP(ctx, sc.get(&d_rp64, (size_t)nv + 1));
     KOMB_HIP(ctx, sc.get(&d_bad, 1));
     KOMB_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(int), s));

@@ -318,8 +318,10 @@ int truss_support_canonical(komb_ctx *ctx)
     hipStream_t s = ctx->stream;
     const int64_t m = ctx->t_ne;
     KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_sup, (size_t)m * sizeof(int32_t)));
+#ifndef KOMB_TEST_SKIP_SLICE_ZERO                                    // (negative control of the poisoned-memory tests only: tests/manual)
     if (ctx->t_k_lo) KOMB_HIP(ctx, hipMemsetAsync(ctx->d_t_sup, 0, (size_t)ctx->t_k_lo * sizeof(int32_t), s));
     if (ctx->t_k_hi < (uint32_t)m) KOMB_HIP(ctx, hipMemsetAsync(ctx->d_t_sup + ctx->t_k_hi, 0, ((size_t)m - ctx->t_k_hi) * sizeof(int32_t), s));
+#endif
     k_scatter_len<<<grid_for(m), kBlock, 0, s>>>(ctx->d_t_slice, ctx->prep.e2k, m, ctx->t_k_lo, ctx->t_k_hi, ctx->d_t_sup);
     KOMB_HIP(ctx, hipStreamSynchronize(s));
     ctx->t_sup_ready = true;
@@ -864,8 +866,10 @@ int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, kom
         // (komb_truss_run_slice: this rank's slice of the canonical edges only, zeros elsewhere)
         if (ctx->slice_world > 1) {
             shard_bounds((uint64_t)m, ctx->slice_rank, ctx->slice_world, &k_lo, &k_hi);
+#ifndef KOMB_TEST_SKIP_SLICE_ZERO
             if (k_lo) KOMB_HIP(ctx, hipMemsetAsync(ctx->d_t_truss, 0, (size_t)k_lo * sizeof(int32_t), s));
             if (k_hi < (uint32_t)m) KOMB_HIP(ctx, hipMemsetAsync(ctx->d_t_truss + k_hi, 0, ((size_t)m - k_hi) * sizeof(int32_t), s));
+#endif
         }
     } else {
         ctx->t_own_edges = true;

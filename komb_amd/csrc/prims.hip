@@ -35,7 +35,7 @@ int prim_sort_u64(komb_ctx *ctx, uint64_t *keys, uint64_t *tmp_keys, int64_t n, 
 int prim_unique_u64(komb_ctx *ctx, const uint64_t *in, uint64_t *out, int64_t n, int64_t *n_out)
 {
     long long *d_num = nullptr;
-    KOMB_HIP(ctx, hipMalloc(&d_num, sizeof(long long)));
+    KOMB_HIP(ctx, dev_malloc(ctx, (void **)&d_num, sizeof(long long)));
     size_t bytes = 0;
     hipError_t e = hipcub::DeviceSelect::Unique(nullptr, bytes, in, out, d_num, (int64_t)n, ctx->stream);
     TempBuf t(ctx);

@@ -12,8 +12,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _launch(mode, nproc, port, threads="2"):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS=threads)
+def _launch(mode, nproc, port, threads="2", extra_env=None):
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS=threads, **(extra_env or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "tests", "_dist_worker.py"), mode]
     return subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
@@ -55,6 +55,14 @@ def test_sharded_peel_on_gpu(built, world):
     ranges owned by the ranks, the frontier exchanged every sub-round -- against the oracle, 2 and 3 ranks (uneven ranges)."""
     r = _launch("peel", world, 29615 + world)
     assert r.returncode == 0 and f"DIST_OK peel {world}" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+@pytest.mark.gpu
+def test_sharded_peel_on_gpu_poisoned(built):
+    """The sharded core / truss peels of two ranks with every device allocation of both filled with 0xFFFFFFFF first (option
+    POISON, forwarded to the ranks as KOMB_POISON): a header, exchange buffer or cursor read before it is written shows."""
+    r = _launch("peel", 2, 29620, extra_env={"KOMB_POISON": "0xFFFFFFFF"})
+    assert r.returncode == 0 and "DIST_OK peel 2" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 @pytest.mark.gpu
