@@ -158,6 +158,24 @@ int komb_core_run_sharded(komb_ctx *ctx, int32_t rank, int32_t world, komb_allre
 int komb_core_fetch(komb_ctx *ctx, int32_t *degree /*[nv]*/, int32_t *coreness /*[nv]*/);
 int komb_degree_coreness(komb_ctx *ctx, int32_t *degree, int32_t *coreness);
 
+/* ---- onion decomposition ---------------------------------------------- */
+/* The onion decomposition of the resident simple graph (L. Hebert-Dufresne, J. A. Grochow, A. Allard, "Multi-scale
+ * structure and topological anomaly detection via a new network statistic: the onion decomposition", Scientific
+ * Reports 6, 31708 (2016)): per vertex, the synchronous layer inside its k-shell in which it is peeled -- exactly what
+ * networkx.onion_layers returns.  Layers are numbered from 1.  Isolated vertices (degree 0) all form layer 1 when there
+ * are any, and the other layers then start at 2.  Then, with k = 1 at first, until the graph is empty: if the smallest
+ * live degree is greater than k, k becomes it; the next layer is EVERY live vertex of live degree <= k; all of them are
+ * removed at once and their neighbours' live degrees decremented.  The k at which a vertex leaves is its coreness (0 if
+ * isolated), equal to komb_core_run's.
+ * komb_onion_run computes on the device and keeps the results in HBM; komb_onion_fetch copies layer[nv] and
+ * coreness[nv] out (either may be NULL); komb_onion_info reports the last run: the number of layers (the largest layer
+ * number, 0 for an empty graph), the largest coreness and the run's device time in ms.  The onion uses arrays of its
+ * own: it changes no k-core, k-truss or CoreA result and no komb_stats field.  No graph loaded: KOMB_ERR_ARG; fetch /
+ * info before a run on the current graph: KOMB_ERR_STATE. */
+int komb_onion_run(komb_ctx *ctx);
+int komb_onion_fetch(komb_ctx *ctx, int32_t *layer /*[nv]*/, int32_t *coreness /*[nv]*/);
+int komb_onion_info(komb_ctx *ctx, int64_t *n_layers, int32_t *max_coreness, double *ms);
+
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness
  * (src/graph.cpp:502, src/graph.cpp:508).  vmask (host, nv bytes, nullable)

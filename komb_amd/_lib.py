@@ -72,6 +72,9 @@ SIGNATURES = {
     "komb_set_shard_peel": (_i32, [_vp, ctypes.c_int32]),
     "komb_core_fetch": (_i32, [_vp, _vp, _vp]),
     "komb_degree_coreness": (_i32, [_vp, _vp, _vp]),
+    "komb_onion_run": (_i32, [_vp]),
+    "komb_onion_fetch": (_i32, [_vp, _vp, _vp]),
+    "komb_onion_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

@@ -152,6 +152,29 @@ class KombAccel:
         self.core_run()
         return self.core_fetch()
 
+    # ---- onion decomposition (per-vertex peel layer inside each k-shell; include/komb_accel.h)
+    def onion_run(self):
+        self._sync_env_options()
+        self._check(self._lib.komb_onion_run(self._ctx))
+
+    def onion_fetch(self):
+        """(layer, coreness) int32[nv] of the last komb_onion_run on this graph."""
+        layer = _out_i32(self.nv)
+        core = _out_i32(self.nv)
+        self._check(self._lib.komb_onion_fetch(self._ctx, ptr(layer), ptr(core)))
+        return layer, core
+
+    def run_onion(self):
+        """layer, coreness -- what networkx.onion_layers gives (layers from 1; isolated vertices are layer 1)."""
+        self.onion_run()
+        return self.onion_fetch()
+
+    def onion_info(self):
+        """{"n_layers", "max_coreness", "ms"} of the last komb_onion_run (ms: its device time)."""
+        n, k, ms = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_double()
+        self._check(self._lib.komb_onion_info(self._ctx, ctypes.byref(n), ctypes.byref(k), ctypes.byref(ms)))
+        return {"n_layers": n.value, "max_coreness": k.value, "ms": ms.value}
+
     # ---- k-truss (a5 + a6)
     def truss_run(self, vmask=None):
         if vmask is not None:

@@ -168,6 +168,35 @@ int komb_degree_coreness(komb_ctx *ctx, int32_t *degree, int32_t *coreness)
     return komb_core_fetch(ctx, degree, coreness);
 }
 
+int komb_onion_run(komb_ctx *ctx)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_onion_run: no graph loaded");
+    return onion_run(ctx);
+}
+
+int komb_onion_fetch(komb_ctx *ctx, int32_t *layer, int32_t *coreness)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_onion_fetch: no graph loaded");
+    if (!ctx->onion_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_onion_fetch: komb_onion_run has not completed on this graph");
+    if (ctx->nv == 0) return KOMB_OK;
+    if (layer) KOMB_HIP(ctx, staged_copy(ctx, layer, ctx->d_onion_layer, (size_t)ctx->nv * sizeof(int32_t), false));
+    if (coreness) KOMB_HIP(ctx, staged_copy(ctx, coreness, ctx->d_onion_core, (size_t)ctx->nv * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_onion_info(komb_ctx *ctx, int64_t *n_layers, int32_t *max_coreness, double *ms)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_onion_info: no graph loaded");
+    if (!ctx->onion_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_onion_info: komb_onion_run has not completed on this graph");
+    if (n_layers) *n_layers = ctx->onion_layers;
+    if (max_coreness) *max_coreness = ctx->onion_max_core;
+    if (ms) *ms = ctx->onion_ms;
+    return KOMB_OK;
+}
+
 int komb_set_option(komb_ctx *ctx, const char *name, const char *value)
 {
     if (!ctx || !name || !*name) return KOMB_ERR_ARG;

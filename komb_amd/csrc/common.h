@@ -270,6 +270,14 @@ struct komb_ctx {
     int32_t *d_core = nullptr;               // [nv] coreness (a3), ORIGINAL ids
     bool core_done = false;
 
+    // ---- onion decomposition results (onion.hip): arrays of their own, none of k-core's
+    int32_t *d_onion_layer = nullptr;        // [nv] layer, ORIGINAL ids
+    int32_t *d_onion_core = nullptr;         // [nv] coreness the vertex left at
+    int64_t onion_layers = 0;                // largest layer number of the last run
+    int32_t onion_max_core = 0;
+    double onion_ms = 0.0;                   // device time of the last run (HIP events)
+    bool onion_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                       // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -426,6 +434,7 @@ int prim_sort_pairs_u64_u32(komb_ctx *ctx, uint64_t *keys, uint64_t *keys_alt, u
 
 // ---- stages (each in its own translation unit)
 int core_run(komb_ctx *ctx, int rank = 0, int world = 1, komb_allreduce_fn fn = nullptr, void *user = nullptr, bool sharded = false);
+int onion_run(komb_ctx *ctx);
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);
 int corea_ranks(komb_ctx *ctx, const int32_t *deg, const int32_t *core, int64_t n, double *rank_deg, double *rank_key);

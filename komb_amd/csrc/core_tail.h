@@ -9,6 +9,8 @@
 // the set bits of row(v) & live mask, a decrement is an LDS atomic, a sub-round two __syncthreads().
 // Coreness is unique, so any peel order inside a level gives the same values as the general engine.
 // Nothing of the general engine's state is written before the tail has finished.
+// kLayers (the onion decomposition, onion.hip): every sub-round is a layer; each vertex's layer is the control block's
+// round at hand-over plus the index of the sub-round it leaves in, and the round moves on by the tail's sub-rounds.
 #pragma once
 
 #include "peel_dev.h"
@@ -75,11 +77,14 @@ __global__ __launch_bounds__(kBlock) void k_ctail_rows(const uint32_t *__restric
 }
 
 // ---- the tail peel
-__global__ __launch_bounds__(1024) void k_core_tail(PeelCtrl *ctrl, CoreTailBufs T, const int32_t *__restrict__ degw, int32_t *__restrict__ core)
+template <bool kLayers>
+__global__ __launch_bounds__(1024) void k_core_tail(PeelCtrl *ctrl, CoreTailBufs T, const int32_t *__restrict__ degw, int32_t *__restrict__ core,
+                                                    int32_t *__restrict__ layer)
 {
     __shared__ unsigned long long A[kCoreTailV * kCoreTailWords];     // 128 KB
     __shared__ int32_t deg[kCoreTailV];
     __shared__ uint16_t lvl[kCoreTailV];
+    __shared__ uint16_t sub[kLayers ? kCoreTailV : 1];                 // kLayers: the tail's sub-round the vertex leaves in
     __shared__ uint16_t q[2][kCoreTailV];
     __shared__ unsigned long long M[kCoreTailWords];                    // live and not (yet) in a frontier
     __shared__ uint32_t sh_cnt[2];
@@ -104,6 +109,7 @@ __global__ __launch_bounds__(1024) void k_core_tail(PeelCtrl *ctrl, CoreTailBufs
     __syncthreads();
 
     int32_t L = ctrl->level;
+    const int32_t round0 = ctrl->round;
     uint32_t alive = n, rounds = 0, levels = 0;
     int32_t max_level = ctrl->max_level;
     int sel = 0;
@@ -134,6 +140,7 @@ __global__ __launch_bounds__(1024) void k_core_tail(PeelCtrl *ctrl, CoreTailBufs
             for (uint32_t i = tid; i < ncur; i += 1024) {
                 const uint32_t v = q[sel][i];
                 lvl[v] = (uint16_t)L;
+                if constexpr (kLayers) sub[v] = (uint16_t)rounds;
                 atomicAnd(&M[v >> 6], ~(1ull << (v & 63)));
             }
             __syncthreads();
@@ -160,9 +167,13 @@ __global__ __launch_bounds__(1024) void k_core_tail(PeelCtrl *ctrl, CoreTailBufs
         L += 1;
     }
     __syncthreads();
-    if (state == 1 && tid < n) core[T.vlist[tid]] = (int32_t)lvl[tid];
+    if (state == 1 && tid < n) {
+        core[T.vlist[tid]] = (int32_t)lvl[tid];
+        if constexpr (kLayers) layer[T.vlist[tid]] = round0 + (int32_t)sub[tid];
+    }
     if (tid == 0) {
         ctrl->remaining = alive;
+        if constexpr (kLayers) ctrl->round = round0 + (int32_t)rounds;
         ctrl->n_levels += (int32_t)levels;
         ctrl->n_rounds += (int32_t)rounds;
         ctrl->n_scans += (int32_t)levels;

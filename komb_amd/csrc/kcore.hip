@@ -310,7 +310,7 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
         int64_t gm = ((int64_t)n_in + kBlock - 1) / kBlock;
         k_ctail_mark<<<(int)(gm < 1 ? 1 : (gm > 1024 ? 1024 : gm)), kBlock, 0, s>>>(list, n_in, ctx->d_core, T);
         k_ctail_rows<<<dim3(kCoreTailV, 8), kBlock, 0, s>>>(ctx->d_o_rowptr, ctx->d_o_col, T);
-        k_core_tail<<<1, 1024, 0, s>>>(d_ctrl, T, d_degw, ctx->d_core);
+        k_core_tail<false><<<1, 1024, 0, s>>>(d_ctrl, T, d_degw, ctx->d_core, nullptr);
         KOMB_HIP(ctx, d2h(ctx, &ctx->h_ctrl[0], d_ctrl, sizeof(PeelCtrl)));
         return KOMB_OK;
     };

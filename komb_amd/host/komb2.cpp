@@ -16,6 +16,8 @@
 //   KOMB_V1_ONLY=1      only those two stages, from the kcore.tsv + CoreA_anomaly.txt already in -o
 //   KOMB_TRUSS=1        re-enable the runTruss stage the reference has commented
 //                       out at src/graph.cpp:478 (writes truss_unitigs.fasta)
+//   KOMB_ONION=1        also write onion.tsv after kcore.tsv: #VID, Name, Coreness, Layer (the onion decomposition's
+//                       peel layer of every unitig, include/komb_accel.h); nothing else changes
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -727,6 +729,28 @@ int main(int argc, const char **argv)
             buf.append(tmp, (size_t)len);
         });
         fclose(kcf);
+    }
+
+    // onion decomposition (no counterpart in the reference; opt-in): onion.tsv beside kcore.tsv, one row per vertex in VID order
+    if (env_on("KOMB_ONION")) {
+        rc = komb_onion_run(ctx);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_onion_run", rc);
+        std::vector<int32_t> layer((size_t)nv), ocore((size_t)nv);
+        rc = komb_onion_fetch(ctx, layer.data(), ocore.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_onion_fetch", rc);
+        const std::string path = args.outdir + "/onion.tsv";
+        FILE *of = fopen(path.c_str(), "w+");
+        if (!of) file_not_found(path);
+        fprintf(of, "#VID\tName\tCoreness\tLayer\n");
+        write_rows(of, nv, args.threads, [&](int64_t i, std::string &buf) {
+            char tmp[48];
+            int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+            buf.append(tmp, (size_t)len);
+            buf.append(names.name[(size_t)i]);
+            len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", ocore[(size_t)i], layer[(size_t)i]);
+            buf.append(tmp, (size_t)len);
+        });
+        fclose(of);
     }
 
     // runTruss (src/graph.cpp:486-563) -- disabled in the reference at :478, opt-in here
