@@ -115,7 +115,8 @@ int         komb_abi_version(void);
  * longer reads: ambient environment cannot change which engine a drop-in runs).  None changes a result.  name: FINISH
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
- * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, and POISON ("0xWWWWWWWW": every device
+ * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, COMP_SAMPLE (0 | 1:
+ * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), and POISON ("0xWWWWWWWW": every device
  * allocation the context hands out is filled with that 32-bit word first -- tests of reads of memory nothing wrote)
  * (DESIGN.md section 8).  value NULL unsets. */
 int         komb_set_option(komb_ctx *ctx, const char *name, const char *value);
@@ -175,6 +176,34 @@ int komb_degree_coreness(komb_ctx *ctx, int32_t *degree, int32_t *coreness);
 int komb_onion_run(komb_ctx *ctx);
 int komb_onion_fetch(komb_ctx *ctx, int32_t *layer /*[nv]*/, int32_t *coreness /*[nv]*/);
 int komb_onion_info(komb_ctx *ctx, int64_t *n_layers, int32_t *max_coreness, double *ms);
+
+/* ---- connected components of a k-core / k-truss subgraph ---------------- */
+/* Which vertices belong together: the connected components of the subgraph a threshold k selects.
+ * label[v] is the SMALLEST original vertex id of v's component, -1 for a vertex that is not a member; size[v] is the
+ * number of vertices of v's component, 0 for a non-member.  Both are fully determined by the graph: they do not depend
+ * on the run, on an option or on scheduling.
+ * KOMB_COMP_CORE: k == 0 is the whole resident graph -- every vertex a member, an isolated vertex a component of size
+ * 1 -- and needs nothing but a graph; k >= 1 or KOMB_COMP_K_MAX reads the coreness komb_core_run left on this graph
+ * (KOMB_ERR_STATE if there is none; k-core is never run here).
+ * KOMB_COMP_TRUSS works on whatever the last k-truss call left, whole graph or vmask run alike (the endpoints are
+ * original ids either way); k <= 2 means every edge of that result.  Without a completed k-truss result on this graph,
+ * or after komb_truss_run_slice / a sharded run that materialised only part of the canonical edges: KOMB_ERR_STATE.
+ * Canonical endpoints of a whole-graph result that no fetch has asked for yet are made here as that fetch makes them.
+ * A result with no edges has no members, and k_used is 2 under KOMB_COMP_K_MAX.
+ * k above the maximum: no members, n_components == 0, largest == 0; not an error.  k < -1 or an unknown kind:
+ * KOMB_ERR_ARG.  No graph loaded: KOMB_ERR_ARG.  fetch / info before a run on the current graph: KOMB_ERR_STATE.
+ * komb_components_info: the kind, the threshold actually applied (KOMB_COMP_K_MAX resolved), members, components, the
+ * size of the largest component and the device time of the run in ms (the context's HIP-event timer).
+ * The result is a snapshot in arrays of its own: loading a graph drops it; later k-core / k-truss calls neither change
+ * nor invalidate it; a call changes no k-core, k-truss, onion or CoreA result and no komb_stats field.  Option
+ * COMP_SAMPLE (0 | 1) selects between the one-pass and the giant-component-skipping link of the core kind. */
+#define KOMB_COMP_CORE   0    /* members: vertices with coreness >= k; edges: resident edges between two members     */
+#define KOMB_COMP_TRUSS  1    /* edges: those of the last k-truss result with trussness >= k; members: their endpoints */
+#define KOMB_COMP_K_MAX (-1)  /* k = the largest coreness / the largest trussness of that result                        */
+int komb_components_run(komb_ctx *ctx, int32_t kind, int32_t k);
+int komb_components_fetch(komb_ctx *ctx, int32_t *label /*[nv]*/, int32_t *size /*[nv]*/);   /* either may be NULL */
+int komb_components_info(komb_ctx *ctx, int32_t *kind, int32_t *k_used, int64_t *n_members,
+                         int64_t *n_components, int64_t *largest, double *ms);               /* any may be NULL    */
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

@@ -41,7 +41,7 @@ def gen_hug_edges(nv, n_cliques, alpha=2.6, seed=42):
 FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
-                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "POISON")
+                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -174,6 +174,36 @@ class KombAccel:
         n, k, ms = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_double()
         self._check(self._lib.komb_onion_info(self._ctx, ctypes.byref(n), ctypes.byref(k), ctypes.byref(ms)))
         return {"n_layers": n.value, "max_coreness": k.value, "ms": ms.value}
+
+    # ---- connected components of a k-core / k-truss subgraph (include/komb_accel.h)
+    COMP_KINDS = {"core": _lib.KOMB_COMP_CORE, "truss": _lib.KOMB_COMP_TRUSS}
+
+    def components_run(self, kind, k):
+        """kind: "core" | "truss" (or the KOMB_COMP_* number); k: the threshold, -1 (KOMB_COMP_K_MAX) for the largest."""
+        self._sync_env_options()
+        self._check(self._lib.komb_components_run(self._ctx, self.COMP_KINDS.get(kind, kind), k))
+
+    def components_fetch(self):
+        """(label, size) int32[nv] of the last komb_components_run on this graph: the smallest vertex id of the vertex'
+        component (-1: not a member) and the component's number of vertices (0: not a member)."""
+        label = _out_i32(max(self.nv, 0))
+        size = _out_i32(max(self.nv, 0))
+        self._check(self._lib.komb_components_fetch(self._ctx, ptr(label), ptr(size)))
+        return label, size
+
+    def components_info(self):
+        """{"kind", "k_used", "n_members", "n_components", "largest", "ms"} of the last komb_components_run."""
+        kind, k = ctypes.c_int32(), ctypes.c_int32()
+        mem, comp, big, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        self._check(self._lib.komb_components_info(self._ctx, ctypes.byref(kind), ctypes.byref(k), ctypes.byref(mem),
+                                                   ctypes.byref(comp), ctypes.byref(big), ctypes.byref(ms)))
+        return {"kind": kind.value, "k_used": k.value, "n_members": mem.value, "n_components": comp.value,
+                "largest": big.value, "ms": ms.value}
+
+    def run_components(self, kind="core", k=0):
+        """label, size of the connected components of the k-core (kind="core") or of the last k-truss result's k-truss."""
+        self.components_run(kind, k)
+        return self.components_fetch()
 
     # ---- k-truss (a5 + a6)
     def truss_run(self, vmask=None):

@@ -197,6 +197,50 @@ int komb_onion_info(komb_ctx *ctx, int64_t *n_layers, int32_t *max_coreness, dou
     return KOMB_OK;
 }
 
+int komb_components_run(komb_ctx *ctx, int32_t kind, int32_t k)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_run: no graph loaded");
+    if (kind != KOMB_COMP_CORE && kind != KOMB_COMP_TRUSS) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_run: unknown kind %d", kind);
+    if (k < KOMB_COMP_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_run: bad threshold %d", k);
+    if (kind == KOMB_COMP_CORE) {
+        if (k != 0 && !ctx->core_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_run: komb_core_run has not completed on this graph");
+        if (k == KOMB_COMP_K_MAX) k = ctx->nv > 0 ? ctx->stats.max_coreness : 0;
+    } else {
+        if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_run: no completed k-truss result on this graph");
+        if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+            KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                      ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+        if (k == KOMB_COMP_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
+    }
+    return components_run(ctx, kind, k);
+}
+
+int komb_components_fetch(komb_ctx *ctx, int32_t *label, int32_t *size)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_fetch: no graph loaded");
+    if (!ctx->comp_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_fetch: komb_components_run has not completed on this graph");
+    if (ctx->nv == 0) return KOMB_OK;
+    if (label) KOMB_HIP(ctx, staged_copy(ctx, label, ctx->d_comp_label, (size_t)ctx->nv * sizeof(int32_t), false));
+    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_comp_size, (size_t)ctx->nv * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_components_info(komb_ctx *ctx, int32_t *kind, int32_t *k_used, int64_t *n_members, int64_t *n_components, int64_t *largest, double *ms)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_info: no graph loaded");
+    if (!ctx->comp_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_info: komb_components_run has not completed on this graph");
+    if (kind) *kind = ctx->comp_kind;
+    if (k_used) *k_used = ctx->comp_k;
+    if (n_members) *n_members = ctx->comp_members;
+    if (n_components) *n_components = ctx->comp_count;
+    if (largest) *largest = ctx->comp_largest;
+    if (ms) *ms = ctx->comp_ms;
+    return KOMB_OK;
+}
+
 int komb_set_option(komb_ctx *ctx, const char *name, const char *value)
 {
     if (!ctx || !name || !*name) return KOMB_ERR_ARG;

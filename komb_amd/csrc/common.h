@@ -278,6 +278,14 @@ struct komb_ctx {
     double onion_ms = 0.0;                   // device time of the last run (HIP events)
     bool onion_done = false;
 
+    // ---- connected components of a k-core / k-truss subgraph (components.hip): a snapshot in arrays of its own
+    int32_t *d_comp_label = nullptr;         // [nv] smallest ORIGINAL id of the vertex' component, -1 for a non-member
+    int32_t *d_comp_size = nullptr;          // [nv] vertices of that component, 0 for a non-member
+    int32_t comp_kind = 0, comp_k = 0;       // what the last run was asked for (k resolved)
+    int64_t comp_members = 0, comp_count = 0, comp_largest = 0;
+    double comp_ms = 0.0;                    // device time of the last run (HIP events)
+    bool comp_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                       // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -435,6 +443,7 @@ int prim_sort_pairs_u64_u32(komb_ctx *ctx, uint64_t *keys, uint64_t *keys_alt, u
 // ---- stages (each in its own translation unit)
 int core_run(komb_ctx *ctx, int rank = 0, int world = 1, komb_allreduce_fn fn = nullptr, void *user = nullptr, bool sharded = false);
 int onion_run(komb_ctx *ctx);
+int components_run(komb_ctx *ctx, int32_t kind, int32_t k);   // components.hip: kind checked, k resolved by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);
 int corea_ranks(komb_ctx *ctx, const int32_t *deg, const int32_t *core, int64_t n, double *rank_deg, double *rank_key);

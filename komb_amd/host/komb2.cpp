@@ -18,6 +18,13 @@
 //                       out at src/graph.cpp:478 (writes truss_unitigs.fasta)
 //   KOMB_ONION=1        also write onion.tsv after kcore.tsv: #VID, Name, Coreness, Layer (the onion decomposition's
 //                       peel layer of every unitig, include/komb_accel.h); nothing else changes
+//   KOMB_COMPONENTS=<k>|max   also write core_components.tsv after kcore.tsv (and onion.tsv): #VID, Name, Coreness,
+//                       Component, Size -- one row per unitig of coreness >= k (max: the largest coreness) in VID
+//                       order; Component is the Name of the member with the smallest VID of the unitig's connected
+//                       component in that k-core, Size its number of unitigs (komb_components_run).  VIDs depend on
+//                       -t, so only the partition by Name compares between runs.  With KOMB_TRUSS=1 also
+//                       truss_components.tsv (Trussness = the threshold in place of Coreness): the records of
+//                       truss_unitigs.fasta split into components.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -505,6 +512,32 @@ bool env_on(const char *name)
     return v && *v && strcmp(v, "0") != 0;
 }
 
+// KOMB_COMPONENTS: the last komb_components_run as a table, one row per member vertex in VID order
+template <class ValueFn>
+void write_components(komb_ctx *ctx, const std::string &path, const char *third, const Names &names, int64_t nv, int threads,
+                      ValueFn &&value)
+{
+    std::vector<int32_t> label((size_t)nv), size((size_t)nv);
+    const int rc = komb_components_fetch(ctx, label.data(), size.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_components_fetch", rc);
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\t%s\tComponent\tSize\n", third);
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (label[(size_t)i] < 0) return;
+        char tmp[48];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t", value(i));
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)label[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\n", size[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // CombineCoreA::run (src/CombineCoreA.h:16-43)
 void corea_stage(komb_ctx *ctx, const std::string &outdir, const std::vector<int32_t> &deg, const std::vector<int32_t> &core, int threads)
 {
@@ -753,6 +786,23 @@ int main(int argc, const char **argv)
         fclose(of);
     }
 
+    // connected components of a k-core (no counterpart in the reference; opt-in): core_components.tsv
+    const char *comp_env = getenv("KOMB_COMPONENTS");
+    const bool comp_on = comp_env && *comp_env;
+    if (comp_on) {
+        char *end = nullptr;
+        const bool comp_max = strcmp(comp_env, "max") == 0;
+        const long kc = comp_max ? (long)KOMB_COMP_K_MAX : strtol(comp_env, &end, 10);
+        if (!comp_max && (*end || kc < 0 || kc > 2147483647L)) {
+            fprintf(stderr, "komb2: KOMB_COMPONENTS=%s: expected a coreness threshold >= 0 or max\n", comp_env);
+            leave(EXIT_FAILURE);
+        }
+        rc = komb_components_run(ctx, KOMB_COMP_CORE, (int32_t)kc);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_components_run", rc);
+        write_components(ctx, args.outdir + "/core_components.tsv", "Coreness", names, nv, args.threads,
+                         [&](int64_t i) { return (int)core[(size_t)i]; });
+    }
+
     // runTruss (src/graph.cpp:486-563) -- disabled in the reference at :478, opt-in here
     if (env_on("KOMB_TRUSS") && nv > 0) {
         fprintf(stdout, "BUILDING K-TRUSS:\n");
@@ -783,6 +833,14 @@ int main(int argc, const char **argv)
         }
         fclose(tf);
         fprintf(stdout, "Found %d unitigs in %d-truss, saved at %s\n", count, threshold + 1, path.c_str());   // "+1" as src/graph.cpp:557
+        if (comp_on) {                                     // the records of truss_unitigs.fasta, split into components
+            rc = komb_components_run(ctx, KOMB_COMP_TRUSS, KOMB_COMP_K_MAX);
+            if (rc != KOMB_OK) die_accel(ctx, "komb_components_run", rc);
+            int32_t k_used = 0;
+            komb_components_info(ctx, nullptr, &k_used, nullptr, nullptr, nullptr, nullptr);
+            write_components(ctx, args.outdir + "/truss_components.tsv", "Trussness", names, nv, args.threads,
+                             [&](int64_t) { return (int)k_used; });
+        }
     }
     fprintf(stdout, "\nTime elapsed doing K-core decomposition: %.3f s\n", since(t0));
     fprintf(stdout, "Created Kcore\n");
