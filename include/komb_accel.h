@@ -205,6 +205,40 @@ int komb_components_fetch(komb_ctx *ctx, int32_t *label /*[nv]*/, int32_t *size 
 int komb_components_info(komb_ctx *ctx, int32_t *kind, int32_t *k_used, int64_t *n_members,
                          int64_t *n_components, int64_t *largest, double *ms);               /* any may be NULL    */
 
+/* ---- k-truss communities (triangle-connected edge classes) --------------- */
+/* Which EDGES of the k-truss belong together: the k-truss communities of Huang, Cheng, Qin, Tian, Yu ("Querying k-truss
+ * community in large and dynamic graphs", SIGMOD 2014).  Input: the last completed k-truss result, whole graph or vmask
+ * run alike -- ne_sub canonical edges (eu[i], ev[i]) with trussness truss[i] -- and a threshold k.
+ * Member edges: truss[i] >= k; 0 <= k <= 2 is run as 2 (every edge of the result) and k_used reports 2.  Two members are
+ * adjacent when they are two sides of a triangle whose three edges are all members; the communities are the classes of
+ * the transitive closure.  label[i] is the SMALLEST canonical edge index of i's community, -1 for a non-member;
+ * size[i] is the number of edges of that community, 0 for a non-member.  For k >= 3 no community has size 1; for
+ * k <= 2 an edge in no triangle is a community of size 1.  n_comm[v], per original vertex, is the number of distinct
+ * communities among the member edges at v (0 without one): a vertex may belong to several.  All three are fully
+ * determined by the graph: they do not depend on the run, on an option or on scheduling.
+ * k < -1: KOMB_ERR_ARG.  No graph loaded: KOMB_ERR_ARG.  Without a completed k-truss result on this graph, or after
+ * komb_truss_run_slice / a sharded run that materialised only part of the canonical edges: KOMB_ERR_STATE.  k above
+ * the largest trussness: no members, every count 0, not an error.  A result with no edges has no members, and k_used is
+ * 2 under KOMB_COMM_K_MAX.  Canonical endpoints of a whole-graph result that no fetch has asked for yet are made here
+ * as that fetch makes them.
+ * komb_truss_communities_info: the threshold applied, the member edges, the communities, the edges of the largest one,
+ * the vertices with n_comm > 1, and ms -- the device time of komb_truss_communities_run (labels and sizes) on the
+ * context's HIP-event timer.  n_comm and n_multi_vertices are made by the first fetch_vertices / info call that asks
+ * for them after a run (a sort of the distinct (vertex, label) pairs), outside ms.
+ * The result lives in arrays of its own, and its labels index the canonical edge list of the k-truss result it was
+ * computed from: whatever replaces or drops that result -- a new k-truss run of any kind, komb_truss_unprepare, a graph
+ * load -- drops the communities too, and fetch / info then return KOMB_ERR_STATE until the next run.  k-core, onion,
+ * components and CoreA calls neither change nor drop it.  A communities run changes no k-core, k-truss, onion,
+ * components or CoreA result, no komb_stats field and not the resident k-truss preparation.  Options COMM_SHORT /
+ * COMM_HEAVY (tests) move the lengths at which an edge's triangle search goes from its lane to its wave / to several
+ * workgroups; neither changes a result. */
+#define KOMB_COMM_K_MAX (-1)   /* k = the largest trussness of the result (2 when it has no edges) */
+int komb_truss_communities_run(komb_ctx *ctx, int32_t k);
+int komb_truss_communities_fetch(komb_ctx *ctx, int32_t *label /*[ne_sub]*/, int32_t *size /*[ne_sub]*/);  /* either may be NULL */
+int komb_truss_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm /*[nv]*/);
+int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edges, int64_t *n_communities,
+                                int64_t *largest, int64_t *n_multi_vertices, double *ms);                 /* any may be NULL */
+
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness
  * (src/graph.cpp:502, src/graph.cpp:508).  vmask (host, nv bytes, nullable)

@@ -51,6 +51,7 @@ class KombStats(ctypes.Structure):
 
 KOMB_CREATE_NULL_STREAM, KOMB_CREATE_NO_WARMUP, KOMB_CREATE_WARM_UPLOAD = 1, 2, 4
 KOMB_COMP_CORE, KOMB_COMP_TRUSS, KOMB_COMP_K_MAX = 0, 1, -1
+KOMB_COMM_K_MAX = -1
 
 
 # every symbol include/komb_accel.h declares: name -> (restype, argtypes)
@@ -80,6 +81,11 @@ SIGNATURES = {
     "komb_components_fetch": (_i32, [_vp, _vp, _vp]),
     "komb_components_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64),
                                     ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_truss_communities_run": (_i32, [_vp, ctypes.c_int32]),
+    "komb_truss_communities_fetch": (_i32, [_vp, _vp, _vp]),
+    "komb_truss_communities_fetch_vertices": (_i32, [_vp, _vp]),
+    "komb_truss_communities_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                           ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

@@ -41,7 +41,7 @@ def gen_hug_edges(nv, n_cliques, alpha=2.6, seed=42):
 FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
-                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "POISON")
+                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -258,6 +258,42 @@ class KombAccel:
         """(eu, ev, trussness) in canonical edge order, original vertex ids."""
         self.truss_run(vmask)
         return self.truss_fetch(with_support)
+
+    # ---- k-truss communities: triangle-connected classes of the k-truss' edges (include/komb_accel.h)
+    def truss_communities_run(self, k=3):
+        """k: the trussness threshold (0..2 run as 2), -1 (KOMB_COMM_K_MAX) for the largest trussness of the result."""
+        self._sync_env_options()
+        self._check(self._lib.komb_truss_communities_run(self._ctx, k))
+
+    def truss_communities_fetch(self):
+        """(label, size) int32[ne_sub] of the last komb_truss_communities_run, in the canonical edge order of the k-truss
+        result: the smallest canonical edge index of the edge's community (-1: not a member) and its number of edges."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_truss_count(self._ctx, ctypes.byref(n)))
+        label = _out_i32(max(n.value, 0))
+        size = _out_i32(max(n.value, 0))
+        self._check(self._lib.komb_truss_communities_fetch(self._ctx, ptr(label), ptr(size)))
+        return label, size
+
+    def truss_communities_fetch_vertices(self):
+        """n_comm int32[nv]: the number of distinct communities among the member edges at every vertex."""
+        n_comm = _out_i32(max(self.nv, 0))
+        self._check(self._lib.komb_truss_communities_fetch_vertices(self._ctx, ptr(n_comm)))
+        return n_comm
+
+    def truss_communities_info(self):
+        """{"k_used", "n_member_edges", "n_communities", "largest", "n_multi_vertices", "ms"} of the last run."""
+        k = ctypes.c_int32()
+        mem, comm, big, multi, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        self._check(self._lib.komb_truss_communities_info(self._ctx, ctypes.byref(k), ctypes.byref(mem), ctypes.byref(comm),
+                                                          ctypes.byref(big), ctypes.byref(multi), ctypes.byref(ms)))
+        return {"k_used": k.value, "n_member_edges": mem.value, "n_communities": comm.value, "largest": big.value,
+                "n_multi_vertices": multi.value, "ms": ms.value}
+
+    def run_truss_communities(self, k=3):
+        """label, size of the k-truss communities of the last k-truss result."""
+        self.truss_communities_run(k)
+        return self.truss_communities_fetch()
 
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):

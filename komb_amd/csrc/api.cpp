@@ -241,6 +241,60 @@ int komb_components_info(komb_ctx *ctx, int32_t *kind, int32_t *k_used, int64_t 
     return KOMB_OK;
 }
 
+int komb_truss_communities_run(komb_ctx *ctx, int32_t k)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_run: no graph loaded");
+    if (k < KOMB_COMM_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_run: bad threshold %d", k);
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    if (k == KOMB_COMM_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
+    if (k < 2) k = 2;
+    return communities_run(ctx, k);
+}
+
+int komb_truss_communities_fetch(komb_ctx *ctx, int32_t *label, int32_t *size)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_fetch: no graph loaded");
+    if (!ctx->comm_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_fetch: no communities of the current k-truss result");
+    const size_t bytes = (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0) * sizeof(int32_t);
+    if (bytes == 0) return KOMB_OK;
+    if (label) KOMB_HIP(ctx, staged_copy(ctx, label, ctx->d_comm_label, bytes, false));
+    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_comm_size, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_truss_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_fetch_vertices: no graph loaded");
+    if (!ctx->comm_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_fetch_vertices: no communities of the current k-truss result");
+    KOMB_TRY(communities_vertices(ctx));
+    if (ctx->nv > 0 && n_comm) KOMB_HIP(ctx, staged_copy(ctx, n_comm, ctx->d_comm_ncomm, (size_t)ctx->nv * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edges, int64_t *n_communities,
+                                int64_t *largest, int64_t *n_multi_vertices, double *ms)
+{
+    KOMB_TRY(require_device(ctx));
+    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_info: no graph loaded");
+    if (!ctx->comm_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_info: no communities of the current k-truss result");
+    if (n_multi_vertices) {                              // (the vertex pass runs when somebody asks for what it makes)
+        KOMB_TRY(communities_vertices(ctx));
+        *n_multi_vertices = ctx->comm_multi;
+    }
+    if (k_used) *k_used = ctx->comm_k;
+    if (n_member_edges) *n_member_edges = ctx->comm_members;
+    if (n_communities) *n_communities = ctx->comm_count;
+    if (largest) *largest = ctx->comm_largest;
+    if (ms) *ms = ctx->comm_ms;
+    return KOMB_OK;
+}
+
 int komb_set_option(komb_ctx *ctx, const char *name, const char *value)
 {
     if (!ctx || !name || !*name) return KOMB_ERR_ARG;

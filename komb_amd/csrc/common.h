@@ -286,6 +286,16 @@ struct komb_ctx {
     double comp_ms = 0.0;                    // device time of the last run (HIP events)
     bool comp_done = false;
 
+    // ---- k-truss communities (communities.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
+    // computed from and dropped with it (truss_free)
+    int32_t *d_comm_label = nullptr;         // [t_ne] smallest canonical edge index of the edge's community, -1 for a non-member
+    int32_t *d_comm_size = nullptr;          // [t_ne] edges of that community, 0 for a non-member
+    int32_t *d_comm_ncomm = nullptr;         // [nv] distinct communities at the vertex: made by the first fetch_vertices / info after a run
+    int32_t comm_k = 0;                      // the threshold of the last run (resolved)
+    int64_t comm_members = 0, comm_count = 0, comm_largest = 0, comm_multi = 0;
+    double comm_ms = 0.0, comm_ms_vertices = 0.0;   // device time of the run | of the vertex pass (HIP events)
+    bool comm_done = false, comm_v_ready = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                       // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -444,6 +454,9 @@ int prim_sort_pairs_u64_u32(komb_ctx *ctx, uint64_t *keys, uint64_t *keys_alt, u
 int core_run(komb_ctx *ctx, int rank = 0, int world = 1, komb_allreduce_fn fn = nullptr, void *user = nullptr, bool sharded = false);
 int onion_run(komb_ctx *ctx);
 int components_run(komb_ctx *ctx, int32_t kind, int32_t k);   // components.hip: kind checked, k resolved by the caller
+int communities_run(komb_ctx *ctx, int32_t k);                // communities.hip: k checked and resolved by the caller
+int communities_vertices(komb_ctx *ctx);                      // communities.hip: n_comm[] and the multi-community count, made on first request
+void communities_drop(komb_ctx *ctx);                         // communities.hip: the result goes with the k-truss result it indexes
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);
 int corea_ranks(komb_ctx *ctx, const int32_t *deg, const int32_t *core, int64_t n, double *rank_deg, double *rank_key);

@@ -29,6 +29,7 @@
 // Every access to parent[] inside the linking launches is a relaxed agent-scope atomic load / store (it bypasses the
 // L1, so a walk sees a hook soon, and no dirty line of parent[] waits in an L2 behind an atomic of another XCD).
 #include "common.h"
+#include "unionfind_dev.h"   // pload / pstore, comp_find, comp_find_ro, comp_link (shared with communities.hip)
 
 namespace komb {
 
@@ -48,42 +49,6 @@ struct CompCtl {                            // 64 bytes, zeroed before every run
     uint32_t pad[11];
 };
 static_assert(sizeof(CompCtl) == 64, "CompCtl layout");
-
-__device__ __forceinline__ int32_t pload(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void pstore(int32_t *p, int32_t x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root above x as far as this lane can tell (a stale read ends the walk early: at a vertex of the same tree);
-// path splitting on the way: every vertex passed is pointed at what was read as its grandparent
-__device__ __forceinline__ int32_t comp_find(int32_t *parent, int32_t x)
-{
-    int32_t p = pload(parent + x);
-    while (p < x) {
-        const int32_t gp = pload(parent + p);
-        if (gp < p) pstore(parent + x, gp);  // x is a non-root for good; gp was on the way up from it
-        x = p; p = gp;
-    }
-    return x;
-}
-
-// the same walk without stores (the labelling launch: a word of parent[] is then written by its own vertex' lane only)
-__device__ __forceinline__ int32_t comp_find_ro(const int32_t *parent, int32_t x)
-{
-    int32_t p = pload(parent + x);
-    while (p < x) { x = p; p = pload(parent + x); }
-    return x;
-}
-
-__device__ __forceinline__ void comp_link(int32_t *parent, int32_t u, int32_t v)
-{
-    int32_t a = comp_find(parent, u), b = comp_find(parent, v);
-    while (a != b) {
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;               // hi was a root: it hangs under the smaller id now
-        a = comp_find(parent, old);          // hi had been hooked already: go on from its parent (< hi)
-        b = lo;
-    }
-}
 
 // parent[v] = v; flag[v] = member (core kind: coreness >= k, everyone when k == 0; truss kind: 0, the edge pass sets it); cnt[v] = 0
 __global__ void k_comp_init(uint32_t nv, const int32_t *__restrict__ core, int32_t k, bool all, bool none,

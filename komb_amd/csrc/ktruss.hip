@@ -277,6 +277,7 @@ struct TrussLocal {
 
 void truss_free(komb_ctx *ctx)
 {
+    communities_drop(ctx);                   // (its labels index this result's canonical edges)
     if (ctx->t_own_edges) { ctx->pool.put(ctx->d_t_eu); ctx->pool.put(ctx->d_t_ev); }
     ctx->pool.put(ctx->d_t_truss);
     ctx->pool.put(ctx->d_t_sup);

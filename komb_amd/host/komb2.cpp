@@ -25,6 +25,14 @@
 //                       -t, so only the partition by Name compares between runs.  With KOMB_TRUSS=1 also
 //                       truss_components.tsv (Trussness = the threshold in place of Coreness): the records of
 //                       truss_unitigs.fasta split into components.  Nothing else changes.
+//   KOMB_COMMUNITIES=<k>|max  with KOMB_TRUSS=1: also write, after the truss stage, the k-truss communities of its result
+//                       (komb_truss_communities_run: the classes of the edges of trussness >= k, max: the largest
+//                       trussness, under "two sides of a triangle of such edges").  truss_communities.tsv: #VID_U,
+//                       Name_U, VID_V, Name_V, Trussness, Community, Size -- one row per member edge in canonical
+//                       order, Community numbering the communities from 0 in the order of their first edge, Size the
+//                       community's number of edges.  truss_community_vertices.tsv: #VID, Name, Communities -- the
+//                       unitigs with a member edge and the number of communities they belong to (more than one: a
+//                       unitig shared between dense regions).  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -538,6 +546,52 @@ void write_components(komb_ctx *ctx, const std::string &path, const char *third,
     fclose(fp);
 }
 
+// KOMB_COMMUNITIES: the last komb_truss_communities_run as two tables (edges in canonical order, vertices in VID order)
+void write_communities(komb_ctx *ctx, const std::string &outdir, const Names &names, int64_t nv, int threads,
+                       const std::vector<int32_t> &eu, const std::vector<int32_t> &ev, const std::vector<int32_t> &tr)
+{
+    const int64_t ne = (int64_t)tr.size();
+    std::vector<int32_t> label((size_t)ne), size((size_t)ne), rank((size_t)ne, -1), n_comm((size_t)nv);
+    int rc = komb_truss_communities_fetch(ctx, label.data(), size.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_truss_communities_fetch", rc);
+    rc = komb_truss_communities_fetch_vertices(ctx, n_comm.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_truss_communities_fetch_vertices", rc);
+    int32_t next = 0;
+    for (int64_t i = 0; i < ne; ++i)                       // a label is the community's first edge: ranks in ascending label order
+        if (label[(size_t)i] == (int32_t)i) rank[(size_t)i] = next++;
+    std::string path = outdir + "/truss_communities.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID_U\tName_U\tVID_V\tName_V\tTrussness\tCommunity\tSize\n");
+    write_rows(fp, ne, threads, [&](int64_t i, std::string &buf) {
+        if (label[(size_t)i] < 0) return;
+        char tmp[64];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)eu[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)eu[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t", (int)ev[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)ev[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\t%d\n", (int)tr[(size_t)i], (int)rank[(size_t)label[(size_t)i]], (int)size[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    path = outdir + "/truss_community_vertices.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tCommunities\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (n_comm[(size_t)i] < 1) return;
+        char tmp[48];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\n", (int)n_comm[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // CombineCoreA::run (src/CombineCoreA.h:16-43)
 void corea_stage(komb_ctx *ctx, const std::string &outdir, const std::vector<int32_t> &deg, const std::vector<int32_t> &core, int threads)
 {
@@ -803,6 +857,19 @@ int main(int argc, const char **argv)
                          [&](int64_t i) { return (int)core[(size_t)i]; });
     }
 
+    // k-truss communities of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
+    const char *comm_env = getenv("KOMB_COMMUNITIES");
+    const bool comm_on = comm_env && *comm_env;
+    long comm_k = (long)KOMB_COMM_K_MAX;
+    if (comm_on && strcmp(comm_env, "max") != 0) {
+        char *end = nullptr;
+        comm_k = strtol(comm_env, &end, 10);
+        if (*end || comm_k < 0 || comm_k > 2147483647L) {
+            fprintf(stderr, "komb2: KOMB_COMMUNITIES=%s: expected a trussness threshold >= 0 or max\n", comm_env);
+            leave(EXIT_FAILURE);
+        }
+    }
+
     // runTruss (src/graph.cpp:486-563) -- disabled in the reference at :478, opt-in here
     if (env_on("KOMB_TRUSS") && nv > 0) {
         fprintf(stdout, "BUILDING K-TRUSS:\n");
@@ -840,6 +907,11 @@ int main(int argc, const char **argv)
             komb_components_info(ctx, nullptr, &k_used, nullptr, nullptr, nullptr, nullptr);
             write_components(ctx, args.outdir + "/truss_components.tsv", "Trussness", names, nv, args.threads,
                              [&](int64_t) { return (int)k_used; });
+        }
+        if (comm_on) {
+            rc = komb_truss_communities_run(ctx, (int32_t)comm_k);
+            if (rc != KOMB_OK) die_accel(ctx, "komb_truss_communities_run", rc);
+            write_communities(ctx, args.outdir, names, nv, args.threads, eu, ev, tr);
         }
     }
     fprintf(stdout, "\nTime elapsed doing K-core decomposition: %.3f s\n", since(t0));
