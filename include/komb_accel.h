@@ -205,6 +205,37 @@ int komb_components_fetch(komb_ctx *ctx, int32_t *label /*[nv]*/, int32_t *size 
 int komb_components_info(komb_ctx *ctx, int32_t *kind, int32_t *k_used, int64_t *n_members,
                          int64_t *n_components, int64_t *largest, double *ms);               /* any may be NULL    */
 
+/* ---- component hierarchy: the nesting forest of the k-core / k-truss components ---- */
+/* All thresholds at once: which component of G_k lies inside which component of G_(k-1).
+ * KOMB_COMP_CORE: G_k is the subgraph induced by the vertices of coreness >= k, k >= 0 (G_0: the whole graph, isolated
+ * vertices included); lvl(v) = coreness(v).  KOMB_COMP_TRUSS: G_k is the edges of trussness >= k of the last complete
+ * k-truss result, whole graph or vmask run alike, with their endpoints, k >= 2; lvl(v) = the largest trussness of an edge
+ * at v, and a vertex without an edge in that result is no member.
+ * A NODE is a pair (k, S): S is the vertex set of a connected component of G_k and not the vertex set of a component of
+ * G_(k+1) -- S holds a vertex of level exactly k, or (truss kind only) joins two or more components of G_(k+1) by edges
+ * of trussness k.  rep = the smallest original vertex id in S.  Nodes are numbered 0 .. n_nodes-1 in ascending (k, rep)
+ * order.  parent = the node (k', S') with S inside S' and the largest k' < k, -1 when there is none (S is then a whole
+ * component of G_0 / G_2); parent[i] < i always.  size[i] = |S|; shell[i] = the vertices v with node[v] == i; size[i] ==
+ * shell[i] + the sizes of i's children.  node[v] = the node (lvl(v), the component of G_lvl(v) that holds v), -1 for a
+ * non-member.  Everything is determined by the graph: it does not depend on the run, on an option or on scheduling.
+ * It follows that for a member v of G_k, walking up from node[v] while the parent's k is still >= k ends at the node
+ * whose rep is label[v] of komb_components_run(kind, k).
+ * komb_hierarchy_info: the kind, nodes, nodes without a parent, the largest node level (without nodes: 0 / 2), depth =
+ * the most nodes on a path from a root down (0 without nodes) and the device time of the run in ms.
+ * No graph loaded or an unknown kind: KOMB_ERR_ARG.  Core kind without a komb_core_run result on this graph (k-core is
+ * never run here), truss kind without a complete k-truss result (none yet, after komb_truss_run_slice, a sharded partial
+ * result or komb_truss_unprepare), count / fetch / info before a run on the current graph: KOMB_ERR_STATE.  A failed
+ * call leaves the previous result readable.  The empty graph has no nodes; not an error.
+ * The result is a snapshot in arrays of its own: loading a graph drops it; later k-core, k-truss, onion, components and
+ * communities calls neither change nor drop it; a run changes none of their results and no komb_stats field. */
+int komb_hierarchy_run(komb_ctx *ctx, int32_t kind);                 /* KOMB_COMP_CORE | KOMB_COMP_TRUSS */
+int komb_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes);
+int komb_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent,
+                               int32_t *size, int32_t *shell);       /* [n_nodes] each, any may be NULL */
+int komb_hierarchy_fetch_vertices(komb_ctx *ctx, int32_t *node /*[nv]*/);
+int komb_hierarchy_info(komb_ctx *ctx, int32_t *kind, int64_t *n_nodes, int64_t *n_roots,
+                        int32_t *k_max, int32_t *depth, double *ms); /* any may be NULL */
+
 /* ---- k-truss communities (triangle-connected edge classes) --------------- */
 /* Which EDGES of the k-truss belong together: the k-truss communities of Huang, Cheng, Qin, Tian, Yu ("Querying k-truss
  * community in large and dynamic graphs", SIGMOD 2014).  Input: the last completed k-truss result, whole graph or vmask

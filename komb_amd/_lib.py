@@ -81,6 +81,12 @@ SIGNATURES = {
     "komb_components_fetch": (_i32, [_vp, _vp, _vp]),
     "komb_components_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64),
                                     ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_hierarchy_run": (_i32, [_vp, ctypes.c_int32]),
+    "komb_hierarchy_count": (_i32, [_vp, ctypes.POINTER(_i64)]),
+    "komb_hierarchy_fetch_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "komb_hierarchy_fetch_vertices": (_i32, [_vp, _vp]),
+    "komb_hierarchy_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_communities_run": (_i32, [_vp, ctypes.c_int32]),
     "komb_truss_communities_fetch": (_i32, [_vp, _vp, _vp]),
     "komb_truss_communities_fetch_vertices": (_i32, [_vp, _vp]),

@@ -205,6 +205,42 @@ class KombAccel:
         self.components_run(kind, k)
         return self.components_fetch()
 
+    # ---- component hierarchy: the nesting forest of the k-core / k-truss components over all k (include/komb_accel.h)
+    HIER_FIELDS = ("k", "rep", "parent", "size", "shell")
+
+    def hierarchy_run(self, kind="core"):
+        """kind: "core" | "truss" (or the KOMB_COMP_* number); needs the coreness / a complete k-truss result on this graph."""
+        self._sync_env_options()
+        self._check(self._lib.komb_hierarchy_run(self._ctx, self.COMP_KINDS.get(kind, kind)))
+
+    def hierarchy_fetch_nodes(self):
+        """{"k", "rep", "parent", "size", "shell"}: int32[n_nodes] each, nodes in ascending (k, rep) order."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_hierarchy_count(self._ctx, ctypes.byref(n)))
+        out = {name: _out_i32(max(n.value, 0)) for name in self.HIER_FIELDS}
+        self._check(self._lib.komb_hierarchy_fetch_nodes(self._ctx, *(ptr(out[name]) for name in self.HIER_FIELDS)))
+        return out
+
+    def hierarchy_fetch_vertices(self):
+        """node int32[nv]: the node of every vertex (its level's component), -1 for a non-member (truss kind only)."""
+        node = _out_i32(max(self.nv, 0))
+        self._check(self._lib.komb_hierarchy_fetch_vertices(self._ctx, ptr(node)))
+        return node
+
+    def hierarchy_info(self):
+        """{"kind", "n_nodes", "n_roots", "k_max", "depth", "ms"} of the last komb_hierarchy_run."""
+        kind, kmax, depth = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        n, roots, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        self._check(self._lib.komb_hierarchy_info(self._ctx, ctypes.byref(kind), ctypes.byref(n), ctypes.byref(roots),
+                                                  ctypes.byref(kmax), ctypes.byref(depth), ctypes.byref(ms)))
+        return {"kind": kind.value, "n_nodes": n.value, "n_roots": roots.value, "k_max": kmax.value, "depth": depth.value,
+                "ms": ms.value}
+
+    def run_hierarchy(self, kind="core"):
+        """(nodes, node): the dict of hierarchy_fetch_nodes and the per-vertex node array of the hierarchy of `kind`."""
+        self.hierarchy_run(kind)
+        return self.hierarchy_fetch_nodes(), self.hierarchy_fetch_vertices()
+
     # ---- k-truss (a5 + a6)
     def truss_run(self, vmask=None):
         if vmask is not None:

@@ -241,6 +241,70 @@ int komb_components_info(komb_ctx *ctx, int32_t *kind, int32_t *k_used, int64_t 
     return KOMB_OK;
 }
 
+// the hierarchy entry points ask for the graph first: a context without one says so whether or not it has a device
+#define KOMB_HIER_ENTER(ctx, what)                                                         \
+    do {                                                                                   \
+        if (!(ctx)) return KOMB_ERR_ARG;                                                   \
+        if ((ctx)->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, what ": no graph loaded");         \
+        KOMB_TRY(require_device(ctx));                                                     \
+    } while (0)
+
+int komb_hierarchy_run(komb_ctx *ctx, int32_t kind)
+{
+    KOMB_HIER_ENTER(ctx, "komb_hierarchy_run");
+    if (kind != KOMB_COMP_CORE && kind != KOMB_COMP_TRUSS) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_hierarchy_run: unknown kind %d", kind);
+    if (kind == KOMB_COMP_CORE) {
+        if (!ctx->core_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_run: komb_core_run has not completed on this graph");
+    } else {
+        if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_run: no completed k-truss result on this graph");
+        if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+            KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                      ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    }
+    return hierarchy_run(ctx, kind);
+}
+
+int komb_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes)
+{
+    KOMB_HIER_ENTER(ctx, "komb_hierarchy_count");
+    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_count: komb_hierarchy_run has not completed on this graph");
+    if (n_nodes) *n_nodes = ctx->hier_nodes;
+    return KOMB_OK;
+}
+
+int komb_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent, int32_t *size, int32_t *shell)
+{
+    KOMB_HIER_ENTER(ctx, "komb_hierarchy_fetch_nodes");
+    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_fetch_nodes: komb_hierarchy_run has not completed on this graph");
+    if (ctx->hier_nodes == 0) return KOMB_OK;
+    const size_t stride = (size_t)(ctx->nv > 0 ? ctx->nv : 1), bytes = (size_t)ctx->hier_nodes * sizeof(int32_t);
+    int32_t *const out[5] = {k, rep, parent, size, shell};
+    for (int i = 0; i < 5; ++i)
+        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_hier_nodes + i * stride, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_hierarchy_fetch_vertices(komb_ctx *ctx, int32_t *node)
+{
+    KOMB_HIER_ENTER(ctx, "komb_hierarchy_fetch_vertices");
+    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_fetch_vertices: komb_hierarchy_run has not completed on this graph");
+    if (ctx->nv > 0 && node) KOMB_HIP(ctx, staged_copy(ctx, node, ctx->d_hier_vnode, (size_t)ctx->nv * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_hierarchy_info(komb_ctx *ctx, int32_t *kind, int64_t *n_nodes, int64_t *n_roots, int32_t *k_max, int32_t *depth, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_hierarchy_info");
+    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_info: komb_hierarchy_run has not completed on this graph");
+    if (kind) *kind = ctx->hier_kind;
+    if (n_nodes) *n_nodes = ctx->hier_nodes;
+    if (n_roots) *n_roots = ctx->hier_roots;
+    if (k_max) *k_max = ctx->hier_kmax;
+    if (depth) *depth = ctx->hier_depth;
+    if (ms) *ms = ctx->hier_ms;
+    return KOMB_OK;
+}
+
 int komb_truss_communities_run(komb_ctx *ctx, int32_t k)
 {
     KOMB_TRY(require_device(ctx));

@@ -286,6 +286,14 @@ struct komb_ctx {
     double comp_ms = 0.0;                    // device time of the last run (HIP events)
     bool comp_done = false;
 
+    // ---- component hierarchy (hierarchy.hip): the nesting forest of the k-core / k-truss components, a snapshot in arrays of its own
+    int32_t *d_hier_nodes = nullptr;         // [5 * max(nv, 1)] k | rep | parent | size | shell, each a block of max(nv, 1) words with hier_nodes in use
+    int32_t *d_hier_vnode = nullptr;         // [nv] the node of every vertex, -1 for a non-member
+    int32_t hier_kind = 0, hier_kmax = 0, hier_depth = 0;
+    int64_t hier_nodes = 0, hier_roots = 0;
+    double hier_ms = 0.0;                    // device time of the last run (HIP events)
+    bool hier_done = false;
+
     // ---- k-truss communities (communities.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
     int32_t *d_comm_label = nullptr;         // [t_ne] smallest canonical edge index of the edge's community, -1 for a non-member
@@ -454,6 +462,7 @@ int prim_sort_pairs_u64_u32(komb_ctx *ctx, uint64_t *keys, uint64_t *keys_alt, u
 int core_run(komb_ctx *ctx, int rank = 0, int world = 1, komb_allreduce_fn fn = nullptr, void *user = nullptr, bool sharded = false);
 int onion_run(komb_ctx *ctx);
 int components_run(komb_ctx *ctx, int32_t kind, int32_t k);   // components.hip: kind checked, k resolved by the caller
+int hierarchy_run(komb_ctx *ctx, int32_t kind);               // hierarchy.hip: kind and the results it needs checked by the caller
 int communities_run(komb_ctx *ctx, int32_t k);                // communities.hip: k checked and resolved by the caller
 int communities_vertices(komb_ctx *ctx);                      // communities.hip: n_comm[] and the multi-community count, made on first request
 void communities_drop(komb_ctx *ctx);                         // communities.hip: the result goes with the k-truss result it indexes

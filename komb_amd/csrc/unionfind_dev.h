@@ -48,4 +48,20 @@ __device__ __forceinline__ void comp_link(int32_t *parent, int32_t u, int32_t v)
     }
 }
 
+// comp_link that reports its hook (hierarchy.hip): the root this call hung under a smaller id, -1 when u and v were in
+// one tree already.  A vertex is a root until it is hooked and never again: over any number of launches every vertex is
+// reported at most once.
+__device__ __forceinline__ int32_t comp_link_hooked(int32_t *parent, int32_t u, int32_t v)
+{
+    int32_t a = comp_find(parent, u), b = comp_find(parent, v);
+    while (a != b) {
+        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const int32_t old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) return hi;
+        a = comp_find(parent, old);
+        b = lo;
+    }
+    return -1;
+}
+
 } // namespace komb

@@ -33,6 +33,15 @@
 //                       community's number of edges.  truss_community_vertices.tsv: #VID, Name, Communities -- the
 //                       unitigs with a member edge and the number of communities they belong to (more than one: a
 //                       unitig shared between dense regions).  Nothing else changes.
+//   KOMB_HIERARCHY=1    also write, after kcore.tsv, the nesting forest of the k-core components over all k
+//                       (komb_hierarchy_run).  core_hierarchy.tsv: #Node, K, Rep, Parent, Size, Shell -- one row per node
+//                       in node order (ascending K, then the VID of Rep); Rep is the Name of the unitig with the smallest
+//                       VID in the node, Parent a node index or -1, Size the node's number of unitigs, Shell those of
+//                       coreness exactly K among them.  core_hierarchy_vertices.tsv: #VID, Name, Coreness, Node -- every
+//                       unitig in VID order with the node it belongs to at its own coreness.  With KOMB_TRUSS=1 also
+//                       truss_hierarchy.tsv and truss_hierarchy_vertices.tsv (#VID, Name, Trussness, Node) for the truss
+//                       stage's result: the unitigs with an edge in it, Trussness the largest of their edges.  VIDs depend
+//                       on -t, so only the forest by Name compares between runs.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -546,6 +555,50 @@ void write_components(komb_ctx *ctx, const std::string &path, const char *third,
     fclose(fp);
 }
 
+// KOMB_HIERARCHY: komb_hierarchy_run of `kind` as two tables: <prefix>_hierarchy.tsv, one row per node in node order, and
+// <prefix>_hierarchy_vertices.tsv, one row per member vertex in VID order (level(v): its coreness / its largest trussness)
+template <class LevelFn>
+void write_hierarchy(komb_ctx *ctx, int32_t kind, const std::string &outdir, const char *prefix, const char *third, const Names &names,
+                     int64_t nv, int threads, LevelFn &&level)
+{
+    int rc = komb_hierarchy_run(ctx, kind);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_hierarchy_run", rc);
+    int64_t n = 0;
+    komb_hierarchy_count(ctx, &n);
+    std::vector<int32_t> k((size_t)n), rep((size_t)n), parent((size_t)n), size((size_t)n), shell((size_t)n), node((size_t)nv);
+    rc = komb_hierarchy_fetch_nodes(ctx, k.data(), rep.data(), parent.data(), size.data(), shell.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_hierarchy_fetch_nodes", rc);
+    rc = komb_hierarchy_fetch_vertices(ctx, node.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_hierarchy_fetch_vertices", rc);
+    std::string path = outdir + "/" + prefix + "_hierarchy.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Node\tK\tRep\tParent\tSize\tShell\n");
+    write_rows(fp, n, threads, [&](int64_t i, std::string &buf) {
+        char tmp[64];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t%d\t", (int)i, (int)k[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)rep[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\t%d\n", (int)parent[(size_t)i], (int)size[(size_t)i], (int)shell[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    path = outdir + "/" + prefix + "_hierarchy_vertices.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\t%s\tNode\n", third);
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (node[(size_t)i] < 0) return;
+        char tmp[48];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", level(i), (int)node[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_COMMUNITIES: the last komb_truss_communities_run as two tables (edges in canonical order, vertices in VID order)
 void write_communities(komb_ctx *ctx, const std::string &outdir, const Names &names, int64_t nv, int threads,
                        const std::vector<int32_t> &eu, const std::vector<int32_t> &ev, const std::vector<int32_t> &tr)
@@ -857,6 +910,12 @@ int main(int argc, const char **argv)
                          [&](int64_t i) { return (int)core[(size_t)i]; });
     }
 
+    // the nesting forest of the k-core components over all k (no counterpart in the reference; opt-in): core_hierarchy*.tsv
+    const bool hier_on = env_on("KOMB_HIERARCHY");
+    if (hier_on)
+        write_hierarchy(ctx, KOMB_COMP_CORE, args.outdir, "core", "Coreness", names, nv, args.threads,
+                        [&](int64_t i) { return (int)core[(size_t)i]; });
+
     // k-truss communities of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
     const char *comm_env = getenv("KOMB_COMMUNITIES");
     const bool comm_on = comm_env && *comm_env;
@@ -912,6 +971,15 @@ int main(int argc, const char **argv)
             rc = komb_truss_communities_run(ctx, (int32_t)comm_k);
             if (rc != KOMB_OK) die_accel(ctx, "komb_truss_communities_run", rc);
             write_communities(ctx, args.outdir, names, nv, args.threads, eu, ev, tr);
+        }
+        if (hier_on) {                                     // the forest of the truss stage's result
+            std::vector<int32_t> lvl((size_t)nv, 0);
+            for (int64_t e = 0; e < ne_sub; ++e) {
+                lvl[(size_t)eu[(size_t)e]] = std::max(lvl[(size_t)eu[(size_t)e]], tr[(size_t)e]);
+                lvl[(size_t)ev[(size_t)e]] = std::max(lvl[(size_t)ev[(size_t)e]], tr[(size_t)e]);
+            }
+            write_hierarchy(ctx, KOMB_COMP_TRUSS, args.outdir, "truss", "Trussness", names, nv, args.threads,
+                            [&](int64_t i) { return (int)lvl[(size_t)i]; });
         }
     }
     fprintf(stdout, "\nTime elapsed doing K-core decomposition: %.3f s\n", since(t0));
