@@ -270,6 +270,51 @@ int komb_truss_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm /*[nv]*
 int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edges, int64_t *n_communities,
                                 int64_t *largest, int64_t *n_multi_vertices, double *ms);                 /* any may be NULL */
 
+/* ---- k-truss community hierarchy: the nesting forest of the communities over all k ---- */
+/* All thresholds at once: which k-truss community lies inside which community of a smaller k (the index of Huang et al.
+ * 2014 / the EquiTruss summary of Akbas & Zhao, VLDB 2017, as a forest).  Input: the last COMPLETE k-truss result, whole
+ * graph or vmask run alike -- ne_sub canonical edges (eu[i], ev[i]) with trussness t[i].
+ * An edge is a MEMBER when t[i] >= 3.  An edge has trussness 2 exactly when it lies in no triangle of the result: it is in
+ * no community of any k >= 3 and is no member here, node[i] = -1.
+ * For k >= 3, C_k is the set of k-truss communities of komb_truss_communities_run(k): the classes of the edges with
+ * t >= k under "two sides of a triangle whose three edges all have t >= k".
+ * A NODE is a pair (k, S): S is the edge set of a community of C_k and not the edge set of a community of C_(k+1) -- S
+ * holds an edge of trussness exactly k, or joins two or more communities of C_(k+1) through triangles whose smallest
+ * trussness is k.  rep = the smallest canonical edge index in S.  Nodes are numbered 0 .. n_nodes-1 in ascending (k, rep)
+ * order.  parent = the node (k', S') with S inside S' and the largest k' < k, -1 when there is none; parent[i] < i always.
+ * size[i] = |S|, counted in edges; shell[i] = the edges e with node[e] == i; size[i] == shell[i] + the sizes of i's
+ * children.  node[e] = the node (t[e], the community of C_t[e] that holds e), -1 for a non-member.  Everything is
+ * determined by the graph: it does not depend on the run, on an option or on scheduling.
+ * The walk-up rule: for an edge e with t[e] >= k >= 3, walking up from node[e] while the parent's k is still >= k ends at
+ * the node whose rep is label[e] and whose size is size[e] of komb_truss_communities_run(k).
+ * komb_community_hierarchy_labels runs that rule on the device, one walk per edge over the stored forest and no triangle
+ * work, and returns exactly what komb_truss_communities_run(k) followed by komb_truss_communities_fetch returns, for
+ * every k: KOMB_COMM_K_MAX resolves as it does there; 0 <= k <= 2 runs as 2 -- an edge of trussness 2 is then its own
+ * community (label = its own index, size 1), the members take their root's rep and size; k above the largest trussness
+ * gives -1 / 0 everywhere; k < -1: KOMB_ERR_ARG.  Either output may be NULL.  The call does not touch the stored result
+ * of komb_truss_communities_run.
+ * komb_community_hierarchy_info: nodes, nodes without a parent, the largest node level (2 without nodes), depth = the
+ * most nodes on a path from a root down (0 without nodes), the member edges, and ms -- the device time of
+ * komb_community_hierarchy_run on the context's HIP-event timer.
+ * No graph loaded: KOMB_ERR_ARG.  Without a complete k-truss result (none yet, after komb_truss_run_slice, a sharded
+ * partial result or komb_truss_unprepare), count / fetch / labels / info before a run on the current result:
+ * KOMB_ERR_STATE.  A result with no edge of trussness >= 3 has no nodes; not an error.  A failed call leaves the previous
+ * result readable.  The run writes two link records per triangle of the result; more than 2^31 - 1 of them do not fit its
+ * 32-bit indexing: KOMB_ERR_LIMIT.
+ * The arrays index the canonical edges of one k-truss result and are blocks of their own: whatever replaces or drops that
+ * result -- a new k-truss run of any kind, komb_truss_unprepare, a graph load -- drops them too.  k-core, onion,
+ * components, hierarchy, communities and CoreA calls neither change nor drop them; a run changes none of their results,
+ * no komb_stats field and not the resident k-truss preparation.  Options COMM_SHORT / COMM_HEAVY move the length classes
+ * of the triangle search here as they do for komb_truss_communities_run; neither changes a result. */
+int komb_community_hierarchy_run(komb_ctx *ctx);
+int komb_community_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes);
+int komb_community_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent,
+                                         int32_t *size, int32_t *shell);       /* [n_nodes] each, any may be NULL */
+int komb_community_hierarchy_fetch_edges(komb_ctx *ctx, int32_t *node /*[ne_sub]*/);
+int komb_community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label /*[ne_sub]*/, int32_t *size /*[ne_sub]*/);
+int komb_community_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *k_max, int32_t *depth,
+                                  int64_t *n_member_edges, double *ms);        /* any may be NULL */
+
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness
  * (src/graph.cpp:502, src/graph.cpp:508).  vmask (host, nv bytes, nullable)

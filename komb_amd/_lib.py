@@ -92,6 +92,13 @@ SIGNATURES = {
     "komb_truss_communities_fetch_vertices": (_i32, [_vp, _vp]),
     "komb_truss_communities_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                            ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_community_hierarchy_run": (_i32, [_vp]),
+    "komb_community_hierarchy_count": (_i32, [_vp, ctypes.POINTER(_i64)]),
+    "komb_community_hierarchy_fetch_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "komb_community_hierarchy_fetch_edges": (_i32, [_vp, _vp]),
+    "komb_community_hierarchy_labels": (_i32, [_vp, ctypes.c_int32, _vp, _vp]),
+    "komb_community_hierarchy_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

@@ -331,6 +331,57 @@ class KombAccel:
         self.truss_communities_run(k)
         return self.truss_communities_fetch()
 
+    # ---- k-truss community hierarchy: the nesting forest of the communities over all k (include/komb_accel.h)
+    def community_hierarchy_run(self):
+        """Needs a complete k-truss result on this graph."""
+        self._sync_env_options()
+        self._check(self._lib.komb_community_hierarchy_run(self._ctx))
+
+    def community_hierarchy_fetch_nodes(self):
+        """{"k", "rep", "parent", "size", "shell"}: int32[n_nodes] each, nodes in ascending (k, rep) order; rep is a
+        canonical edge index, size and shell count edges."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_community_hierarchy_count(self._ctx, ctypes.byref(n)))
+        out = {name: _out_i32(max(n.value, 0)) for name in self.HIER_FIELDS}
+        self._check(self._lib.komb_community_hierarchy_fetch_nodes(self._ctx, *(ptr(out[name]) for name in self.HIER_FIELDS)))
+        return out
+
+    def _community_hierarchy_edges(self):
+        """ne_sub of the k-truss result the stored forest indexes (the forest's own errors first: no graph, no run)."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_community_hierarchy_count(self._ctx, None))
+        self._check(self._lib.komb_truss_count(self._ctx, ctypes.byref(n)))
+        return max(n.value, 0)
+
+    def community_hierarchy_fetch_edges(self):
+        """node int32[ne_sub]: the node of every canonical edge of the k-truss result, -1 for an edge of trussness 2."""
+        n = self._community_hierarchy_edges()
+        node = _out_i32(n)
+        self._check(self._lib.komb_community_hierarchy_fetch_edges(self._ctx, ptr(node)))
+        return node
+
+    def community_hierarchy_labels(self, k=3):
+        """(label, size) int32[ne_sub]: what run_truss_communities(k) returns, read off the stored forest."""
+        n = self._community_hierarchy_edges()
+        label = _out_i32(n)
+        size = _out_i32(n)
+        self._check(self._lib.komb_community_hierarchy_labels(self._ctx, k, ptr(label), ptr(size)))
+        return label, size
+
+    def community_hierarchy_info(self):
+        """{"n_nodes", "n_roots", "k_max", "depth", "n_member_edges", "ms"} of the last komb_community_hierarchy_run."""
+        kmax, depth = ctypes.c_int32(), ctypes.c_int32()
+        n, roots, mem, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        self._check(self._lib.komb_community_hierarchy_info(self._ctx, ctypes.byref(n), ctypes.byref(roots), ctypes.byref(kmax),
+                                                            ctypes.byref(depth), ctypes.byref(mem), ctypes.byref(ms)))
+        return {"n_nodes": n.value, "n_roots": roots.value, "k_max": kmax.value, "depth": depth.value,
+                "n_member_edges": mem.value, "ms": ms.value}
+
+    def run_community_hierarchy(self):
+        """(nodes, node): the dict of community_hierarchy_fetch_nodes and the per-edge node array."""
+        self.community_hierarchy_run()
+        return self.community_hierarchy_fetch_nodes(), self.community_hierarchy_fetch_edges()
+
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):
         degree = as_c(degree, np.int32)

@@ -359,6 +359,68 @@ int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_membe
     return KOMB_OK;
 }
 
+int komb_community_hierarchy_run(komb_ctx *ctx)
+{
+    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_run");
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    return community_hierarchy_run(ctx);
+}
+
+int komb_community_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes)
+{
+    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_count");
+    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_count: no community hierarchy of the current k-truss result");
+    if (n_nodes) *n_nodes = ctx->ch_nodes;
+    return KOMB_OK;
+}
+
+int komb_community_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent, int32_t *size, int32_t *shell)
+{
+    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_fetch_nodes");
+    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_fetch_nodes: no community hierarchy of the current k-truss result");
+    if (ctx->ch_nodes == 0) return KOMB_OK;
+    const size_t stride = (size_t)ctx->ch_cap, bytes = (size_t)ctx->ch_nodes * sizeof(int32_t);
+    int32_t *const out[5] = {k, rep, parent, size, shell};
+    for (int i = 0; i < 5; ++i)
+        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_ch_nodes + i * stride, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_community_hierarchy_fetch_edges(komb_ctx *ctx, int32_t *node)
+{
+    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_fetch_edges");
+    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_fetch_edges: no community hierarchy of the current k-truss result");
+    if (ctx->t_ne > 0 && node) KOMB_HIP(ctx, staged_copy(ctx, node, ctx->d_ch_enode, (size_t)ctx->t_ne * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size)
+{
+    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_labels");
+    if (k < KOMB_COMM_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_community_hierarchy_labels: bad threshold %d", k);
+    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_labels: no community hierarchy of the current k-truss result");
+    if (k == KOMB_COMM_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
+    if (k < 2) k = 2;
+    return community_hierarchy_labels(ctx, k, label, size);
+}
+
+int komb_community_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *k_max, int32_t *depth,
+                                  int64_t *n_member_edges, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_info");
+    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_info: no community hierarchy of the current k-truss result");
+    if (n_nodes) *n_nodes = ctx->ch_nodes;
+    if (n_roots) *n_roots = ctx->ch_roots;
+    if (k_max) *k_max = ctx->ch_kmax;
+    if (depth) *depth = ctx->ch_depth;
+    if (n_member_edges) *n_member_edges = ctx->ch_members;
+    if (ms) *ms = ctx->ch_ms;
+    return KOMB_OK;
+}
+
 int komb_set_option(komb_ctx *ctx, const char *name, const char *value)
 {
     if (!ctx || !name || !*name) return KOMB_ERR_ARG;

@@ -304,6 +304,15 @@ struct komb_ctx {
     double comm_ms = 0.0, comm_ms_vertices = 0.0;   // device time of the run | of the vertex pass (HIP events)
     bool comm_done = false, comm_v_ready = false;
 
+    // ---- k-truss community hierarchy (community_hierarchy.hip): the nesting forest of the communities over all k, in pool blocks
+    // of its own, indexed like the k-truss result it was computed from and dropped with it (truss_free)
+    int32_t *d_ch_nodes = nullptr;           // [5 * ch_cap] k | rep | parent | size | shell, each a block of ch_cap words with ch_nodes in use
+    int32_t *d_ch_enode = nullptr;           // [t_ne] the node of every canonical edge, -1 for a non-member
+    int64_t ch_cap = 1, ch_nodes = 0, ch_roots = 0, ch_members = 0;
+    int32_t ch_kmax = 2, ch_depth = 0;
+    double ch_ms = 0.0;                      // device time of the last run (HIP events)
+    bool ch_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                       // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -466,6 +475,9 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind);               // hierarchy.hip: 
 int communities_run(komb_ctx *ctx, int32_t k);                // communities.hip: k checked and resolved by the caller
 int communities_vertices(komb_ctx *ctx);                      // communities.hip: n_comm[] and the multi-community count, made on first request
 void communities_drop(komb_ctx *ctx);                         // communities.hip: the result goes with the k-truss result it indexes
+int community_hierarchy_run(komb_ctx *ctx);                   // community_hierarchy.hip: the k-truss result it needs checked by the caller
+int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
+void community_hierarchy_drop(komb_ctx *ctx);                 // community_hierarchy.hip: the result goes with the k-truss result it indexes
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);
 int corea_ranks(komb_ctx *ctx, const int32_t *deg, const int32_t *core, int64_t n, double *rank_deg, double *rank_key);

@@ -278,6 +278,7 @@ struct TrussLocal {
 void truss_free(komb_ctx *ctx)
 {
     communities_drop(ctx);                   // (its labels index this result's canonical edges)
+    community_hierarchy_drop(ctx);           // (so do the community hierarchy's reps and node[])
     if (ctx->t_own_edges) { ctx->pool.put(ctx->d_t_eu); ctx->pool.put(ctx->d_t_ev); }
     ctx->pool.put(ctx->d_t_truss);
     ctx->pool.put(ctx->d_t_sup);

@@ -42,6 +42,15 @@
 //                       truss_hierarchy.tsv and truss_hierarchy_vertices.tsv (#VID, Name, Trussness, Node) for the truss
 //                       stage's result: the unitigs with an edge in it, Trussness the largest of their edges.  VIDs depend
 //                       on -t, so only the forest by Name compares between runs.  Nothing else changes.
+//   KOMB_COMMUNITY_HIERARCHY=1  with KOMB_TRUSS=1: also write, after the truss stage, the nesting forest of the k-truss
+//                       communities of its result over all k (komb_community_hierarchy_run).
+//                       truss_community_hierarchy.tsv: #Node, K, Rep_U, Rep_V, Parent, Size, Shell -- one row per node in
+//                       node order; Rep_U and Rep_V are the Names of the unitigs of the node's first edge in canonical
+//                       order, Parent a node index or -1, Size the node's number of edges, Shell those of trussness exactly
+//                       K among them.  truss_community_hierarchy_edges.tsv: #VID_U, Name_U, VID_V, Name_V, Trussness, Node
+//                       -- one row per edge of trussness >= 3 in canonical order with the node it belongs to at its own
+//                       trussness.  VIDs depend on -t, so only the forest by Name compares between runs.  Nothing else
+//                       changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -645,6 +654,54 @@ void write_communities(komb_ctx *ctx, const std::string &outdir, const Names &na
     fclose(fp);
 }
 
+// KOMB_COMMUNITY_HIERARCHY: komb_community_hierarchy_run as two tables (nodes in node order, member edges in canonical order)
+void write_community_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads,
+                               const std::vector<int32_t> &eu, const std::vector<int32_t> &ev, const std::vector<int32_t> &tr)
+{
+    const int64_t ne = (int64_t)tr.size();
+    int rc = komb_community_hierarchy_run(ctx);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_community_hierarchy_run", rc);
+    int64_t n = 0;
+    komb_community_hierarchy_count(ctx, &n);
+    std::vector<int32_t> k((size_t)n), rep((size_t)n), parent((size_t)n), size((size_t)n), shell((size_t)n), node((size_t)ne);
+    rc = komb_community_hierarchy_fetch_nodes(ctx, k.data(), rep.data(), parent.data(), size.data(), shell.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_community_hierarchy_fetch_nodes", rc);
+    rc = komb_community_hierarchy_fetch_edges(ctx, node.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_community_hierarchy_fetch_edges", rc);
+    std::string path = outdir + "/truss_community_hierarchy.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Node\tK\tRep_U\tRep_V\tParent\tSize\tShell\n");
+    write_rows(fp, n, threads, [&](int64_t i, std::string &buf) {
+        char tmp[64];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t%d\t", (int)i, (int)k[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)eu[(size_t)rep[(size_t)i]]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)ev[(size_t)rep[(size_t)i]]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\t%d\n", (int)parent[(size_t)i], (int)size[(size_t)i], (int)shell[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    path = outdir + "/truss_community_hierarchy_edges.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID_U\tName_U\tVID_V\tName_V\tTrussness\tNode\n");
+    write_rows(fp, ne, threads, [&](int64_t i, std::string &buf) {
+        if (node[(size_t)i] < 0) return;
+        char tmp[64];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)eu[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)eu[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t", (int)ev[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)ev[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)tr[(size_t)i], (int)node[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // CombineCoreA::run (src/CombineCoreA.h:16-43)
 void corea_stage(komb_ctx *ctx, const std::string &outdir, const std::vector<int32_t> &deg, const std::vector<int32_t> &core, int threads)
 {
@@ -972,6 +1029,8 @@ int main(int argc, const char **argv)
             if (rc != KOMB_OK) die_accel(ctx, "komb_truss_communities_run", rc);
             write_communities(ctx, args.outdir, names, nv, args.threads, eu, ev, tr);
         }
+        if (env_on("KOMB_COMMUNITY_HIERARCHY"))            // the forest of the communities of the truss stage's result
+            write_community_hierarchy(ctx, args.outdir, names, args.threads, eu, ev, tr);
         if (hier_on) {                                     // the forest of the truss stage's result
             std::vector<int32_t> lvl((size_t)nv, 0);
             for (int64_t e = 0; e < ne_sub; ++e) {
