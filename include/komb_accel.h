@@ -116,7 +116,8 @@ int         komb_abi_version(void);
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, COMP_SAMPLE (0 | 1:
- * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), and POISON ("0xWWWWWWWW": every device
+ * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
+ * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
  * allocation the context hands out is filled with that 32-bit word first -- tests of reads of memory nothing wrote)
  * (DESIGN.md section 8).  value NULL unsets. */
 int         komb_set_option(komb_ctx *ctx, const char *name, const char *value);
@@ -314,6 +315,47 @@ int komb_community_hierarchy_fetch_edges(komb_ctx *ctx, int32_t *node /*[ne_sub]
 int komb_community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label /*[ne_sub]*/, int32_t *size /*[ne_sub]*/);
 int komb_community_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *k_max, int32_t *depth,
                                   int64_t *n_member_edges, double *ms);        /* any may be NULL */
+
+/* ---- densest-subgraph search with a certified bound ---------------------- */
+/* Which vertex set of the resident graph is the densest, and how dense can any be.  The density of a vertex set S is
+ * rho(S) = m(S) / |S|, m(S) = the resident edges with both ends in S.  Every comparison of two densities is exact: a
+ * cross-multiplication in 64-bit integers, never floating point.  komb_densest_subgraph_run(ctx, iters), iters >= 0, reads
+ * the coreness komb_core_run left on this graph (KOMB_ERR_STATE if there is none; k-core is never run here):
+ *  1. Core density profile.  For k = 0 .. k_max: n_k = the vertices of coreness >= k, m_k = the edges whose two ends both
+ *     have coreness >= k.  The best core is the k that maximises m_k / n_k, the LARGER k on a tie: (k*, m*, n*).
+ *  2. Prune.  c = ceil(m* / n*), P = the vertices of coreness >= c, E_P = the edges inside P.  Every densest subgraph lies
+ *     inside P (each of its vertices has at least rho_opt >= m* / n* neighbours in it), so P has the same optimum.
+ *  3. iters synchronous Frank-Wolfe rounds on integer loads (Danisch, Chan, Sozio, "Large scale density-friendly graph
+ *     decomposition via convex programming", WWW 2017; with step 1 / (t + 1) the iterate is the average of the rounds, so
+ *     the cumulative counts are the whole state).  L_0 = 0.  In round t = 0 .. iters - 1 every edge {u, v} of E_P, u < v,
+ *     reads L_t and gives one unit to the endpoint with the smaller load; on equal loads to u when t is even, to v when t
+ *     is odd.  L_(t+1) = L_t + those units.  Every read of round t sees L_t only: the result does not depend on scheduling.
+ *  4. Extract.  P ordered by (load descending, id ascending); for every prefix length i >= 1, m_i = the edges of E_P with
+ *     both ends among the first i vertices.  The best prefix maximises m_i / i, the SHORTEST on a tie.
+ *  5. The result is the best prefix when iters >= 1 and it is strictly denser than the best core (source == 1,
+ *     KOMB_DENSEST_PREFIX), else the best core (source == 0, KOMB_DENSEST_CORE).
+ *  6. Certificate.  For iters >= 1, rho_opt <= load_max / iters with load_max = the largest load: the averaged assignment is
+ *     a feasible point of the dual of Charikar's LP, and the loads inside an optimal set sum to at least its edge count.
+ *     rho_opt <= k_max always.  info reports m_sub, n_sub, load_max, iters and k_max as integers; the caller forms the ratios.
+ * The empty graph: no members, every count 0.  A graph without edges: the 0-core, every vertex, m_sub == 0.  iters < 0, or
+ * no graph loaded: KOMB_ERR_ARG.  iters * (the largest degree inside P) above 2^31 - 1 does not fit the load word:
+ * KOMB_ERR_LIMIT, before a round is queued.  fetch / profile / info before a run on the current graph: KOMB_ERR_STATE.
+ * komb_densest_subgraph_fetch: member[v] = 1 | 0, load[v] = the load of v after the last round, 0 outside P; either may be
+ * NULL.  komb_densest_subgraph_profile: n_k, m_k, k_max + 1 entries each (k_max from info); either may be NULL.
+ * komb_densest_subgraph_info: source, k* , c, |P|, |E_P|, the result's vertices and edges, load_max, iters, k_max and the
+ * device time of the run in ms (the context's HIP-event timer); any pointer may be NULL.
+ * The result is a snapshot in arrays of its own: loading a graph drops it, no other call changes it, a run changes no other
+ * result and no komb_stats field, and a failed run leaves the previous result readable.  Option DENSEST_LOCAL (0 = never,
+ * 1 = whenever loads and deltas fit in LDS, unset = automatic) selects between one launch per round and one workgroup that
+ * runs all rounds in a single launch; it changes no result. */
+#define KOMB_DENSEST_CORE   0
+#define KOMB_DENSEST_PREFIX 1
+int komb_densest_subgraph_run(komb_ctx *ctx, int32_t iters);
+int komb_densest_subgraph_fetch(komb_ctx *ctx, int32_t *member /*[nv] 0|1*/, int32_t *load /*[nv], 0 outside P*/);
+int komb_densest_subgraph_profile(komb_ctx *ctx, int64_t *n_k, int64_t *m_k /*[k_max+1] each*/);
+int komb_densest_subgraph_info(komb_ctx *ctx, int32_t *source, int32_t *k_best, int32_t *k_prune, int64_t *n_pruned,
+                               int64_t *m_pruned, int64_t *n_sub, int64_t *m_sub, int64_t *load_max, int32_t *iters,
+                               int32_t *k_max, double *ms);
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

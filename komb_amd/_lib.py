@@ -52,6 +52,7 @@ class KombStats(ctypes.Structure):
 KOMB_CREATE_NULL_STREAM, KOMB_CREATE_NO_WARMUP, KOMB_CREATE_WARM_UPLOAD = 1, 2, 4
 KOMB_COMP_CORE, KOMB_COMP_TRUSS, KOMB_COMP_K_MAX = 0, 1, -1
 KOMB_COMM_K_MAX = -1
+KOMB_DENSEST_CORE, KOMB_DENSEST_PREFIX = 0, 1
 
 
 # every symbol include/komb_accel.h declares: name -> (restype, argtypes)
@@ -99,6 +100,13 @@ SIGNATURES = {
     "komb_community_hierarchy_labels": (_i32, [_vp, ctypes.c_int32, _vp, _vp]),
     "komb_community_hierarchy_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32),
                                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_densest_subgraph_run": (_i32, [_vp, ctypes.c_int32]),
+    "komb_densest_subgraph_fetch": (_i32, [_vp, _vp, _vp]),
+    "komb_densest_subgraph_profile": (_i32, [_vp, _vp, _vp]),
+    "komb_densest_subgraph_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                          ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

@@ -41,7 +41,7 @@ def gen_hug_edges(nv, n_cliques, alpha=2.6, seed=42):
 FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
-                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "POISON")
+                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -240,6 +240,48 @@ class KombAccel:
         """(nodes, node): the dict of hierarchy_fetch_nodes and the per-vertex node array of the hierarchy of `kind`."""
         self.hierarchy_run(kind)
         return self.hierarchy_fetch_nodes(), self.hierarchy_fetch_vertices()
+
+    # ---- densest-subgraph search with a certified bound (include/komb_accel.h)
+    DENSEST_INFO = ("source", "k_best", "k_prune", "n_pruned", "m_pruned", "n_sub", "m_sub", "load_max", "iters", "k_max", "ms")
+
+    def densest_subgraph_run(self, iters=64):
+        """iters Frank-Wolfe rounds (0: the best core only); needs the coreness komb_core_run left on this graph."""
+        self._sync_env_options()
+        self._check(self._lib.komb_densest_subgraph_run(self._ctx, iters))
+
+    def densest_subgraph_fetch(self):
+        """(member, load) int32[nv] of the last komb_densest_subgraph_run: 1 | 0, and the vertex' load (0 outside the pruned set)."""
+        member = _out_i32(max(self.nv, 0))
+        load = _out_i32(max(self.nv, 0))
+        self._check(self._lib.komb_densest_subgraph_fetch(self._ctx, ptr(member), ptr(load)))
+        return member, load
+
+    def densest_subgraph_info(self):
+        """{"source", "k_best", "k_prune", "n_pruned", "m_pruned", "n_sub", "m_sub", "load_max", "iters", "k_max", "ms"}."""
+        i32 = {n: ctypes.c_int32() for n in ("source", "k_best", "k_prune", "iters", "k_max")}
+        i64 = {n: ctypes.c_int64() for n in ("n_pruned", "m_pruned", "n_sub", "m_sub", "load_max")}
+        ms = ctypes.c_double()
+        self._check(self._lib.komb_densest_subgraph_info(
+            self._ctx, ctypes.byref(i32["source"]), ctypes.byref(i32["k_best"]), ctypes.byref(i32["k_prune"]),
+            ctypes.byref(i64["n_pruned"]), ctypes.byref(i64["m_pruned"]), ctypes.byref(i64["n_sub"]), ctypes.byref(i64["m_sub"]),
+            ctypes.byref(i64["load_max"]), ctypes.byref(i32["iters"]), ctypes.byref(i32["k_max"]), ctypes.byref(ms)))
+        out = {n: v.value for n, v in {**i32, **i64}.items()}
+        out["ms"] = ms.value
+        return out
+
+    def densest_subgraph_profile(self):
+        """(n_k, m_k) int64[k_max + 1]: vertices of coreness >= k, edges between two of them."""
+        k = self.densest_subgraph_info()["k_max"] + 1
+        n_k = np.full(k, SENTINEL_I32, dtype=np.int64)
+        m_k = np.full(k, SENTINEL_I32, dtype=np.int64)
+        self._check(self._lib.komb_densest_subgraph_profile(self._ctx, ptr(n_k), ptr(m_k)))
+        return n_k, m_k
+
+    def run_densest_subgraph(self, iters=64):
+        """(member, load, info): the densest subgraph found on the resident graph and the integers of its certificate."""
+        self.densest_subgraph_run(iters)
+        member, load = self.densest_subgraph_fetch()
+        return member, load, self.densest_subgraph_info()
 
     # ---- k-truss (a5 + a6)
     def truss_run(self, vmask=None):

@@ -359,6 +359,54 @@ int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_membe
     return KOMB_OK;
 }
 
+int komb_densest_subgraph_run(komb_ctx *ctx, int32_t iters)
+{
+    KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_run");
+    if (iters < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_densest_subgraph_run: bad number of rounds %d", iters);
+    if (!ctx->core_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_run: komb_core_run has not completed on this graph");
+    return densest_run(ctx, iters);
+}
+
+int komb_densest_subgraph_fetch(komb_ctx *ctx, int32_t *member, int32_t *load)
+{
+    KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_fetch");
+    if (!ctx->dens_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_fetch: komb_densest_subgraph_run has not completed on this graph");
+    if (ctx->nv == 0) return KOMB_OK;
+    if (member) KOMB_HIP(ctx, staged_copy(ctx, member, ctx->d_dens_member, (size_t)ctx->nv * sizeof(int32_t), false));
+    if (load) KOMB_HIP(ctx, staged_copy(ctx, load, ctx->d_dens_load, (size_t)ctx->nv * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_densest_subgraph_profile(komb_ctx *ctx, int64_t *n_k, int64_t *m_k)
+{
+    KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_profile");
+    if (!ctx->dens_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_profile: komb_densest_subgraph_run has not completed on this graph");
+    const size_t K = ctx->dens_profile.size() / 2;
+    if (n_k) memcpy(n_k, ctx->dens_profile.data(), K * sizeof(int64_t));
+    if (m_k) memcpy(m_k, ctx->dens_profile.data() + K, K * sizeof(int64_t));
+    return KOMB_OK;
+}
+
+int komb_densest_subgraph_info(komb_ctx *ctx, int32_t *source, int32_t *k_best, int32_t *k_prune, int64_t *n_pruned, int64_t *m_pruned,
+                               int64_t *n_sub, int64_t *m_sub, int64_t *load_max, int32_t *iters, int32_t *k_max, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_info");
+    if (!ctx->dens_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_info: komb_densest_subgraph_run has not completed on this graph");
+    const komb_ctx::Densest &r = ctx->dens;
+    if (source) *source = r.source;
+    if (k_best) *k_best = r.k_best;
+    if (k_prune) *k_prune = r.k_prune;
+    if (n_pruned) *n_pruned = r.n_pruned;
+    if (m_pruned) *m_pruned = r.m_pruned;
+    if (n_sub) *n_sub = r.n_sub;
+    if (m_sub) *m_sub = r.m_sub;
+    if (load_max) *load_max = r.load_max;
+    if (iters) *iters = r.iters;
+    if (k_max) *k_max = r.k_max;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_community_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_run");

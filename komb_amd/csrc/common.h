@@ -294,6 +294,18 @@ struct komb_ctx {
     double hier_ms = 0.0;                    // device time of the last run (HIP events)
     bool hier_done = false;
 
+    // ---- densest-subgraph search (densest.hip): a snapshot in arrays of its own (pool blocks), dropped with the graph
+    int32_t *d_dens_member = nullptr;        // [nv] 1 for a vertex of the result, 0 otherwise
+    int32_t *d_dens_load = nullptr;          // [nv] Frank-Wolfe load of the vertex, 0 outside the pruned set
+    struct Densest {
+        int32_t source = 0, k_best = 0, k_prune = 0, iters = 0, k_max = 0;
+        int64_t n_pruned = 0, m_pruned = 0, n_sub = 0, m_sub = 0, load_max = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        bool local = false;                  // the rounds ran in the single-workgroup LDS kernel
+    } dens;
+    std::vector<int64_t> dens_profile;       // n_k[k_max + 1] | m_k[k_max + 1] of the last run
+    bool dens_done = false;
+
     // ---- k-truss communities (communities.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
     int32_t *d_comm_label = nullptr;         // [t_ne] smallest canonical edge index of the edge's community, -1 for a non-member
@@ -478,6 +490,7 @@ void communities_drop(komb_ctx *ctx);                         // communities.hip
 int community_hierarchy_run(komb_ctx *ctx);                   // community_hierarchy.hip: the k-truss result it needs checked by the caller
 int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
 void community_hierarchy_drop(komb_ctx *ctx);                 // community_hierarchy.hip: the result goes with the k-truss result it indexes
+int densest_run(komb_ctx *ctx, int32_t iters);                // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);
 int corea_ranks(komb_ctx *ctx, const int32_t *deg, const int32_t *core, int64_t n, double *rank_deg, double *rank_key);

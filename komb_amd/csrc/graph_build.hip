@@ -300,6 +300,9 @@ void graph_free(komb_ctx *ctx)
     if (ctx->d_ceu) ctx->pool.put(ctx->d_ceu);
     if (ctx->d_cev) ctx->pool.put(ctx->d_cev);
     ctx->d_ceu = ctx->d_cev = nullptr;
+    if (ctx->d_dens_member) ctx->pool.put(ctx->d_dens_member);
+    if (ctx->d_dens_load) ctx->pool.put(ctx->d_dens_load);
+    ctx->d_dens_member = ctx->d_dens_load = nullptr; ctx->dens_done = false;
     ctx->pool.clear();                                   // scratch sized for the old graph
 }
 

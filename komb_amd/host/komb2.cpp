@@ -33,6 +33,10 @@
 //                       community's number of edges.  truss_community_vertices.tsv: #VID, Name, Communities -- the
 //                       unitigs with a member edge and the number of communities they belong to (more than one: a
 //                       unitig shared between dense regions).  Nothing else changes.
+//   KOMB_DENSEST=<rounds>   also write, after kcore.tsv, the densest subgraph komb_densest_subgraph_run(rounds) finds on
+//                       the coreness: densest_subgraph.tsv -- #VID, Name, Coreness, Load, members only, in VID order -- and
+//                       core_density.tsv -- #K, Vertices, Edges, the vertices of coreness >= K and the edges between two
+//                       of them, one row per K.
 //   KOMB_HIERARCHY=1    also write, after kcore.tsv, the nesting forest of the k-core components over all k
 //                       (komb_hierarchy_run).  core_hierarchy.tsv: #Node, K, Rep, Parent, Size, Shell -- one row per node
 //                       in node order (ascending K, then the VID of Rep); Rep is the Name of the unitig with the smallest
@@ -564,6 +568,44 @@ void write_components(komb_ctx *ctx, const std::string &path, const char *third,
     fclose(fp);
 }
 
+// KOMB_DENSEST: komb_densest_subgraph_run(iters) as two tables: densest_subgraph.tsv, one row per member vertex in VID order,
+// and core_density.tsv, one row per k
+void write_densest(komb_ctx *ctx, int32_t iters, const std::string &outdir, const Names &names, int64_t nv, int threads,
+                   const std::vector<int32_t> &core)
+{
+    int rc = komb_densest_subgraph_run(ctx, iters);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_densest_subgraph_run", rc);
+    std::vector<int32_t> member((size_t)nv), load((size_t)nv);
+    rc = komb_densest_subgraph_fetch(ctx, member.data(), load.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_densest_subgraph_fetch", rc);
+    int32_t k_max = 0;
+    rc = komb_densest_subgraph_info(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &k_max, nullptr);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_densest_subgraph_info", rc);
+    std::vector<int64_t> n_k((size_t)k_max + 1), m_k((size_t)k_max + 1);
+    rc = komb_densest_subgraph_profile(ctx, n_k.data(), m_k.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_densest_subgraph_profile", rc);
+    std::string path = outdir + "/densest_subgraph.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tCoreness\tLoad\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (!member[(size_t)i]) return;
+        char tmp[48];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)core[(size_t)i], (int)load[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    path = outdir + "/core_density.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#K\tVertices\tEdges\n");
+    for (int32_t k = 0; k <= k_max; ++k) fprintf(fp, "%d\t%lld\t%lld\n", (int)k, (long long)n_k[(size_t)k], (long long)m_k[(size_t)k]);
+    fclose(fp);
+}
+
 // KOMB_HIERARCHY: komb_hierarchy_run of `kind` as two tables: <prefix>_hierarchy.tsv, one row per node in node order, and
 // <prefix>_hierarchy_vertices.tsv, one row per member vertex in VID order (level(v): its coreness / its largest trussness)
 template <class LevelFn>
@@ -972,6 +1014,18 @@ int main(int argc, const char **argv)
     if (hier_on)
         write_hierarchy(ctx, KOMB_COMP_CORE, args.outdir, "core", "Coreness", names, nv, args.threads,
                         [&](int64_t i) { return (int)core[(size_t)i]; });
+
+    // densest-subgraph search on the coreness just computed (no counterpart in the reference; opt-in): KOMB_DENSEST=<rounds>
+    const char *dens_env = getenv("KOMB_DENSEST");
+    if (dens_env && *dens_env) {
+        char *end = nullptr;
+        const long it = strtol(dens_env, &end, 10);
+        if (*end || it < 0 || it > 2147483647L) {
+            fprintf(stderr, "komb2: KOMB_DENSEST=%s: expected a number of rounds >= 0\n", dens_env);
+            leave(EXIT_FAILURE);
+        }
+        write_densest(ctx, (int32_t)it, args.outdir, names, nv, args.threads, core);
+    }
 
     // k-truss communities of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
     const char *comm_env = getenv("KOMB_COMMUNITIES");
