@@ -115,7 +115,7 @@ int         komb_abi_version(void);
  * longer reads: ambient environment cannot change which engine a drop-in runs).  None changes a result.  name: FINISH
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
- * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, COMP_SAMPLE (0 | 1:
+ * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
  * allocation the context hands out is filled with that 32-bit word first -- tests of reads of memory nothing wrote)
@@ -356,6 +356,52 @@ int komb_densest_subgraph_profile(komb_ctx *ctx, int64_t *n_k, int64_t *m_k /*[k
 int komb_densest_subgraph_info(komb_ctx *ctx, int32_t *source, int32_t *k_best, int32_t *k_prune, int64_t *n_pruned,
                                int64_t *m_pruned, int64_t *n_sub, int64_t *m_sub, int64_t *load_max, int32_t *iters,
                                int32_t *k_max, double *ms);
+
+/* ---- structural clustering: clusters, hubs and outliers ------------------ */
+/* Which vertices tie several dense regions together, and which belong to none: structural clustering after Xu, Yuret, Feng,
+ * Schweiger ("SCAN: a structural clustering algorithm for networks", KDD 2007), computed without an index as in pSCAN (Chang
+ * et al., ICDE 2016).  Input: the last COMPLETE k-truss result on the resident graph, whole graph or vmask run alike -- ne_sub
+ * canonical edges (eu[i], ev[i]), eu < ev, in (min, max) lexicographic order of original ids, and their initial supports
+ * sup[i], the triangles of the result through edge i (komb_truss_fetch_support).  Parameters: eps = eps_num / eps_den with
+ * 1 <= eps_num <= eps_den <= 1 000 000, and mu >= 2.
+ * d(v) is the number of result edges at v (a whole-graph result: the CSR row length; 0 for a vertex outside the vmask and
+ * for an isolated vertex).  With Gamma(v) = N(v) + {v}, sigma(u, v) = |Gamma(u) & Gamma(v)| / sqrt(|Gamma(u)| |Gamma(v)|),
+ * which on an edge is (sup + 2) / sqrt((d(u) + 1) (d(v) + 1)).  Edge i is SIMILAR iff
+ *     (sup + 2)^2 * eps_den^2 >= eps_num^2 * (d(u) + 1) * (d(v) + 1),
+ * evaluated exactly in 128-bit integers (the left side reaches 2^102): there is no floating point anywhere.
+ * sim_deg[v] is the number of similar edges at v.
+ * v is a CORE iff sim_deg[v] + 1 >= mu (a vertex is similar to itself, as in the paper).  The CLUSTERS are the classes of the
+ * cores under "joined by a similar edge whose two ends are both cores"; label of a core = the smallest vertex id of its class.
+ * A non-core with at least one similar edge to a core is a BORDER; its label is the smallest label among those cores (a
+ * border may touch several clusters and is counted in exactly one: the one place the paper leaves open, fixed here so that
+ * the output is a function of the graph).  Every other vertex has label -1: it is a HUB iff two of its neighbours in the
+ * result -- over any edge, not only similar ones -- carry different labels >= 0, else an OUTLIER.
+ * size[v] = the vertices that carry v's label, 0 for label -1.  role[v] = KOMB_SC_*.
+ * Everything is determined by the graph and the three parameters: nothing depends on the run, on scheduling or on an option.
+ * komb_structural_clusters_fetch: label, size, role, sim_deg, [nv] each; komb_structural_clusters_fetch_edges: similar[i] =
+ * 1 | 0 in canonical order; komb_structural_clusters_info: the parameters of the last run, the similar edges, the vertices
+ * of each role, the clusters, the size of the largest one (borders included) and ms -- the device time of the run on the
+ * context's HIP-event timer.  Any output pointer may be NULL.
+ * No context or no graph loaded: KOMB_ERR_ARG.  A parameter outside the ranges above: KOMB_ERR_ARG.  Without a completed
+ * k-truss result on this graph, after komb_truss_run_slice / a sharded run that materialised only part of the canonical
+ * edges, after komb_truss_unprepare, fetch / info before a run: KOMB_ERR_STATE.  A result without edges makes every vertex
+ * an outlier and every count 0; the empty graph is not an error.  Canonical endpoints and supports of a whole-graph result
+ * that no fetch has asked for yet are made here as those fetches make them.
+ * The result lives in arrays of its own, installed when a run has succeeded: a refused or failed run leaves the previous
+ * result readable.  It indexes one k-truss result: whatever replaces or drops that result -- a new k-truss run of any kind,
+ * komb_truss_unprepare, a graph load -- drops it too.  k-core, onion, components, hierarchy, communities, densest and CoreA
+ * calls neither change nor drop it; a run changes none of their results, no komb_stats field and not the resident k-truss
+ * preparation.  Option STRUCT_DEBUG (stderr trace: the device time of the run and of its similarity pass) changes no result. */
+#define KOMB_SC_OUTLIER 0
+#define KOMB_SC_HUB     1
+#define KOMB_SC_BORDER  2
+#define KOMB_SC_CORE    3
+int komb_structural_clusters_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu);
+int komb_structural_clusters_fetch(komb_ctx *ctx, int32_t *label, int32_t *size, int32_t *role, int32_t *sim_deg);   /* [nv] each, any may be NULL */
+int komb_structural_clusters_fetch_edges(komb_ctx *ctx, int32_t *similar /*[ne_sub] 0|1, canonical order*/);
+int komb_structural_clusters_info(komb_ctx *ctx, int32_t *eps_num, int32_t *eps_den, int32_t *mu, int64_t *n_similar_edges,
+                                  int64_t *n_cores, int64_t *n_borders, int64_t *n_hubs, int64_t *n_outliers, int64_t *n_clusters,
+                                  int64_t *largest, double *ms);                                                     /* any may be NULL */
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

@@ -53,6 +53,7 @@ KOMB_CREATE_NULL_STREAM, KOMB_CREATE_NO_WARMUP, KOMB_CREATE_WARM_UPLOAD = 1, 2, 
 KOMB_COMP_CORE, KOMB_COMP_TRUSS, KOMB_COMP_K_MAX = 0, 1, -1
 KOMB_COMM_K_MAX = -1
 KOMB_DENSEST_CORE, KOMB_DENSEST_PREFIX = 0, 1
+KOMB_SC_OUTLIER, KOMB_SC_HUB, KOMB_SC_BORDER, KOMB_SC_CORE = 0, 1, 2, 3
 
 
 # every symbol include/komb_accel.h declares: name -> (restype, argtypes)
@@ -107,6 +108,12 @@ SIGNATURES = {
                                           ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                           ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                           ctypes.POINTER(ctypes.c_double)]),
+    "komb_structural_clusters_run": (_i32, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "komb_structural_clusters_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "komb_structural_clusters_fetch_edges": (_i32, [_vp, _vp]),
+    "komb_structural_clusters_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                             ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

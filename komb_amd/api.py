@@ -41,7 +41,7 @@ def gen_hug_edges(nv, n_cliques, alpha=2.6, seed=42):
 FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
-                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "POISON")
+                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -423,6 +423,46 @@ class KombAccel:
         """(nodes, node): the dict of community_hierarchy_fetch_nodes and the per-edge node array."""
         self.community_hierarchy_run()
         return self.community_hierarchy_fetch_nodes(), self.community_hierarchy_fetch_edges()
+
+    # ---- structural clustering: clusters, hubs and outliers of the last k-truss result (include/komb_accel.h)
+    SC_INFO_FIELDS = ("eps_num", "eps_den", "mu", "n_similar_edges", "n_cores", "n_borders", "n_hubs", "n_outliers", "n_clusters",
+                      "largest", "ms")
+
+    def structural_clusters_run(self, eps_num=7, eps_den=10, mu=3):
+        """eps = eps_num / eps_den (1 <= eps_num <= eps_den <= 1 000 000), mu >= 2.  Needs a complete k-truss result."""
+        self._sync_env_options()
+        self._check(self._lib.komb_structural_clusters_run(self._ctx, eps_num, eps_den, mu))
+
+    def structural_clusters_fetch(self):
+        """(label, size, role, sim_deg) int32[nv] of the last komb_structural_clusters_run: the vertex' cluster (the smallest
+        id of its cores' class; -1 for a hub / an outlier), the vertices that carry that label, KOMB_SC_* and the number of
+        similar edges at the vertex."""
+        out = [_out_i32(max(self.nv, 0)) for _ in range(4)]
+        self._check(self._lib.komb_structural_clusters_fetch(self._ctx, *(ptr(x) for x in out)))
+        return tuple(out)
+
+    def structural_clusters_fetch_edges(self):
+        """similar int32[ne_sub]: 1 for a similar edge, in the canonical edge order of the k-truss result."""
+        self._check(self._lib.komb_structural_clusters_info(self._ctx, *([None] * 11)))    # (the clustering's own errors first)
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_truss_count(self._ctx, ctypes.byref(n)))
+        similar = _out_i32(max(n.value, 0))
+        self._check(self._lib.komb_structural_clusters_fetch_edges(self._ctx, ptr(similar)))
+        return similar
+
+    def structural_clusters_info(self):
+        """{"eps_num", "eps_den", "mu", "n_similar_edges", "n_cores", "n_borders", "n_hubs", "n_outliers", "n_clusters",
+        "largest", "ms"} of the last run."""
+        i32 = [ctypes.c_int32() for _ in range(3)]
+        i64 = [ctypes.c_int64() for _ in range(7)]
+        ms = ctypes.c_double()
+        self._check(self._lib.komb_structural_clusters_info(self._ctx, *(ctypes.byref(x) for x in i32 + i64), ctypes.byref(ms)))
+        return dict(zip(self.SC_INFO_FIELDS, [x.value for x in i32 + i64] + [ms.value]))
+
+    def run_structural_clusters(self, eps_num=7, eps_den=10, mu=3):
+        """(label, size, role, sim_deg) of the structural clustering of the last k-truss result."""
+        self.structural_clusters_run(eps_num, eps_den, mu)
+        return self.structural_clusters_fetch()
 
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):

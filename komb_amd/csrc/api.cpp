@@ -407,6 +407,60 @@ int komb_densest_subgraph_info(komb_ctx *ctx, int32_t *source, int32_t *k_best, 
     return KOMB_OK;
 }
 
+int komb_structural_clusters_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu)
+{
+    KOMB_HIER_ENTER(ctx, "komb_structural_clusters_run");
+    if (eps_num < 1 || eps_num > eps_den || eps_den > 1000000)
+        KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_structural_clusters_run: bad epsilon %d / %d (1 <= eps_num <= eps_den <= 1000000)", eps_num, eps_den);
+    if (mu < 2) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_structural_clusters_run: bad mu %d (at least 2)", mu);
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    return structural_run(ctx, eps_num, eps_den, mu);
+}
+
+int komb_structural_clusters_fetch(komb_ctx *ctx, int32_t *label, int32_t *size, int32_t *role, int32_t *sim_deg)
+{
+    KOMB_HIER_ENTER(ctx, "komb_structural_clusters_fetch");
+    if (!ctx->sc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_fetch: no structural clustering of the current k-truss result");
+    if (ctx->nv == 0) return KOMB_OK;
+    const size_t bytes = (size_t)ctx->nv * sizeof(int32_t);
+    if (label) KOMB_HIP(ctx, staged_copy(ctx, label, ctx->d_sc_label, bytes, false));
+    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_sc_size, bytes, false));
+    if (role) KOMB_HIP(ctx, staged_copy(ctx, role, ctx->d_sc_role, bytes, false));
+    if (sim_deg) KOMB_HIP(ctx, staged_copy(ctx, sim_deg, ctx->d_sc_simdeg, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_structural_clusters_fetch_edges(komb_ctx *ctx, int32_t *similar)
+{
+    KOMB_HIER_ENTER(ctx, "komb_structural_clusters_fetch_edges");
+    if (!ctx->sc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_fetch_edges: no structural clustering of the current k-truss result");
+    return structural_fetch_edges(ctx, similar);
+}
+
+int komb_structural_clusters_info(komb_ctx *ctx, int32_t *eps_num, int32_t *eps_den, int32_t *mu, int64_t *n_similar_edges,
+                                  int64_t *n_cores, int64_t *n_borders, int64_t *n_hubs, int64_t *n_outliers, int64_t *n_clusters,
+                                  int64_t *largest, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_structural_clusters_info");
+    if (!ctx->sc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_info: no structural clustering of the current k-truss result");
+    const komb_ctx::Structural &r = ctx->sc;
+    if (eps_num) *eps_num = r.eps_num;
+    if (eps_den) *eps_den = r.eps_den;
+    if (mu) *mu = r.mu;
+    if (n_similar_edges) *n_similar_edges = r.n_similar;
+    if (n_cores) *n_cores = r.n_cores;
+    if (n_borders) *n_borders = r.n_borders;
+    if (n_hubs) *n_hubs = r.n_hubs;
+    if (n_outliers) *n_outliers = r.n_outliers;
+    if (n_clusters) *n_clusters = r.n_clusters;
+    if (largest) *largest = r.largest;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_community_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_run");

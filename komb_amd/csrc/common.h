@@ -325,8 +325,22 @@ struct komb_ctx {
     double ch_ms = 0.0;                      // device time of the last run (HIP events)
     bool ch_done = false;
 
+    // ---- structural clustering (structural.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
+    // computed from and dropped with it (truss_free)
+    int32_t *d_sc_label = nullptr;           // [nv] the cluster of the vertex (smallest ORIGINAL id of its cores' class), -1 for a hub / an outlier
+    int32_t *d_sc_size = nullptr;            // [nv] vertices that carry that label, 0 for label -1
+    int32_t *d_sc_role = nullptr;            // [nv] KOMB_SC_*
+    int32_t *d_sc_simdeg = nullptr;          // [nv] similar edges at the vertex
+    uint8_t *d_sc_similar = nullptr;         // [t_ne] 1 for a similar edge
+    struct Structural {
+        int32_t eps_num = 0, eps_den = 0, mu = 0;
+        int64_t n_similar = 0, n_cores = 0, n_borders = 0, n_hubs = 0, n_outliers = 0, n_clusters = 0, largest = 0;
+        double ms = 0.0, ms_similar = 0.0;   // device time of the last run | of its similarity pass (HIP events)
+    } sc;
+    bool sc_done = false;
+
     // ---- k-truss results (canonical order)
-    int64_t t_ne = -1;                       // edges of the (sub)graph last run
+    int64_t t_ne = -1;                      // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
     uint2 *d_t_slice = nullptr;              // [t_ne] (start, length) of every internal edge's index slice: the length is the support the peel started from; komb_truss_fetch_support puts them in canonical
     uint32_t t_k_lo = 0, t_k_hi = 0;         // the canonical edges the last run materialised (komb_truss_run_slice: this rank's slice)
@@ -490,7 +504,10 @@ void communities_drop(komb_ctx *ctx);                         // communities.hip
 int community_hierarchy_run(komb_ctx *ctx);                   // community_hierarchy.hip: the k-truss result it needs checked by the caller
 int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
 void community_hierarchy_drop(komb_ctx *ctx);                 // community_hierarchy.hip: the result goes with the k-truss result it indexes
-int densest_run(komb_ctx *ctx, int32_t iters);                // densest.hip: the graph, iters and the k-core result checked by the caller
+int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu);   // structural.hip: the parameters and the k-truss result it needs checked by the caller
+int structural_fetch_edges(komb_ctx *ctx, int32_t *similar);  // structural.hip: similar[] of the last run as 0 | 1 words (host output)
+void structural_drop(komb_ctx *ctx);                          // structural.hip: the result goes with the k-truss result it indexes
+int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);
 int corea_ranks(komb_ctx *ctx, const int32_t *deg, const int32_t *core, int64_t n, double *rank_deg, double *rank_key);

@@ -55,6 +55,14 @@
 //                       -- one row per edge of trussness >= 3 in canonical order with the node it belongs to at its own
 //                       trussness.  VIDs depend on -t, so only the forest by Name compares between runs.  Nothing else
 //                       changes.
+//   KOMB_STRUCTURAL=<num>/<den>,<mu>  (for example 7/10,3) also write structural_clusters.tsv: the structural clustering
+//                       (komb_structural_clusters_run, eps = num/den, mu) of a whole-graph k-truss run of its own, made
+//                       before the KOMB_TRUSS stage, which then runs on the max core exactly as without it.  #VID, Name,
+//                       Role, Cluster, ClusterSize, SimilarNeighbours -- one row per unitig in VID order; Role is core,
+//                       border, hub or outlier; Cluster the Name of the unitig with the smallest VID among the cluster's
+//                       cores, or - for a hub / an outlier; ClusterSize its number of unitigs (0 then);
+//                       SimilarNeighbours the unitig's number of similar edges.  VIDs depend on -t, so only the
+//                       partition by Name compares between runs.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -606,6 +614,40 @@ void write_densest(komb_ctx *ctx, int32_t iters, const std::string &outdir, cons
     fclose(fp);
 }
 
+// KOMB_STRUCTURAL: a whole-graph k-truss run of its own and komb_structural_clusters_run on it as one table, one row per vertex
+// in VID order
+void write_structural(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu, const std::string &outdir, const Names &names,
+                      int64_t nv, int threads)
+{
+    std::vector<int32_t> label((size_t)nv), size((size_t)nv), role((size_t)nv), simdeg((size_t)nv);
+    if (nv > 0) {
+        int rc = komb_truss_run(ctx, nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_truss_run", rc);
+        rc = komb_structural_clusters_run(ctx, eps_num, eps_den, mu);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_structural_clusters_run", rc);
+        rc = komb_structural_clusters_fetch(ctx, label.data(), size.data(), role.data(), simdeg.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_structural_clusters_fetch", rc);
+    }
+    const std::string path = outdir + "/structural_clusters.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tRole\tCluster\tClusterSize\tSimilarNeighbours\n");
+    static const char *const kRole[4] = {"outlier", "hub", "border", "core"};
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        char tmp[48];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        buf.push_back('\t');
+        buf.append(kRole[role[(size_t)i] & 3]);
+        buf.push_back('\t');
+        if (label[(size_t)i] >= 0) buf.append(names.name[(size_t)label[(size_t)i]]); else buf.push_back('-');
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)size[(size_t)i], (int)simdeg[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_HIERARCHY: komb_hierarchy_run of `kind` as two tables: <prefix>_hierarchy.tsv, one row per node in node order, and
 // <prefix>_hierarchy_vertices.tsv, one row per member vertex in VID order (level(v): its coreness / its largest trussness)
 template <class LevelFn>
@@ -1038,6 +1080,21 @@ int main(int argc, const char **argv)
             fprintf(stderr, "komb2: KOMB_COMMUNITIES=%s: expected a trussness threshold >= 0 or max\n", comm_env);
             leave(EXIT_FAILURE);
         }
+    }
+
+    // structural clustering of the whole graph (no counterpart in the reference; opt-in): KOMB_STRUCTURAL=<num>/<den>,<mu>.  It
+    // makes a whole-graph k-truss run of its own, before the truss stage below replaces that result with the max core's.
+    const char *sc_env = getenv("KOMB_STRUCTURAL");
+    if (sc_env && *sc_env) {
+        char *end = nullptr;
+        const long num = strtol(sc_env, &end, 10);
+        const long den = end != sc_env && *end == '/' && end[1] >= '0' && end[1] <= '9' ? strtol(end + 1, &end, 10) : -1;
+        const long mu = den >= 0 && *end == ',' && end[1] >= '0' && end[1] <= '9' ? strtol(end + 1, &end, 10) : -1;
+        if (mu < 2 || *end || num < 1 || num > den || den > 1000000L || mu > 2147483647L) {
+            fprintf(stderr, "komb2: KOMB_STRUCTURAL=%s: expected <num>/<den>,<mu> with 1 <= num <= den <= 1000000 and mu >= 2\n", sc_env);
+            leave(EXIT_FAILURE);
+        }
+        write_structural(ctx, (int32_t)num, (int32_t)den, (int32_t)mu, args.outdir, names, nv, args.threads);
     }
 
     // runTruss (src/graph.cpp:486-563) -- disabled in the reference at :478, opt-in here
