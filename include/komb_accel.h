@@ -115,7 +115,8 @@ int         komb_abi_version(void);
  * longer reads: ambient environment cannot change which engine a drop-in runs).  None changes a result.  name: FINISH
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
- * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, COMP_SAMPLE (0 | 1:
+ * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), and the
+ * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
  * allocation the context hands out is filled with that 32-bit word first -- tests of reads of memory nothing wrote)
@@ -402,6 +403,48 @@ int komb_structural_clusters_fetch_edges(komb_ctx *ctx, int32_t *similar /*[ne_s
 int komb_structural_clusters_info(komb_ctx *ctx, int32_t *eps_num, int32_t *eps_den, int32_t *mu, int64_t *n_similar_edges,
                                   int64_t *n_cores, int64_t *n_borders, int64_t *n_hubs, int64_t *n_outliers, int64_t *n_clusters,
                                   int64_t *largest, double *ms);                                                     /* any may be NULL */
+
+/* ---- (3,4)-nucleus decomposition: triangles peeled by 4-cliques ----------- */
+/* The third rung of the nucleus ladder of Sariyuce, Seshadhri, Pinar, Catalyurek ("Finding the hierarchy of dense subgraphs
+ * using nucleus decompositions", WWW 2015): k-core peels vertices by edges (1,2), k-truss peels edges by triangles (2,3),
+ * this peels TRIANGLES by the 4-CLIQUES they lie in (3,4).  A triangle-rich region that is no near-clique has a high
+ * trussness and a low nucleus number.
+ * Input: the last COMPLETE k-truss result on the resident graph, whole graph or vmask run alike -- its ne_sub canonical edges
+ * (eu[i], ev[i]), eu < ev, sorted by (eu, ev), original vertex ids.  Call their graph H.
+ * A TRIANGLE is a < b < c with all three edges in H.  Triangles are numbered in ascending (a, b, c) order, which is also the
+ * order (canonical index of (a, b), c).  A 4-CLIQUE is a < b < c < d with all six edges in H.  key0[t] is the number of
+ * 4-cliques that contain triangle t.
+ * theta(t), the NUCLEUS NUMBER, is the largest k such that t belongs to a family S of triangles in which every member lies
+ * in at least k 4-cliques whose four triangles are all in S.  No connectivity condition is applied, exactly as coreness has
+ * none.  A triangle in no 4-clique has theta = 0; K_n gives theta = n - 3 on every triangle; theta <= key0.  theta is unique:
+ * nothing in any output depends on the run, on scheduling or on an option.
+ * edge_theta[i] is the largest theta over the triangles through canonical edge i, -1 if there is none; vertex_theta[v] is the
+ * same per vertex.
+ * komb_nucleus_count: the triangles of the result.  komb_nucleus_fetch: a, b, c, key0, theta, [n_triangles] each.
+ * komb_nucleus_fetch_edges: edge_theta[ne_sub], canonical order.  komb_nucleus_fetch_vertices: vertex_theta[nv].
+ * komb_nucleus_info: triangles, 4-cliques, the largest theta (-1 without a triangle), n_levels -- the distinct values of
+ * theta --, n_subrounds -- the frontiers the level-synchronous peel went through, >= n_levels --, and ms, the device time
+ * of the run on the context's HIP-event timer.  Any output pointer may be NULL.
+ * No context or no graph loaded: KOMB_ERR_ARG.  Without a completed k-truss result on this graph, after komb_truss_run_slice
+ * / a sharded run that materialised only part of the canonical edges, after komb_truss_unprepare, count / fetch / info
+ * before a run: KOMB_ERR_STATE.  A result without triangles is not an error: the count is 0, every edge_theta and
+ * vertex_theta is -1 and theta_max = -1.  More than 2^31 - 1 triangles or more than 2^30 - 1 4-cliques: KOMB_ERR_LIMIT
+ * (clique ids are 32-bit and a clique has four incidences); each count is checked after its count pass and before the
+ * storage it sizes is reserved.  A pool failure: KOMB_ERR_NOMEM.
+ * The result lives in arrays of its own, installed when a run has succeeded: a refused or failed run leaves the previous
+ * result readable.  It indexes one k-truss result: whatever replaces or drops that result -- a new k-truss run of any kind,
+ * komb_truss_unprepare, a graph load -- drops it too.  No other call changes or drops it; a run changes no other result, no
+ * komb_stats field and not the resident k-truss preparation.  Options (none changes a result): NUC_SHORT / NUC_HEAVY move the
+ * lengths at which a walked side goes from its lane to its wave (default 16) / in the triangle pass to several workgroups
+ * (default 2048); NUC_CAP=<n> refuses above n 4-cliques with KOMB_ERR_LIMIT (tests of the refusal); NUC_DEBUG prints one
+ * stderr line with the counts and the device times of the passes. */
+int komb_nucleus_run(komb_ctx *ctx);
+int komb_nucleus_count(komb_ctx *ctx, int64_t *n_triangles);
+int komb_nucleus_fetch(komb_ctx *ctx, int32_t *a, int32_t *b, int32_t *c, int32_t *key0, int32_t *theta);   /* [n_triangles] each, any may be NULL */
+int komb_nucleus_fetch_edges(komb_ctx *ctx, int32_t *edge_theta);      /* [ne_sub], canonical order */
+int komb_nucleus_fetch_vertices(komb_ctx *ctx, int32_t *vertex_theta); /* [nv] */
+int komb_nucleus_info(komb_ctx *ctx, int64_t *n_triangles, int64_t *n_cliques4, int32_t *theta_max,
+                      int32_t *n_levels, int64_t *n_subrounds, double *ms);   /* any may be NULL */
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

@@ -114,6 +114,13 @@ SIGNATURES = {
     "komb_structural_clusters_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                              ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                              ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_nucleus_run": (_i32, [_vp]),
+    "komb_nucleus_count": (_i32, [_vp, ctypes.POINTER(_i64)]),
+    "komb_nucleus_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "komb_nucleus_fetch_edges": (_i32, [_vp, _vp]),
+    "komb_nucleus_fetch_vertices": (_i32, [_vp, _vp]),
+    "komb_nucleus_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32),
+                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

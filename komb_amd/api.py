@@ -41,7 +41,8 @@ def gen_hug_edges(nv, n_cliques, alpha=2.6, seed=42):
 FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
-                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG", "POISON")
+                "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
+                "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -463,6 +464,52 @@ class KombAccel:
         """(label, size, role, sim_deg) of the structural clustering of the last k-truss result."""
         self.structural_clusters_run(eps_num, eps_den, mu)
         return self.structural_clusters_fetch()
+
+    # ---- (3,4)-nucleus decomposition: triangles of the last k-truss result peeled by their 4-cliques (include/komb_accel.h)
+    NUCLEUS_FIELDS = ("a", "b", "c", "key0", "theta")
+
+    def nucleus_run(self):
+        """Needs a complete k-truss result on this graph."""
+        self._sync_env_options()
+        self._check(self._lib.komb_nucleus_run(self._ctx))
+
+    def nucleus_fetch(self):
+        """{"a", "b", "c", "key0", "theta"}: int32[n_triangles] each, the triangles a < b < c in ascending (a, b, c) order, the
+        4-cliques each lies in and its nucleus number."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_nucleus_count(self._ctx, ctypes.byref(n)))
+        out = {name: _out_i32(max(n.value, 0)) for name in self.NUCLEUS_FIELDS}
+        self._check(self._lib.komb_nucleus_fetch(self._ctx, *(ptr(out[name]) for name in self.NUCLEUS_FIELDS)))
+        return out
+
+    def nucleus_fetch_edges(self):
+        """edge_theta int32[ne_sub]: the largest theta over the triangles through every canonical edge, -1 without one."""
+        self._check(self._lib.komb_nucleus_count(self._ctx, None))                 # (the decomposition's own errors first)
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_truss_count(self._ctx, ctypes.byref(n)))
+        edge_theta = _out_i32(max(n.value, 0))
+        self._check(self._lib.komb_nucleus_fetch_edges(self._ctx, ptr(edge_theta)))
+        return edge_theta
+
+    def nucleus_fetch_vertices(self):
+        """vertex_theta int32[nv]: the largest theta over the triangles at every vertex, -1 without one."""
+        vertex_theta = _out_i32(max(self.nv, 0))
+        self._check(self._lib.komb_nucleus_fetch_vertices(self._ctx, ptr(vertex_theta)))
+        return vertex_theta
+
+    def nucleus_info(self):
+        """{"n_triangles", "n_cliques4", "theta_max", "n_levels", "n_subrounds", "ms"} of the last komb_nucleus_run."""
+        tri, clq, sub, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        tmax, lev = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._lib.komb_nucleus_info(self._ctx, ctypes.byref(tri), ctypes.byref(clq), ctypes.byref(tmax), ctypes.byref(lev),
+                                                ctypes.byref(sub), ctypes.byref(ms)))
+        return {"n_triangles": tri.value, "n_cliques4": clq.value, "theta_max": tmax.value, "n_levels": lev.value,
+                "n_subrounds": sub.value, "ms": ms.value}
+
+    def run_nucleus(self):
+        """(triangles, edge_theta, vertex_theta): the dict of nucleus_fetch and the per-edge / per-vertex maxima."""
+        self.nucleus_run()
+        return self.nucleus_fetch(), self.nucleus_fetch_edges(), self.nucleus_fetch_vertices()
 
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):

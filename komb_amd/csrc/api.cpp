@@ -461,6 +461,67 @@ int komb_structural_clusters_info(komb_ctx *ctx, int32_t *eps_num, int32_t *eps_
     return KOMB_OK;
 }
 
+int komb_nucleus_run(komb_ctx *ctx)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_run");
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    return nucleus_run(ctx);
+}
+
+int komb_nucleus_count(komb_ctx *ctx, int64_t *n_triangles)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_count");
+    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_count: no nucleus decomposition of the current k-truss result");
+    if (n_triangles) *n_triangles = ctx->nuc.n_tri;
+    return KOMB_OK;
+}
+
+int komb_nucleus_fetch(komb_ctx *ctx, int32_t *a, int32_t *b, int32_t *c, int32_t *key0, int32_t *theta)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_fetch");
+    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_fetch: no nucleus decomposition of the current k-truss result");
+    const size_t bytes = (size_t)ctx->nuc.n_tri * sizeof(int32_t);
+    if (bytes == 0) return KOMB_OK;
+    int32_t *const out[5] = {a, b, c, key0, theta};
+    const int32_t *const src[5] = {ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_nuc_key0, ctx->d_nuc_theta};
+    for (int i = 0; i < 5; ++i)
+        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], src[i], bytes, false));
+    return KOMB_OK;
+}
+
+int komb_nucleus_fetch_edges(komb_ctx *ctx, int32_t *edge_theta)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_fetch_edges");
+    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_fetch_edges: no nucleus decomposition of the current k-truss result");
+    if (ctx->t_ne > 0 && edge_theta) KOMB_HIP(ctx, staged_copy(ctx, edge_theta, ctx->d_nuc_edge, (size_t)ctx->t_ne * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_nucleus_fetch_vertices(komb_ctx *ctx, int32_t *vertex_theta)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_fetch_vertices");
+    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_fetch_vertices: no nucleus decomposition of the current k-truss result");
+    if (ctx->nv > 0 && vertex_theta) KOMB_HIP(ctx, staged_copy(ctx, vertex_theta, ctx->d_nuc_vertex, (size_t)ctx->nv * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+int komb_nucleus_info(komb_ctx *ctx, int64_t *n_triangles, int64_t *n_cliques4, int32_t *theta_max, int32_t *n_levels, int64_t *n_subrounds, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_info");
+    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_info: no nucleus decomposition of the current k-truss result");
+    const komb_ctx::Nucleus &r = ctx->nuc;
+    if (n_triangles) *n_triangles = r.n_tri;
+    if (n_cliques4) *n_cliques4 = r.n_clq;
+    if (theta_max) *theta_max = r.theta_max;
+    if (n_levels) *n_levels = r.n_levels;
+    if (n_subrounds) *n_subrounds = r.n_subrounds;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_community_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_run");

@@ -339,6 +339,20 @@ struct komb_ctx {
     } sc;
     bool sc_done = false;
 
+    // ---- (3,4)-nucleus decomposition (nucleus.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
+    // computed from and dropped with it (truss_free)
+    int32_t *d_nuc_a = nullptr, *d_nuc_b = nullptr, *d_nuc_c = nullptr;   // [n_tri] the triangles a < b < c in ascending (a, b, c) order, ORIGINAL ids
+    int32_t *d_nuc_key0 = nullptr;           // [n_tri + 1] the 4-cliques of the result the triangle lies in
+    int32_t *d_nuc_theta = nullptr;          // [n_tri] its nucleus number
+    int32_t *d_nuc_edge = nullptr;           // [t_ne] largest theta over the triangles through the canonical edge, -1 without one
+    int32_t *d_nuc_vertex = nullptr;         // [nv] the same per vertex
+    struct Nucleus {
+        int64_t n_tri = 0, n_clq = 0, n_subrounds = 0;
+        int32_t theta_max = -1, n_levels = 0;
+        double ms = 0.0, ms_tri = 0.0, ms_clq = 0.0, ms_peel = 0.0;   // device time of the last run | of its passes (HIP events; option NUC_DEBUG prints them)
+    } nuc;
+    bool nuc_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                      // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -507,6 +521,8 @@ void community_hierarchy_drop(komb_ctx *ctx);                 // community_hiera
 int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu);   // structural.hip: the parameters and the k-truss result it needs checked by the caller
 int structural_fetch_edges(komb_ctx *ctx, int32_t *similar);  // structural.hip: similar[] of the last run as 0 | 1 words (host output)
 void structural_drop(komb_ctx *ctx);                          // structural.hip: the result goes with the k-truss result it indexes
+int nucleus_run(komb_ctx *ctx);                               // nucleus.hip: the k-truss result it needs checked by the caller
+void nucleus_drop(komb_ctx *ctx);                             // nucleus.hip: the result goes with the k-truss result it indexes
 int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);

@@ -1,0 +1,654 @@
+// nucleus.hip -- the (3,4)-nucleus decomposition (komb_nucleus_run): triangles peeled by the 4-cliques they lie in, the
+// third rung of the nucleus ladder of Sariyuce, Seshadhri, Pinar, Catalyurek ("Finding the hierarchy of dense subgraphs
+// using nucleus decompositions", WWW 2015) after k-core (1,2) and k-truss (2,3).  DESIGN.md section 4.6h.
+//
+// Input: the canonical edges (eu[i] < ev[i], sorted by (eu, ev), original ids) of the last complete k-truss result, whole
+// graph and vmask runs alike.  As in communities.hip the list is an oriented CSR: row a = the positions [rs[a], re[a]) with
+// eu == a, their ev ascending.
+//
+// The launches of a run:
+//   k_nuc_rows                    row bounds
+//   k_nuc_tri<count>, <fill>      triangles a < b < c from edge j = (a, b): c is in row a behind j and in row b; the shorter
+//                                 side is walked, the longer one bisected.  A short side stays with the edge's lane, a medium
+//                                 one is walked by its wave, a long one is queued for k_nuc_tri_heavy (several workgroups,
+//                                 each a contiguous part of the side).  Counts -> exclusive sum -> tri_ptr[m + 1]; the fill
+//                                 writes the third vertices ASCENDING within an edge, so id(a, b, c) = tri_ptr[pos(a, b)] +
+//                                 rank of c: triangle order is (a, b, c) order, and an id is one bisection away.
+//   k_nuc_clq<count>, <fill>      THE HOT PASS.  4-cliques a < b < c < d from triangle t = (a, b, c): d is behind c in rows
+//                                 a and b and anywhere in row c (all of row c is above c).  The shortest of the three tails
+//                                 is walked, the other two bisected; a d found in all three closes a clique, and three
+//                                 bisections in tc[], on the triangle's own edges (a, b), (a, c), (b, c), give the ids of
+//                                 (a, b, d), (a, c, d), (b, c, d).  One 16-byte record of four triangle ids per clique; key0
+//                                 by atomicAdd.  Storage is reserved from the COUNT.
+//   k_nuc_inc                     the per-triangle incidence lists (inc_ptr = exclusive sum of key0; clique ids)
+//   the peel (below)              level-synchronous over the triangles with a live key
+//   k_nuc_out                     edge_theta / vertex_theta by atomicMax, skipped when a relaxed read shows it cannot land
+//
+// The peel.  theta[t] < 0 marks a live triangle; key[t] is its number of live cliques.  A level k starts from
+// k_nuc_min (k = the smallest live key) and k_nuc_collect (the live triangles with key <= k: the first frontier).  A
+// sub-round is two launches: k_nuc_stamp writes theta = k on its frontier, and only then k_nuc_walk goes through the
+// frontier's incidence lists -- so the walk reads stamps a PREVIOUS launch wrote and needs no hand-off inside a launch.
+// A clique is retired once, by whoever wins the atomicExch on its word; its members that are still live take an atomicSub,
+// and the one decrement that lands a key on exactly k appends the triangle to the next sub-round's queue (later decrements
+// take it below k; it is stamped k all the same).  The host reads the 64-byte control block once per sub-round and
+// launches the next, or the next level when the queue is empty.  No workgroup waits for another.  Bounds: every sub-round
+// that is launched retires at least one triangle, so there are at most n_triangles of them; a triangle enters a queue
+// once, so a queue of n_triangles words cannot overflow (appends are guarded all the same); the device loops run over row
+// parts, incidence lists and queue lengths that are fixed before the launch.
+#include "common.h"
+
+namespace komb {
+
+namespace {
+
+constexpr uint32_t kNucShort = 16;          // walked side up to this long: the unit's own lane
+constexpr uint32_t kNucHeavy = 2048;        // triangle pass: from this length on several workgroups of k_nuc_tri_heavy (between: the wave)
+constexpr int kNucHeavyGrid = 256, kNucHeavyChunks = 8;     // k_nuc_tri_heavy: edges side by side x parts of one side
+constexpr int kNucSweepGrid = 2048;         // sweeps over all triangles and frontiers of unknown length: workgroups, each over several tiles
+constexpr uint32_t kNucNone = 0xFFFFFFFFu;
+constexpr int64_t kNucMaxTri = 0x7FFFFFFFll, kNucMaxClq = 0x3FFFFFFFll;
+
+struct NucCtl {                             // 64 bytes, zeroed before every run
+    unsigned long long n_tri, n_clq;        // counted by the two count passes
+    uint32_t n_heavy;                       // edges for k_nuc_tri_heavy: counted by the count pass, which sizes their queue ...
+    uint32_t n_queued;                      // ... and the cursor k_nuc_queue fills it with
+    uint32_t bad;                           // a triangle id that a bisection did not find (cannot happen; checked)
+    int32_t kmin;                           // the level: smallest live key (k_nuc_min)
+    uint32_t n_q[2];                        // entries of the two frontier queues
+    uint32_t pad[6];
+};
+static_assert(sizeof(NucCtl) == 64, "NucCtl layout");
+
+struct NucTri {                             // per triangle: vertices (the result), the position of (a, b), of (a, c), of (b, c)
+    int32_t *a, *b, *c;
+    uint32_t *j, *pac, *pbc;
+};
+
+inline int nuc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
+inline int nuc_sweep(int64_t n) { const int g = nuc_grid(n); return g < 1 ? 1 : (g < kNucSweepGrid ? g : kNucSweepGrid); }
+
+// row bounds per original vertex (rs / re zeroed before: a vertex without a row has an empty one)
+__global__ void k_nuc_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    const int32_t u = eu[j];
+    if (j == 0 || eu[j - 1] != u) rs[u] = j;
+    if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
+}
+
+// the position of x in ev[lo, end) (ascending), kNucNone if it is not there
+__device__ __forceinline__ uint32_t nuc_find(const int32_t *__restrict__ ev, int32_t x, uint32_t lo, uint32_t end)
+{
+    uint32_t hi = end;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (ev[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && ev[lo] == x ? lo : kNucNone;
+}
+
+__device__ __forceinline__ unsigned long long nuc_below(int lane) { return (1ull << lane) - 1ull; }
+
+// the two sides of edge j = (a, b): [it, it + n) is walked, [lo, hi) is searched; n <= hi - lo
+struct NucSides { uint32_t it, n, lo, hi; bool walk_a; };
+
+__device__ __forceinline__ NucSides nuc_sides(const int32_t *__restrict__ eu, const int32_t *__restrict__ ev,
+                                              const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t j)
+{
+    const int32_t a = eu[j], b = ev[j];
+    const uint32_t ab = j + 1, ae = re[a], bb = rs[b], be = re[b];   // (row a holds j: ae > j)
+    const uint32_t la = ae - ab, lb = be - bb;
+    NucSides s;
+    s.walk_a = la <= lb;
+    if (s.walk_a) { s.it = ab; s.n = la; s.lo = bb; s.hi = be; }
+    else { s.it = bb; s.n = lb; s.lo = ab; s.hi = ae; }
+    if (s.hi == s.lo) s.n = 0;
+    return s;
+}
+
+__device__ __forceinline__ void nuc_emit(const NucTri &o, uint32_t t, uint32_t j, int32_t a, int32_t b, int32_t c, uint32_t x, uint32_t hit, bool walk_a)
+{
+    o.a[t] = a; o.b[t] = b; o.c[t] = c;
+    o.j[t] = j; o.pac[t] = walk_a ? x : hit; o.pbc[t] = walk_a ? hit : x;
+}
+
+// The triangle pass: one lane per edge.  !kFill: cnt[j] = the triangles of edge j found here (an edge with a long side: 0,
+// it is counted in ctl->n_heavy and the heavy kernel adds its own), cnt[m] = 0, the total into ctl.  kFill: triangle tri_ptr[j] + r for the r-th hit, the walked side
+// ascending.
+template <bool kFill>
+__global__ void k_nuc_tri(const int32_t *__restrict__ eu, const int32_t *__restrict__ ev, const uint32_t *__restrict__ rs,
+                          const uint32_t *__restrict__ re, uint32_t m, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ tri_ptr,
+                          NucCtl *ctl, uint32_t n_short, uint32_t n_heavy, NucTri o)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    NucSides s{0, 0, 0, 0, true};
+    if (j < m) s = nuc_sides(eu, ev, rs, re, j);
+    bool act = s.n > 0;
+    if (act && s.n >= n_heavy) {
+        if (!kFill) atomicAdd(&ctl->n_heavy, 1u);
+        act = false;
+    }
+    const bool mid = act && s.n > n_short;
+    uint32_t mine = 0;
+    if (act && !mid) {
+        const int32_t a = eu[j], b = ev[j];
+        const uint32_t base = kFill ? tri_ptr[j] : 0u;
+        for (uint32_t x = s.it; x < s.it + s.n; ++x) {
+            const int32_t c = ev[x];
+            const uint32_t hit = nuc_find(ev, c, s.lo, s.hi);
+            if (hit == kNucNone) continue;
+            if (kFill) nuc_emit(o, base + mine, j, a, b, c, x, hit, s.walk_a);
+            ++mine;
+        }
+    }
+    unsigned long long todo = __ballot(mid);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const uint32_t rj = (uint32_t)__shfl((int32_t)j, src), rit = (uint32_t)__shfl((int32_t)s.it, src), rn = (uint32_t)__shfl((int32_t)s.n, src);
+        const uint32_t rlo = (uint32_t)__shfl((int32_t)s.lo, src), rhi = (uint32_t)__shfl((int32_t)s.hi, src);
+        const bool rwa = __shfl((int32_t)s.walk_a, src) != 0;
+        const int32_t a = eu[rj], b = ev[rj];
+        const uint32_t base = kFill ? tri_ptr[rj] : 0u;
+        uint32_t run = 0;
+        for (uint32_t x0 = rit; x0 < rit + rn; x0 += kWave) {              // (uniform per wave: the ballots see every lane)
+            const uint32_t x = x0 + (uint32_t)lane;
+            int32_t c = 0;
+            uint32_t hit = kNucNone;
+            if (x < rit + rn) { c = ev[x]; hit = nuc_find(ev, c, rlo, rhi); }
+            const unsigned long long hits = __ballot(hit != kNucNone);
+            if (kFill && hit != kNucNone) nuc_emit(o, base + run + (uint32_t)__popcll(hits & nuc_below(lane)), rj, a, b, c, x, hit, rwa);
+            run += (uint32_t)__popcll(hits);
+        }
+        if (lane == src) mine = run;
+    }
+    if (!kFill) {
+        if (j <= m) cnt[j] = j < m ? mine : 0u;
+        unsigned long long sum = mine;
+        for (int off = kWave / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        if (lane == 0 && sum) atomicAdd(&ctl->n_tri, sum);
+    }
+}
+
+// the queue of the edges with a long side, sized from the count pass's n_heavy (cap); its order is whatever the atomics give
+// and stays as it is for both heavy launches
+__global__ void k_nuc_queue(const int32_t *__restrict__ eu, const int32_t *__restrict__ ev, const uint32_t *__restrict__ rs,
+                            const uint32_t *__restrict__ re, uint32_t m, uint32_t n_heavy, NucCtl *ctl, uint32_t *__restrict__ heavy, uint32_t cap)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m || nuc_sides(eu, ev, rs, re, j).n < n_heavy) return;
+    const uint32_t slot = atomicAdd(&ctl->n_queued, 1u);
+    if (slot < cap) heavy[slot] = j;                     // (the same edges the count pass counted: slot < cap)
+}
+
+// The queued edges: block (x, y) takes the edges x, x + gridDim.x, ... of the queue and of each the y-th of gridDim.y
+// contiguous parts of its walked side, 256 entries at a time in ascending order.  !kFill: part[h * gridDim.y + y] = the
+// hits of the part, added to cnt[j] and to the total.  kFill: the part starts behind the hits of the parts before it.
+template <bool kFill>
+__global__ void k_nuc_tri_heavy(const int32_t *__restrict__ eu, const int32_t *__restrict__ ev, const uint32_t *__restrict__ rs,
+                                const uint32_t *__restrict__ re, uint32_t *cnt, const uint32_t *__restrict__ tri_ptr, NucCtl *ctl,
+                                const uint32_t *__restrict__ heavy, uint32_t n_queued, uint32_t *__restrict__ part, NucTri o)
+{
+    __shared__ uint32_t s_w[kBlock / kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    for (uint32_t h = blockIdx.x; h < n_queued; h += gridDim.x) {
+        const uint32_t j = heavy[h];
+        const NucSides s = nuc_sides(eu, ev, rs, re, j);
+        const uint32_t end = s.it + s.n, seg = (s.n + gridDim.y - 1) / gridDim.y;
+        uint32_t x0 = s.it + blockIdx.y * seg, x1 = x0 + seg;
+        if (x0 > end) x0 = end;
+        if (x1 > end) x1 = end;
+        const int32_t a = eu[j], b = ev[j];
+        uint32_t run = 0;
+        if (kFill) {
+            run = tri_ptr[j];
+            for (uint32_t y = 0; y < blockIdx.y; ++y) run += part[(size_t)h * gridDim.y + y];
+        }
+        for (uint32_t xb = x0; xb < x1; xb += kBlock) {                    // (uniform per workgroup)
+            const uint32_t x = xb + threadIdx.x;
+            int32_t c = 0;
+            uint32_t hit = kNucNone;
+            if (x < x1) { c = ev[x]; hit = nuc_find(ev, c, s.lo, s.hi); }
+            const unsigned long long hits = __ballot(hit != kNucNone);
+            if (lane == 0) s_w[wave] = (uint32_t)__popcll(hits);
+            __syncthreads();
+            uint32_t before = 0, all = 0;
+            for (int w = 0; w < kBlock / kWave; ++w) { before += w < wave ? s_w[w] : 0u; all += s_w[w]; }
+            if (kFill && hit != kNucNone) nuc_emit(o, run + before + (uint32_t)__popcll(hits & nuc_below(lane)), j, a, b, c, x, hit, s.walk_a);
+            run += all;
+            __syncthreads();
+        }
+        if (!kFill && threadIdx.x == 0) {
+            part[(size_t)h * gridDim.y + blockIdx.y] = run;
+            if (run) { atomicAdd(cnt + j, run); atomicAdd(&ctl->n_tri, (unsigned long long)run); }
+        }
+    }
+}
+
+// The three tails of triangle t = (a, b, c) a fourth vertex d > c can be in: row a behind (a, c), row b behind (b, c), all of
+// row c.  [it, it + n) is the shortest and is walked; the other two are searched.
+struct NucTails { uint32_t it, n, lo1, hi1, lo2, hi2; };
+
+__device__ __forceinline__ NucTails nuc_tails(const NucTri &o, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t t)
+{
+    const int32_t a = o.a[t], b = o.b[t], c = o.c[t];
+    const uint32_t al = o.pac[t] + 1, ah = re[a], bl = o.pbc[t] + 1, bh = re[b], cl = rs[c], ch = re[c];
+    const uint32_t na = ah - al, nb = bh - bl, nc = ch - cl;
+    NucTails s;
+    if (na <= nb && na <= nc) { s.it = al; s.n = na; s.lo1 = bl; s.hi1 = bh; s.lo2 = cl; s.hi2 = ch; }
+    else if (nb <= nc) { s.it = bl; s.n = nb; s.lo1 = al; s.hi1 = ah; s.lo2 = cl; s.hi2 = ch; }
+    else { s.it = cl; s.n = nc; s.lo1 = al; s.hi1 = ah; s.lo2 = bl; s.hi2 = bh; }
+    return s;                                            // (the walked tail is the shortest: an empty tail gives n = 0)
+}
+
+// the id of the triangle of the edge at position e whose third vertex is d: a bisection in e's ascending part of tc[]
+__device__ __forceinline__ uint32_t nuc_tri_id(const uint32_t *__restrict__ tri_ptr, const int32_t *__restrict__ tc, uint32_t e, int32_t d,
+                                               uint32_t fallback, NucCtl *ctl)
+{
+    uint32_t lo = tri_ptr[e];
+    const uint32_t end = tri_ptr[e + 1];
+    uint32_t hi = end;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (tc[mid] < d) lo = mid + 1; else hi = mid;
+    }
+    if (lo < end && tc[lo] == d) return lo;
+    ctl->bad = 1u;                                       // (three edges of the result that close a triangle the fill did not write)
+    return fallback;
+}
+
+// entry x of the walked tail: a 4-clique iff its vertex d is in the other two tails as well
+__device__ __forceinline__ bool nuc_clq_entry(const int32_t *__restrict__ ev, const NucTails &s, uint32_t x)
+{
+    const int32_t d = ev[x];
+    return nuc_find(ev, d, s.lo1, s.hi1) != kNucNone && nuc_find(ev, d, s.lo2, s.hi2) != kNucNone;
+}
+
+// record q: triangle t and the three triangles its vertices make with d = ev[x].  They hang on t's own edges (a, b), (a, c),
+// (b, c), so the positions of (a, d), (b, d), (c, d) the searches found are not needed again.
+__device__ __forceinline__ void nuc_clq_write(const int32_t *__restrict__ ev, const NucTri &o, const uint32_t *__restrict__ tri_ptr,
+                                              uint32_t t, uint32_t x, uint32_t q, uint4 *__restrict__ clq, uint32_t *key0, NucCtl *ctl)
+{
+    const int32_t d = ev[x];
+    uint4 r;
+    r.x = t;
+    r.y = nuc_tri_id(tri_ptr, o.c, o.j[t], d, t, ctl);       // (a, b, d)
+    r.z = nuc_tri_id(tri_ptr, o.c, o.pac[t], d, t, ctl);     // (a, c, d)
+    r.w = nuc_tri_id(tri_ptr, o.c, o.pbc[t], d, t, ctl);     // (b, c, d)
+    clq[q] = r;
+    atomicAdd(key0 + r.y, 1u); atomicAdd(key0 + r.z, 1u); atomicAdd(key0 + r.w, 1u);
+}
+
+// The 4-clique pass: one lane per triangle; a walked tail above n_short goes through the triangle's wave.  !kFill:
+// qcnt[t] = the cliques whose smallest triangle is t, qcnt[n_tri] = 0, the total into ctl.  kFill: the records at
+// q_ptr[t] + r, key0 of the other three triangles by atomics, of t itself by one add of its count.
+template <bool kFill>
+__global__ void k_nuc_clq(const int32_t *__restrict__ ev, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, NucTri o,
+                          uint32_t n_tri, const uint32_t *__restrict__ tri_ptr, uint32_t *__restrict__ qcnt, const uint32_t *__restrict__ q_ptr,
+                          uint4 *__restrict__ clq, uint32_t *key0, NucCtl *ctl, uint32_t n_short)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    NucTails s{0, 0, 0, 0, 0, 0};
+    if (t < n_tri) s = nuc_tails(o, rs, re, t);
+    const bool act = s.n > 0, mid = act && s.n > n_short;
+    uint32_t mine = 0;
+    if (act && !mid) {
+        const uint32_t base = kFill ? q_ptr[t] : 0u;
+        for (uint32_t x = s.it; x < s.it + s.n; ++x) {
+            if (!nuc_clq_entry(ev, s, x)) continue;
+            if (kFill) nuc_clq_write(ev, o, tri_ptr, t, x, base + mine, clq, key0, ctl);
+            ++mine;
+        }
+    }
+    unsigned long long todo = __ballot(mid);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const uint32_t rt = (uint32_t)__shfl((int32_t)t, src);
+        NucTails r;
+        r.it = (uint32_t)__shfl((int32_t)s.it, src); r.n = (uint32_t)__shfl((int32_t)s.n, src);
+        r.lo1 = (uint32_t)__shfl((int32_t)s.lo1, src); r.hi1 = (uint32_t)__shfl((int32_t)s.hi1, src);
+        r.lo2 = (uint32_t)__shfl((int32_t)s.lo2, src); r.hi2 = (uint32_t)__shfl((int32_t)s.hi2, src);
+        const uint32_t base = kFill ? q_ptr[rt] : 0u;
+        uint32_t run = 0;
+        for (uint32_t x0 = r.it; x0 < r.it + r.n; x0 += kWave) {          // (uniform per wave)
+            const uint32_t x = x0 + (uint32_t)lane;
+            const bool hit = x < r.it + r.n && nuc_clq_entry(ev, r, x);
+            const unsigned long long hits = __ballot(hit);
+            if (kFill && hit) nuc_clq_write(ev, o, tri_ptr, rt, x, base + run + (uint32_t)__popcll(hits & nuc_below(lane)), clq, key0, ctl);
+            run += (uint32_t)__popcll(hits);
+        }
+        if (lane == src) mine = run;
+    }
+    if (kFill) {
+        if (mine) atomicAdd(key0 + t, mine);
+    } else {
+        if (t <= n_tri) qcnt[t] = t < n_tri ? mine : 0u;
+        unsigned long long sum = mine;
+        for (int off = kWave / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        if (lane == 0 && sum) atomicAdd(&ctl->n_clq, sum);
+    }
+}
+
+// the incidence lists: clique q into the list of each of its four triangles (cur zeroed before; the order inside a list is
+// whatever the atomics give -- nothing reads it as an order)
+__global__ void k_nuc_inc(const uint4 *__restrict__ clq, uint32_t n_clq, const uint32_t *__restrict__ inc_ptr, uint32_t *cur, uint32_t *__restrict__ inc)
+{
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= n_clq) return;
+    const uint4 r = clq[q];
+    inc[inc_ptr[r.x] + atomicAdd(cur + r.x, 1u)] = q;
+    inc[inc_ptr[r.y] + atomicAdd(cur + r.y, 1u)] = q;
+    inc[inc_ptr[r.z] + atomicAdd(cur + r.z, 1u)] = q;
+    inc[inc_ptr[r.w] + atomicAdd(cur + r.w, 1u)] = q;
+}
+
+// ---- the peel
+
+__global__ void k_nuc_level_begin(NucCtl *ctl)
+{
+    ctl->kmin = 0x7FFFFFFF; ctl->n_q[0] = 0u; ctl->n_q[1] = 0u;
+}
+
+// kmin = the smallest key of a live triangle
+__global__ void k_nuc_min(uint32_t n_tri, const int32_t *__restrict__ theta, const int32_t *__restrict__ key, NucCtl *ctl)
+{
+    int32_t lo = 0x7FFFFFFF;
+    for (uint32_t t = blockIdx.x * kBlock + threadIdx.x; t < n_tri; t += gridDim.x * kBlock)
+        if (theta[t] < 0) { const int32_t k = key[t]; lo = k < lo ? k : lo; }
+    for (int off = kWave / 2; off > 0; off >>= 1) { const int32_t other = __shfl_xor(lo, off); lo = other < lo ? other : lo; }
+    if ((threadIdx.x & (kWave - 1)) == 0 && lo != 0x7FFFFFFF) atomicMin(&ctl->kmin, lo);
+}
+
+// the first frontier of level kmin: every live triangle whose key is not above it, one append per wave
+__global__ void k_nuc_collect(uint32_t n_tri, const int32_t *__restrict__ theta, const int32_t *__restrict__ key, NucCtl *ctl, uint32_t *__restrict__ queue)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int32_t k = ctl->kmin;
+    for (uint32_t base = blockIdx.x * kBlock; base < n_tri; base += gridDim.x * kBlock) {   // (uniform per workgroup)
+        const uint32_t t = base + threadIdx.x;
+        const bool in = t < n_tri && theta[t] < 0 && key[t] <= k;
+        const unsigned long long b = __ballot(in);
+        if (!b) continue;
+        uint32_t slot = 0;
+        if (lane == __ffsll((long long)b) - 1) slot = atomicAdd(&ctl->n_q[0], (uint32_t)__popcll(b));
+        slot = (uint32_t)__shfl((int32_t)slot, __ffsll((long long)b) - 1) + (uint32_t)__popcll(b & nuc_below(lane));
+        if (in && slot < n_tri) queue[slot] = t;
+    }
+}
+
+// the frontier's stamp, in a launch of its own: theta = k, no longer alive.  It also empties the queue the walk appends to.
+__global__ void k_nuc_stamp(NucCtl *ctl, int sel, const uint32_t *__restrict__ queue, uint32_t n_tri, int32_t *__restrict__ theta)
+{
+    uint32_t n = ctl->n_q[sel];
+    if (n > n_tri) n = n_tri;
+    const int32_t k = ctl->kmin;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) theta[queue[i]] = k;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->n_q[sel ^ 1] = 0u;
+}
+
+// clique q seen from frontier triangle t: the first visitor retires it
+__device__ __forceinline__ void nuc_retire(uint32_t q, uint32_t t, int32_t k, const uint4 *__restrict__ clq, uint32_t *dead,
+                                           const int32_t *__restrict__ theta, int32_t *key, NucCtl *ctl, int nsel, uint32_t *__restrict__ next, uint32_t cap)
+{
+    if (atomicExch(dead + q, 1u) != 0u) return;
+    const uint4 r = clq[q];
+    const uint32_t u[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (u[i] == t || theta[u[i]] >= 0) continue;     // (stamped by an earlier launch: this frontier or an earlier one)
+        if (atomicSub(key + u[i], 1) - 1 == k) {
+            const uint32_t slot = atomicAdd(&ctl->n_q[nsel], 1u);
+            if (slot < cap) next[slot] = u[i];
+        }
+    }
+}
+
+// the walk of a sub-round: one lane per frontier triangle; an incidence list above n_short goes through the wave
+__global__ void k_nuc_walk(NucCtl *ctl, int sel, const uint32_t *__restrict__ queue, uint32_t *__restrict__ next, uint32_t n_tri,
+                           const uint32_t *__restrict__ inc_ptr, const uint32_t *__restrict__ inc, const uint4 *__restrict__ clq, uint32_t *dead,
+                           const int32_t *__restrict__ theta, int32_t *key, uint32_t n_short)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t n = ctl->n_q[sel];
+    if (n > n_tri) n = n_tri;
+    const int32_t k = ctl->kmin;
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {        // (uniform per workgroup)
+        const uint32_t i = base + threadIdx.x;
+        uint32_t t = 0, lo = 0, hi = 0;
+        if (i < n) { t = queue[i]; lo = inc_ptr[t]; hi = inc_ptr[t + 1]; }
+        const bool mid = hi - lo > n_short;
+        if (!mid)
+            for (uint32_t x = lo; x < hi; ++x) nuc_retire(inc[x], t, k, clq, dead, theta, key, ctl, sel ^ 1, next, n_tri);
+        unsigned long long todo = __ballot(mid);
+        while (todo) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const uint32_t rt = (uint32_t)__shfl((int32_t)t, src), rlo = (uint32_t)__shfl((int32_t)lo, src), rhi = (uint32_t)__shfl((int32_t)hi, src);
+            for (uint32_t x = rlo + (uint32_t)lane; x < rhi; x += kWave) nuc_retire(inc[x], rt, k, clq, dead, theta, key, ctl, sel ^ 1, next, n_tri);
+        }
+    }
+}
+
+// ---- outputs
+
+__device__ __forceinline__ void nuc_max(int32_t *p, int32_t x)
+{
+    if (x > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, x);
+}
+
+__global__ void k_nuc_out(uint32_t n_tri, NucTri o, const int32_t *__restrict__ theta, int32_t *edge_theta, int32_t *vertex_theta)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_tri) return;
+    const int32_t th = theta[t];
+    nuc_max(edge_theta + o.j[t], th); nuc_max(edge_theta + o.pac[t], th); nuc_max(edge_theta + o.pbc[t], th);
+    nuc_max(vertex_theta + o.a[t], th); nuc_max(vertex_theta + o.b[t], th); nuc_max(vertex_theta + o.c[t], th);
+}
+
+inline uint32_t nuc_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
+{
+    const char *e = ctx_opt(ctx, name);
+    if (!e) return dflt;
+    const unsigned long v = strtoul(e, nullptr, 10);
+    return v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
+}
+
+struct NucBlocks {                          // the arrays of one result: pool blocks
+    int32_t *a = nullptr, *b = nullptr, *c = nullptr, *key0 = nullptr, *theta = nullptr, *edge = nullptr, *vertex = nullptr;
+};
+
+void nuc_put(komb_ctx *ctx, NucBlocks &b)
+{
+    ctx->pool.put(b.a); ctx->pool.put(b.b); ctx->pool.put(b.c); ctx->pool.put(b.key0); ctx->pool.put(b.theta);
+    ctx->pool.put(b.edge); ctx->pool.put(b.vertex);
+    b = NucBlocks{};
+}
+
+} // namespace
+
+void nucleus_drop(komb_ctx *ctx)
+{
+    NucBlocks b{ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_nuc_key0, ctx->d_nuc_theta, ctx->d_nuc_edge, ctx->d_nuc_vertex};
+    nuc_put(ctx, b);
+    ctx->d_nuc_a = ctx->d_nuc_b = ctx->d_nuc_c = ctx->d_nuc_key0 = ctx->d_nuc_theta = ctx->d_nuc_edge = ctx->d_nuc_vertex = nullptr;
+    ctx->nuc_done = false;
+}
+
+// the k-truss result it needs is checked by the caller (api.cpp).  The result is built in blocks of its own and replaces the
+// previous one only when the run has succeeded.
+int nucleus_run(komb_ctx *ctx)
+{
+    hipStream_t s = ctx->stream;
+    const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv > 0 ? ctx->nv : 0;
+    if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
+    Range r_all("komb_nucleus_run");
+    struct Fresh { komb_ctx *c; NucBlocks b; ~Fresh() { nuc_put(c, b); } } fresh{ctx};   // goes back to the pool unless it is installed
+    komb_ctx::Nucleus res;
+    const uint32_t n_short = nuc_opt_u32(ctx, "NUC_SHORT", kNucShort);       // (tests: every unit through the wave / the queued path)
+    uint32_t n_heavy = nuc_opt_u32(ctx, "NUC_HEAVY", kNucHeavy);
+    if (n_heavy <= n_short) n_heavy = n_short + 1;
+    int64_t cap = kNucMaxClq;                                                // NUC_CAP (tests): a smaller clique limit
+    if (const char *e = ctx_opt(ctx, "NUC_CAP")) { const long long v = strtoll(e, nullptr, 10); if (v >= 0 && v < cap) cap = v; }
+
+    const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev;
+    const uint32_t um = (uint32_t)m;
+    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.edge, (size_t)m * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.vertex, (size_t)nv * sizeof(int32_t)));
+    DevBufs bufs(ctx);
+    EventSet evs;
+    hipEvent_t e_t0 = nullptr, e_t1 = nullptr, e_q0 = nullptr, e_q1 = nullptr, e_p1 = nullptr;
+    KOMB_HIP(ctx, evs.make(&e_t0)); KOMB_HIP(ctx, evs.make(&e_t1));
+    KOMB_HIP(ctx, evs.make(&e_q0)); KOMB_HIP(ctx, evs.make(&e_q1)); KOMB_HIP(ctx, evs.make(&e_p1));
+    NucCtl *d_ctl = nullptr;
+    KOMB_HIP(ctx, bufs.alloc(&d_ctl, 1));
+    NucCtl h;
+    int64_t T = 0, Q = 0;
+    bool timed_clq = false;
+
+    ctx->timer.start(s);
+    KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(NucCtl), s));
+    if (m > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.b.edge, 0xFF, (size_t)m * sizeof(int32_t), s));
+    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.b.vertex, 0xFF, (size_t)nv * sizeof(int32_t), s));
+    (void)hipEventRecord(e_t0, s);
+    if (m > 0) {
+        // ---- triangles
+        uint32_t *d_rs = nullptr, *d_re = nullptr, *d_cnt = nullptr, *d_heavy = nullptr, *d_part = nullptr;
+        KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
+        KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
+        KOMB_HIP(ctx, bufs.alloc(&d_cnt, (size_t)m + 1));        // counts, then tri_ptr
+        KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
+        KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
+        const NucTri none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        k_nuc_rows<<<nuc_grid(m), kBlock, 0, s>>>(eu, um, d_rs, d_re);
+        k_nuc_tri<false><<<nuc_grid(m + 1), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, d_cnt, nullptr, d_ctl, n_short, n_heavy, none);
+        KOMB_HIP(ctx, hipGetLastError());
+        KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));
+        const uint32_t n_queued = h.n_heavy < um ? h.n_heavy : um;
+        const dim3 hgrid(n_queued < (uint32_t)kNucHeavyGrid ? (n_queued ? n_queued : 1u) : (uint32_t)kNucHeavyGrid, kNucHeavyChunks);
+        if (n_queued) {
+            KOMB_HIP(ctx, bufs.alloc(&d_heavy, (size_t)n_queued));          // (sized from the count, as the clique storage is)
+            KOMB_HIP(ctx, bufs.alloc(&d_part, (size_t)n_queued * kNucHeavyChunks));
+            k_nuc_queue<<<nuc_grid(m), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, n_heavy, d_ctl, d_heavy, n_queued);
+            k_nuc_tri_heavy<false><<<hgrid, kBlock, 0, s>>>(eu, ev, d_rs, d_re, d_cnt, nullptr, d_ctl, d_heavy, n_queued, d_part, none);
+            KOMB_HIP(ctx, hipGetLastError());
+            KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));
+        }
+        if (h.n_tri > (unsigned long long)kNucMaxTri)
+            KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_nucleus_run: %llu triangles; triangle ids are limited to 2^31 - 1", h.n_tri);
+        T = (int64_t)h.n_tri;
+        const uint32_t uT = (uint32_t)T;
+        if (T > 0) {
+            uint32_t *tri_ptr = d_cnt;
+            KOMB_TRY(prim_exclusive_sum_u32(ctx, d_cnt, tri_ptr, m + 1));
+            NucTri o;
+            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.a, (size_t)T * sizeof(int32_t)));
+            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.b, (size_t)T * sizeof(int32_t)));
+            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.c, (size_t)T * sizeof(int32_t)));
+            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.key0, ((size_t)T + 1) * sizeof(int32_t)));   // (+ 1: the scan's last entry)
+            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.theta, (size_t)T * sizeof(int32_t)));
+            o.a = fresh.b.a; o.b = fresh.b.b; o.c = fresh.b.c;
+            KOMB_HIP(ctx, bufs.alloc(&o.j, (size_t)T));
+            KOMB_HIP(ctx, bufs.alloc(&o.pac, (size_t)T));
+            KOMB_HIP(ctx, bufs.alloc(&o.pbc, (size_t)T));
+            k_nuc_tri<true><<<nuc_grid(m), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, nullptr, tri_ptr, d_ctl, n_short, n_heavy, o);
+            if (n_queued) k_nuc_tri_heavy<true><<<hgrid, kBlock, 0, s>>>(eu, ev, d_rs, d_re, nullptr, tri_ptr, d_ctl, d_heavy, n_queued, d_part, o);
+            KOMB_HIP(ctx, hipGetLastError());
+            (void)hipEventRecord(e_t1, s);
+
+            // ---- 4-cliques: count, reserve, fill, incidence lists
+            uint32_t *d_qcnt = nullptr, *d_inc_ptr = nullptr, *d_cur = nullptr, *d_inc = nullptr, *d_dead = nullptr, *d_queue = nullptr;
+            int32_t *d_key = nullptr;
+            uint4 *d_clq = nullptr;
+            uint32_t *key0 = (uint32_t *)fresh.b.key0;
+            KOMB_HIP(ctx, bufs.alloc(&d_qcnt, (size_t)T + 1));   // counts, then q_ptr
+            (void)hipEventRecord(e_q0, s);
+            k_nuc_clq<false><<<nuc_grid(T + 1), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, d_qcnt, nullptr, nullptr, nullptr, d_ctl, n_short);
+            KOMB_HIP(ctx, hipGetLastError());
+            KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));
+            if (h.n_clq > (unsigned long long)cap)
+                KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_nucleus_run: %llu 4-cliques on %lld triangles; the limit is %lld (clique ids are 32-bit, four incidences each)",
+                          h.n_clq, (long long)T, (long long)cap);
+            Q = (int64_t)h.n_clq;
+            const uint32_t uQ = (uint32_t)Q;
+            KOMB_TRY(prim_exclusive_sum_u32(ctx, d_qcnt, d_qcnt, T + 1));
+            KOMB_HIP(ctx, bufs.alloc(&d_clq, (size_t)Q));
+            KOMB_HIP(ctx, bufs.alloc(&d_inc_ptr, (size_t)T + 1));
+            KOMB_HIP(ctx, bufs.alloc(&d_cur, (size_t)T));
+            KOMB_HIP(ctx, bufs.alloc(&d_inc, 4 * (size_t)Q));
+            KOMB_HIP(ctx, bufs.alloc(&d_dead, (size_t)Q));
+            KOMB_HIP(ctx, bufs.alloc(&d_key, (size_t)T));
+            KOMB_HIP(ctx, bufs.alloc(&d_queue, 2 * (size_t)T));
+            KOMB_HIP(ctx, hipMemsetAsync(key0, 0, ((size_t)T + 1) * sizeof(uint32_t), s));
+            KOMB_HIP(ctx, hipMemsetAsync(d_cur, 0, (size_t)T * sizeof(uint32_t), s));
+            if (Q > 0) {
+                KOMB_HIP(ctx, hipMemsetAsync(d_dead, 0, (size_t)Q * sizeof(uint32_t), s));
+                k_nuc_clq<true><<<nuc_grid(T), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, nullptr, d_qcnt, d_clq, key0, d_ctl, n_short);
+            }
+            KOMB_TRY(prim_exclusive_sum_u32(ctx, key0, d_inc_ptr, T + 1));
+            if (Q > 0) k_nuc_inc<<<nuc_grid(Q), kBlock, 0, s>>>(d_clq, uQ, d_inc_ptr, d_cur, d_inc);
+            KOMB_HIP(ctx, hipGetLastError());
+            (void)hipEventRecord(e_q1, s);
+            timed_clq = true;
+
+            // ---- the peel
+            KOMB_HIP(ctx, hipMemcpyAsync(d_key, key0, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            KOMB_HIP(ctx, hipMemsetAsync(fresh.b.theta, 0xFF, (size_t)T * sizeof(int32_t), s));
+            uint32_t *queue[2] = {d_queue, d_queue + T};
+            const int sweep = nuc_sweep(T);
+            int64_t remaining = T;
+            while (remaining > 0) {
+                k_nuc_level_begin<<<1, 1, 0, s>>>(d_ctl);
+                k_nuc_min<<<sweep, kBlock, 0, s>>>(uT, fresh.b.theta, d_key, d_ctl);
+                k_nuc_collect<<<sweep, kBlock, 0, s>>>(uT, fresh.b.theta, d_key, d_ctl, queue[0]);
+                int sel = 0, grid = sweep;                       // (the first frontier's length is on the device only)
+                bool first = true;
+                for (;;) {
+                    k_nuc_stamp<<<grid, kBlock, 0, s>>>(d_ctl, sel, queue[sel], uT, fresh.b.theta);
+                    k_nuc_walk<<<grid, kBlock, 0, s>>>(d_ctl, sel, queue[sel], queue[sel ^ 1], uT, d_inc_ptr, d_inc, d_clq, d_dead, fresh.b.theta, d_key, n_short);
+                    KOMB_HIP(ctx, hipGetLastError());
+                    KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));      // the one host read of the sub-round
+                    const int64_t done = h.n_q[sel], next = h.n_q[sel ^ 1];
+                    if (h.bad || done < 1 || done + next > remaining)
+                        KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_nucleus_run: the peel is inconsistent at level %d (frontier %lld, next %lld, left %lld, bad %u)",
+                                  h.kmin, (long long)done, (long long)next, (long long)remaining, h.bad);
+                    remaining -= done;
+                    ++res.n_subrounds;
+                    if (first) { ++res.n_levels; res.theta_max = h.kmin; first = false; }
+                    if (next == 0) break;
+                    sel ^= 1;
+                    grid = nuc_sweep(next);
+                }
+            }
+            (void)hipEventRecord(e_p1, s);
+            k_nuc_out<<<nuc_grid(T), kBlock, 0, s>>>(uT, o, fresh.b.theta, fresh.b.edge, fresh.b.vertex);
+            KOMB_HIP(ctx, hipGetLastError());
+        }
+    }
+    res.ms = ctx->timer.stop(s);
+    KOMB_HIP(ctx, hipGetLastError());
+    res.n_tri = T; res.n_clq = Q;
+    if (T == 0) res.theta_max = -1;
+    if (timed_clq) {
+        float f = 0.f;
+        if (hipEventElapsedTime(&f, e_t0, e_t1) == hipSuccess) res.ms_tri = (double)f;
+        if (hipEventElapsedTime(&f, e_q0, e_q1) == hipSuccess) res.ms_clq = (double)f;
+        if (hipEventElapsedTime(&f, e_q1, e_p1) == hipSuccess) res.ms_peel = (double)f;
+    }
+    if (ctx_flag(ctx, "NUC_DEBUG"))
+        fprintf(stderr, "komb nucleus: %lld edges, %lld triangles, %lld cliques, theta_max %d, %d levels, %lld sub-rounds, run %.3f ms, "
+                "triangle pass %.3f ms, clique pass %.3f ms, peel %.3f ms\n", (long long)m, (long long)T, (long long)Q, res.theta_max,
+                res.n_levels, (long long)res.n_subrounds, res.ms, res.ms_tri, res.ms_clq, res.ms_peel);
+    nucleus_drop(ctx);
+    ctx->d_nuc_a = fresh.b.a; ctx->d_nuc_b = fresh.b.b; ctx->d_nuc_c = fresh.b.c; ctx->d_nuc_key0 = fresh.b.key0;
+    ctx->d_nuc_theta = fresh.b.theta; ctx->d_nuc_edge = fresh.b.edge; ctx->d_nuc_vertex = fresh.b.vertex;
+    fresh.b = NucBlocks{};
+    ctx->nuc = res;
+    ctx->nuc_done = true;
+    return KOMB_OK;
+}
+
+} // namespace komb

@@ -63,6 +63,13 @@
 //                       cores, or - for a hub / an outlier; ClusterSize its number of unitigs (0 then);
 //                       SimilarNeighbours the unitig's number of similar edges.  VIDs depend on -t, so only the
 //                       partition by Name compares between runs.  Nothing else changes.
+//   KOMB_NUCLEUS=1      with KOMB_TRUSS=1: also write, after the truss stage, the (3,4)-nucleus decomposition of its result
+//                       (komb_nucleus_run: triangles peeled by the 4-cliques they lie in).  nucleus_triangles.tsv:
+//                       #Name_A, Name_B, Name_C, Cliques, Theta -- one row per triangle in triangle order (ascending VIDs),
+//                       Cliques the 4-cliques it lies in, Theta its nucleus number.  nucleus_unitigs.tsv: #VID, Name, Theta
+//                       -- the unitigs of the result in VID order with the largest Theta among their triangles (-1 without
+//                       one).  0 is off; any other value than 0 or 1 is a usage error.  VIDs depend on -t, so only the tables
+//                       by Name compare between runs.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -738,6 +745,53 @@ void write_communities(komb_ctx *ctx, const std::string &outdir, const Names &na
     fclose(fp);
 }
 
+// KOMB_NUCLEUS: komb_nucleus_run on the truss stage's result as two tables (triangles in triangle order, the result's unitigs in VID order)
+void write_nucleus(komb_ctx *ctx, const std::string &outdir, const Names &names, int64_t nv, int threads,
+                   const std::vector<int32_t> &eu, const std::vector<int32_t> &ev)
+{
+    int rc = komb_nucleus_run(ctx);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_run", rc);
+    int64_t n = 0;
+    rc = komb_nucleus_count(ctx, &n);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_count", rc);
+    std::vector<int32_t> a((size_t)n), b((size_t)n), c((size_t)n), key0((size_t)n), theta((size_t)n), vtheta((size_t)nv);
+    rc = komb_nucleus_fetch(ctx, a.data(), b.data(), c.data(), key0.data(), theta.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_fetch", rc);
+    rc = komb_nucleus_fetch_vertices(ctx, vtheta.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_fetch_vertices", rc);
+    std::string path = outdir + "/nucleus_triangles.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Name_A\tName_B\tName_C\tCliques\tTheta\n");
+    write_rows(fp, n, threads, [&](int64_t i, std::string &buf) {
+        buf.append(names.name[(size_t)a[(size_t)i]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)b[(size_t)i]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)c[(size_t)i]]);
+        char tmp[48];
+        const int len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)key0[(size_t)i], (int)theta[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    std::vector<uint8_t> in((size_t)nv, 0);                // the vertices of the result: the ends of its edges
+    for (size_t e = 0; e < eu.size(); ++e) { in[(size_t)eu[e]] = 1; in[(size_t)ev[e]] = 1; }
+    path = outdir + "/nucleus_unitigs.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tTheta\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (!in[(size_t)i]) return;
+        char tmp[48];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\n", (int)vtheta[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_COMMUNITY_HIERARCHY: komb_community_hierarchy_run as two tables (nodes in node order, member edges in canonical order)
 void write_community_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads,
                                const std::vector<int32_t> &eu, const std::vector<int32_t> &ev, const std::vector<int32_t> &tr)
@@ -1082,6 +1136,14 @@ int main(int argc, const char **argv)
         }
     }
 
+    // (3,4)-nucleus decomposition of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
+    const char *nuc_env = getenv("KOMB_NUCLEUS");
+    const bool nuc_on = nuc_env && !strcmp(nuc_env, "1");
+    if (nuc_env && *nuc_env && !nuc_on && strcmp(nuc_env, "0") != 0) {
+        fprintf(stderr, "komb2: KOMB_NUCLEUS=%s: expected 0 or 1\n", nuc_env);
+        leave(EXIT_FAILURE);
+    }
+
     // structural clustering of the whole graph (no counterpart in the reference; opt-in): KOMB_STRUCTURAL=<num>/<den>,<mu>.  It
     // makes a whole-graph k-truss run of its own, before the truss stage below replaces that result with the max core's.
     const char *sc_env = getenv("KOMB_STRUCTURAL");
@@ -1142,6 +1204,7 @@ int main(int argc, const char **argv)
         }
         if (env_on("KOMB_COMMUNITY_HIERARCHY"))            // the forest of the communities of the truss stage's result
             write_community_hierarchy(ctx, args.outdir, names, args.threads, eu, ev, tr);
+        if (nuc_on) write_nucleus(ctx, args.outdir, names, nv, args.threads, eu, ev);
         if (hier_on) {                                     // the forest of the truss stage's result
             std::vector<int32_t> lvl((size_t)nv, 0);
             for (int64_t e = 0; e < ne_sub; ++e) {
