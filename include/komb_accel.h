@@ -446,6 +446,58 @@ int komb_nucleus_fetch_vertices(komb_ctx *ctx, int32_t *vertex_theta); /* [nv] *
 int komb_nucleus_info(komb_ctx *ctx, int64_t *n_triangles, int64_t *n_cliques4, int32_t *theta_max,
                       int32_t *n_levels, int64_t *n_subrounds, double *ms);   /* any may be NULL */
 
+/* ---- (3,4)-nucleus hierarchy: the nuclei as connected classes and their forest ---- */
+/* theta has no connectivity condition: two K_5 that share only an edge carry theta = 2 on all twenty triangles.  The k-nuclei
+ * of the paper above are CONNECTED, and their nesting over all k is its forest of dense subgraphs.
+ * Input: the stored result of the last komb_nucleus_run on the current k-truss result -- the triangles, numbered in ascending
+ * (a, b, c) order, with theta per triangle, and the 4-cliques of that result.
+ * For k >= 1, T_k is the set of triangles with theta >= k.  A 4-clique has WEIGHT w = the smallest theta of its four
+ * triangles; every 4-clique has w >= 1.  Two triangles of T_k are k-LINKED when they lie in a common 4-clique of weight >= k.
+ * The k-NUCLEI N_k are the classes of the transitive closure of k-linking on T_k.  A triangle with theta = 0 lies in no clique
+ * and is in no nucleus.
+ * A NODE is a pair (k, S): S is in N_k and not in N_(k+1).  rep = the smallest triangle id in S.  Nodes are numbered
+ * 0 .. n_nodes-1 in ascending (k, rep) order.  parent = the node of the nearest lower level whose set contains S, -1 when
+ * there is none; parent[i] < i always.  size[i] = the triangles in S; shell[i] = the triangles in S with theta exactly k;
+ * size[i] == shell[i] + the sizes of i's children.  node[t] = the node at level theta(t) that contains t, -1 when
+ * theta(t) = 0.  Everything is determined by the input: no output depends on the run, on an option or on scheduling.
+ * The walk-up rule: from node[t], moving to the parent while the parent's level is still >= k ends at the node whose set is
+ * t's k-nucleus.
+ * komb_nucleus_hierarchy_count: the nodes.  komb_nucleus_hierarchy_fetch_nodes: k, rep, parent, size, shell.
+ * komb_nucleus_hierarchy_fetch_triangles: node[n_triangles].
+ * komb_nucleus_hierarchy_labels runs the walk-up rule on the device, one walk per triangle over the stored forest:
+ * label[t] = the rep of t's k-nucleus, -1 when theta(t) < k; size[t] = that nucleus's triangles, 0 when theta(t) < k.
+ * KOMB_NUCLEUS_K_MAX resolves to the largest theta of the result; after that, k <= 1 runs as 1 (so a result without a
+ * member gives -1 / 0 everywhere); k above the largest theta gives -1 / 0 everywhere; k < -1: KOMB_ERR_ARG.  Either output may
+ * be NULL.
+ * komb_nucleus_hierarchy_nuclei lists the k-nuclei as subgraphs, in ascending rep order: rep, the triangles, the distinct
+ * canonical edges and the distinct vertices of each (the density edges / C(vertices, 2) is the caller's to form).  k
+ * resolves as for _labels.  *n_nuclei is the number of k-nuclei; with all four arrays NULL the call only counts.  With an
+ * array given, cap < the number of k-nuclei is KOMB_ERR_ARG and nothing is written.
+ * komb_nucleus_hierarchy_info: nodes, nodes without a parent, the largest theta of the nucleus result (-1 without a
+ * triangle), depth = the most nodes on a path from a root down (0 without nodes), the triangles with theta >= 1, and ms --
+ * the device time of komb_nucleus_hierarchy_run on the context's HIP-event timer.  Any pointer may be NULL.
+ * No context or no graph loaded: KOMB_ERR_ARG.  komb_nucleus_hierarchy_run without a nucleus decomposition of the current
+ * k-truss result, every other call without a hierarchy of the current decomposition: KOMB_ERR_STATE.  A result without a
+ * 4-clique has no nodes; not an error.  A pool failure: KOMB_ERR_NOMEM.  The run enumerates the 4-cliques once more (the
+ * decomposition keeps none) into exactly n_cliques4 records; a different count is KOMB_ERR_DEVICE and installs nothing.
+ * The result lives in blocks of its own (5 n_nodes + n_triangles words), installed when a run has succeeded.  It indexes one
+ * nucleus result: whatever replaces or drops that -- a new komb_nucleus_run, a new k-truss run of any kind,
+ * komb_truss_unprepare, a graph load -- drops it too, so a refused or failed run leaves the previous hierarchy readable
+ * exactly as long as the decomposition it indexes is the current one.  No other call changes or drops it; a run changes no
+ * other result, no komb_stats field and not the resident k-truss preparation.  Option NUC_SHORT moves the length at which
+ * a triangle's walked tail goes from its lane to its wave here as in komb_nucleus_run; it changes no result. */
+#define KOMB_NUCLEUS_K_MAX (-1)   /* k = the largest theta of the nucleus result */
+int komb_nucleus_hierarchy_run(komb_ctx *ctx);
+int komb_nucleus_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes);                       /* n_nodes may be NULL */
+int komb_nucleus_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent,
+                                       int32_t *size, int32_t *shell);         /* [n_nodes] each, any may be NULL */
+int komb_nucleus_hierarchy_fetch_triangles(komb_ctx *ctx, int32_t *node /*[n_triangles]*/);
+int komb_nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label /*[n_triangles]*/, int32_t *size /*[n_triangles]*/);
+int komb_nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_nuclei, int32_t *rep,
+                                  int32_t *n_triangles, int32_t *n_edges, int32_t *n_vertices);   /* [cap] each, any may be NULL */
+int komb_nucleus_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *theta_max, int32_t *depth,
+                                int64_t *n_member_triangles, double *ms);      /* any may be NULL */
+
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness
  * (src/graph.cpp:502, src/graph.cpp:508).  vmask (host, nv bytes, nullable)

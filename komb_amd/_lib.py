@@ -121,6 +121,14 @@ SIGNATURES = {
     "komb_nucleus_fetch_vertices": (_i32, [_vp, _vp]),
     "komb_nucleus_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32),
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_nucleus_hierarchy_run": (_i32, [_vp]),
+    "komb_nucleus_hierarchy_count": (_i32, [_vp, ctypes.POINTER(_i64)]),
+    "komb_nucleus_hierarchy_fetch_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "komb_nucleus_hierarchy_fetch_triangles": (_i32, [_vp, _vp]),
+    "komb_nucleus_hierarchy_labels": (_i32, [_vp, ctypes.c_int32, _vp, _vp]),
+    "komb_nucleus_hierarchy_nuclei": (_i32, [_vp, ctypes.c_int32, _i64, ctypes.POINTER(_i64), _vp, _vp, _vp, _vp]),
+    "komb_nucleus_hierarchy_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

@@ -511,6 +511,69 @@ class KombAccel:
         self.nucleus_run()
         return self.nucleus_fetch(), self.nucleus_fetch_edges(), self.nucleus_fetch_vertices()
 
+    # ---- (3,4)-nucleus hierarchy: the k-nuclei as connected classes and their nesting forest over all k (include/komb_accel.h)
+    NUCLEI_FIELDS = ("rep", "n_triangles", "n_edges", "n_vertices")
+
+    def nucleus_hierarchy_run(self):
+        """Needs a nucleus decomposition (nucleus_run) of the current k-truss result."""
+        self._sync_env_options()
+        self._check(self._lib.komb_nucleus_hierarchy_run(self._ctx))
+
+    def nucleus_hierarchy_fetch_nodes(self):
+        """{"k", "rep", "parent", "size", "shell"}: int32[n_nodes] each, nodes in ascending (k, rep) order; rep is a
+        triangle id, size and shell count triangles."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_nucleus_hierarchy_count(self._ctx, ctypes.byref(n)))
+        out = {name: _out_i32(max(n.value, 0)) for name in self.HIER_FIELDS}
+        self._check(self._lib.komb_nucleus_hierarchy_fetch_nodes(self._ctx, *(ptr(out[name]) for name in self.HIER_FIELDS)))
+        return out
+
+    def _nucleus_hierarchy_triangles(self):
+        """n_triangles of the nucleus result the stored forest indexes (the forest's own errors first: no graph, no run)."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_nucleus_hierarchy_count(self._ctx, None))
+        self._check(self._lib.komb_nucleus_count(self._ctx, ctypes.byref(n)))
+        return max(n.value, 0)
+
+    def nucleus_hierarchy_fetch_triangles(self):
+        """node int32[n_triangles]: the node of every triangle of the nucleus result, -1 for a triangle with theta 0."""
+        node = _out_i32(self._nucleus_hierarchy_triangles())
+        self._check(self._lib.komb_nucleus_hierarchy_fetch_triangles(self._ctx, ptr(node)))
+        return node
+
+    def nucleus_hierarchy_labels(self, k=1):
+        """(label, size) int32[n_triangles]: the rep and the triangle count of every triangle's k-nucleus, -1 / 0 where
+        theta < k; k = -1: the largest theta."""
+        n = self._nucleus_hierarchy_triangles()
+        label = _out_i32(n)
+        size = _out_i32(n)
+        self._check(self._lib.komb_nucleus_hierarchy_labels(self._ctx, k, ptr(label), ptr(size)))
+        return label, size
+
+    def nucleus_hierarchy_nuclei(self, k=1):
+        """{"rep", "n_triangles", "n_edges", "n_vertices"}: int32[n_nuclei] each, the k-nuclei as subgraphs in ascending
+        rep order; k = -1: the largest theta."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_nucleus_hierarchy_nuclei(self._ctx, k, 0, ctypes.byref(n), None, None, None, None))
+        out = {name: _out_i32(max(n.value, 0)) for name in self.NUCLEI_FIELDS}
+        self._check(self._lib.komb_nucleus_hierarchy_nuclei(self._ctx, k, n.value, ctypes.byref(n),
+                                                            *(ptr(out[name]) for name in self.NUCLEI_FIELDS)))
+        return out
+
+    def nucleus_hierarchy_info(self):
+        """{"n_nodes", "n_roots", "theta_max", "depth", "n_member_triangles", "ms"} of the last komb_nucleus_hierarchy_run."""
+        tmax, depth = ctypes.c_int32(), ctypes.c_int32()
+        n, roots, mem, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        self._check(self._lib.komb_nucleus_hierarchy_info(self._ctx, ctypes.byref(n), ctypes.byref(roots), ctypes.byref(tmax),
+                                                          ctypes.byref(depth), ctypes.byref(mem), ctypes.byref(ms)))
+        return {"n_nodes": n.value, "n_roots": roots.value, "theta_max": tmax.value, "depth": depth.value,
+                "n_member_triangles": mem.value, "ms": ms.value}
+
+    def run_nucleus_hierarchy(self):
+        """(nodes, node): the dict of nucleus_hierarchy_fetch_nodes and the per-triangle node array."""
+        self.nucleus_hierarchy_run()
+        return self.nucleus_hierarchy_fetch_nodes(), self.nucleus_hierarchy_fetch_triangles()
+
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):
         degree = as_c(degree, np.int32)

@@ -522,6 +522,80 @@ int komb_nucleus_info(komb_ctx *ctx, int64_t *n_triangles, int64_t *n_cliques4, 
     return KOMB_OK;
 }
 
+int komb_nucleus_hierarchy_run(komb_ctx *ctx)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_run");
+    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_run: no nucleus decomposition of the current k-truss result");
+    return nucleus_hierarchy_run(ctx);
+}
+
+int komb_nucleus_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_count");
+    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_count: no nucleus hierarchy of the current nucleus decomposition");
+    if (n_nodes) *n_nodes = ctx->nh.n_nodes;
+    return KOMB_OK;
+}
+
+int komb_nucleus_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent, int32_t *size, int32_t *shell)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_fetch_nodes");
+    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_fetch_nodes: no nucleus hierarchy of the current nucleus decomposition");
+    if (ctx->nh.n_nodes == 0) return KOMB_OK;
+    const size_t stride = (size_t)ctx->nh.cap, bytes = (size_t)ctx->nh.n_nodes * sizeof(int32_t);
+    int32_t *const out[5] = {k, rep, parent, size, shell};
+    for (int i = 0; i < 5; ++i)
+        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_nh_nodes + i * stride, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_nucleus_hierarchy_fetch_triangles(komb_ctx *ctx, int32_t *node)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_fetch_triangles");
+    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_fetch_triangles: no nucleus hierarchy of the current nucleus decomposition");
+    if (ctx->nuc.n_tri > 0 && node) KOMB_HIP(ctx, staged_copy(ctx, node, ctx->d_nh_tnode, (size_t)ctx->nuc.n_tri * sizeof(int32_t), false));
+    return KOMB_OK;
+}
+
+// k of _labels / _nuclei: KOMB_NUCLEUS_K_MAX is the largest theta, anything up to 1 runs as 1
+static int32_t nucleus_hierarchy_k(const komb_ctx *ctx, int32_t k)
+{
+    if (k == KOMB_NUCLEUS_K_MAX) k = ctx->nh.theta_max;
+    return k < 1 ? 1 : k;
+}
+
+int komb_nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_labels");
+    if (k < KOMB_NUCLEUS_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_nucleus_hierarchy_labels: bad threshold %d", k);
+    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_labels: no nucleus hierarchy of the current nucleus decomposition");
+    return nucleus_hierarchy_labels(ctx, nucleus_hierarchy_k(ctx, k), label, size);
+}
+
+int komb_nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_nuclei, int32_t *rep, int32_t *n_triangles,
+                                  int32_t *n_edges, int32_t *n_vertices)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_nuclei");
+    if (k < KOMB_NUCLEUS_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_nucleus_hierarchy_nuclei: bad threshold %d", k);
+    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_nuclei: no nucleus hierarchy of the current nucleus decomposition");
+    return nucleus_hierarchy_nuclei(ctx, nucleus_hierarchy_k(ctx, k), cap, n_nuclei, rep, n_triangles, n_edges, n_vertices);
+}
+
+int komb_nucleus_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *theta_max, int32_t *depth,
+                                int64_t *n_member_triangles, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_info");
+    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_info: no nucleus hierarchy of the current nucleus decomposition");
+    const komb_ctx::NucleusHierarchy &r = ctx->nh;
+    if (n_nodes) *n_nodes = r.n_nodes;
+    if (n_roots) *n_roots = r.n_roots;
+    if (theta_max) *theta_max = r.theta_max;
+    if (depth) *depth = r.depth;
+    if (n_member_triangles) *n_member_triangles = r.n_members;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_community_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_run");

@@ -353,6 +353,17 @@ struct komb_ctx {
     } nuc;
     bool nuc_done = false;
 
+    // ---- (3,4)-nucleus hierarchy (nucleus_hierarchy.hip): the k-nuclei as connected classes and their nesting forest over all k,
+    // in pool blocks of its own, indexed like the nucleus result it was computed from and dropped with it (nucleus_drop)
+    int32_t *d_nh_nodes = nullptr;           // [5 * nh.cap] k | rep | parent | size | shell, each a block of nh.cap words with nh.n_nodes in use
+    int32_t *d_nh_tnode = nullptr;           // [n_tri] the node of every triangle, -1 where theta == 0
+    struct NucleusHierarchy {
+        int64_t cap = 1, n_nodes = 0, n_roots = 0, n_members = 0;
+        int32_t theta_max = -1, depth = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+    } nh;
+    bool nh_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                      // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -523,6 +534,11 @@ int structural_fetch_edges(komb_ctx *ctx, int32_t *similar);  // structural.hip:
 void structural_drop(komb_ctx *ctx);                          // structural.hip: the result goes with the k-truss result it indexes
 int nucleus_run(komb_ctx *ctx);                               // nucleus.hip: the k-truss result it needs checked by the caller
 void nucleus_drop(komb_ctx *ctx);                             // nucleus.hip: the result goes with the k-truss result it indexes
+int nucleus_hierarchy_run(komb_ctx *ctx);                     // nucleus_hierarchy.hip: the nucleus result it needs checked by the caller
+int nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
+int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_nuclei, int32_t *rep, int32_t *n_triangles,
+                             int32_t *n_edges, int32_t *n_vertices);   // k checked and resolved by the caller; host outputs
+void nucleus_hierarchy_drop(komb_ctx *ctx);                   // nucleus_hierarchy.hip: the result goes with the nucleus result it indexes
 int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);

@@ -36,6 +36,7 @@
 // once, so a queue of n_triangles words cannot overflow (appends are guarded all the same); the device loops run over row
 // parts, incidence lists and queue lengths that are fixed before the launch.
 #include "common.h"
+#include "nucleus_search_dev.h"
 
 namespace komb {
 
@@ -45,7 +46,6 @@ constexpr uint32_t kNucShort = 16;          // walked side up to this long: the 
 constexpr uint32_t kNucHeavy = 2048;        // triangle pass: from this length on several workgroups of k_nuc_tri_heavy (between: the wave)
 constexpr int kNucHeavyGrid = 256, kNucHeavyChunks = 8;     // k_nuc_tri_heavy: edges side by side x parts of one side
 constexpr int kNucSweepGrid = 2048;         // sweeps over all triangles and frontiers of unknown length: workgroups, each over several tiles
-constexpr uint32_t kNucNone = 0xFFFFFFFFu;
 constexpr int64_t kNucMaxTri = 0x7FFFFFFFll, kNucMaxClq = 0x3FFFFFFFll;
 
 struct NucCtl {                             // 64 bytes, zeroed before every run
@@ -59,11 +59,6 @@ struct NucCtl {                             // 64 bytes, zeroed before every run
 };
 static_assert(sizeof(NucCtl) == 64, "NucCtl layout");
 
-struct NucTri {                             // per triangle: vertices (the result), the position of (a, b), of (a, c), of (b, c)
-    int32_t *a, *b, *c;
-    uint32_t *j, *pac, *pbc;
-};
-
 inline int nuc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 inline int nuc_sweep(int64_t n) { const int g = nuc_grid(n); return g < 1 ? 1 : (g < kNucSweepGrid ? g : kNucSweepGrid); }
 
@@ -76,19 +71,6 @@ __global__ void k_nuc_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t 
     if (j == 0 || eu[j - 1] != u) rs[u] = j;
     if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
 }
-
-// the position of x in ev[lo, end) (ascending), kNucNone if it is not there
-__device__ __forceinline__ uint32_t nuc_find(const int32_t *__restrict__ ev, int32_t x, uint32_t lo, uint32_t end)
-{
-    uint32_t hi = end;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (ev[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && ev[lo] == x ? lo : kNucNone;
-}
-
-__device__ __forceinline__ unsigned long long nuc_below(int lane) { return (1ull << lane) - 1ull; }
 
 // the two sides of edge j = (a, b): [it, it + n) is walked, [lo, hi) is searched; n <= hi - lo
 struct NucSides { uint32_t it, n, lo, hi; bool walk_a; };
@@ -227,22 +209,6 @@ __global__ void k_nuc_tri_heavy(const int32_t *__restrict__ eu, const int32_t *_
     }
 }
 
-// The three tails of triangle t = (a, b, c) a fourth vertex d > c can be in: row a behind (a, c), row b behind (b, c), all of
-// row c.  [it, it + n) is the shortest and is walked; the other two are searched.
-struct NucTails { uint32_t it, n, lo1, hi1, lo2, hi2; };
-
-__device__ __forceinline__ NucTails nuc_tails(const NucTri &o, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t t)
-{
-    const int32_t a = o.a[t], b = o.b[t], c = o.c[t];
-    const uint32_t al = o.pac[t] + 1, ah = re[a], bl = o.pbc[t] + 1, bh = re[b], cl = rs[c], ch = re[c];
-    const uint32_t na = ah - al, nb = bh - bl, nc = ch - cl;
-    NucTails s;
-    if (na <= nb && na <= nc) { s.it = al; s.n = na; s.lo1 = bl; s.hi1 = bh; s.lo2 = cl; s.hi2 = ch; }
-    else if (nb <= nc) { s.it = bl; s.n = nb; s.lo1 = al; s.hi1 = ah; s.lo2 = cl; s.hi2 = ch; }
-    else { s.it = cl; s.n = nc; s.lo1 = al; s.hi1 = ah; s.lo2 = bl; s.hi2 = bh; }
-    return s;                                            // (the walked tail is the shortest: an empty tail gives n = 0)
-}
-
 // the id of the triangle of the edge at position e whose third vertex is d: a bisection in e's ascending part of tc[]
 __device__ __forceinline__ uint32_t nuc_tri_id(const uint32_t *__restrict__ tri_ptr, const int32_t *__restrict__ tc, uint32_t e, int32_t d,
                                                uint32_t fallback, NucCtl *ctl)
@@ -257,13 +223,6 @@ __device__ __forceinline__ uint32_t nuc_tri_id(const uint32_t *__restrict__ tri_
     if (lo < end && tc[lo] == d) return lo;
     ctl->bad = 1u;                                       // (three edges of the result that close a triangle the fill did not write)
     return fallback;
-}
-
-// entry x of the walked tail: a 4-clique iff its vertex d is in the other two tails as well
-__device__ __forceinline__ bool nuc_clq_entry(const int32_t *__restrict__ ev, const NucTails &s, uint32_t x)
-{
-    const int32_t d = ev[x];
-    return nuc_find(ev, d, s.lo1, s.hi1) != kNucNone && nuc_find(ev, d, s.lo2, s.hi2) != kNucNone;
 }
 
 // record q: triangle t and the three triangles its vertices make with d = ev[x].  They hang on t's own edges (a, b), (a, c),
@@ -472,6 +431,7 @@ void nuc_put(komb_ctx *ctx, NucBlocks &b)
 
 void nucleus_drop(komb_ctx *ctx)
 {
+    nucleus_hierarchy_drop(ctx);             // (the nuclei and their forest index this result's triangles)
     NucBlocks b{ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_nuc_key0, ctx->d_nuc_theta, ctx->d_nuc_edge, ctx->d_nuc_vertex};
     nuc_put(ctx, b);
     ctx->d_nuc_a = ctx->d_nuc_b = ctx->d_nuc_c = ctx->d_nuc_key0 = ctx->d_nuc_theta = ctx->d_nuc_edge = ctx->d_nuc_vertex = nullptr;

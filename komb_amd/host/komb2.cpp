@@ -70,6 +70,17 @@
 //                       -- the unitigs of the result in VID order with the largest Theta among their triangles (-1 without
 //                       one).  0 is off; any other value than 0 or 1 is a usage error.  VIDs depend on -t, so only the tables
 //                       by Name compare between runs.  Nothing else changes.
+//   KOMB_NUCLEUS_HIERARCHY=1  with KOMB_TRUSS=1: also write, after the truss stage, the (3,4)-nuclei of its result as connected
+//                       classes and their nesting forest over all k (komb_nucleus_hierarchy_run; it runs komb_nucleus_run
+//                       itself when KOMB_NUCLEUS=1 has not).  nucleus_hierarchy.tsv: #Node, Theta, Rep_A, Rep_B, Rep_C, Parent,
+//                       Triangles, Shell, Edges, Vertices -- one row per node in node order; Rep_A, Rep_B, Rep_C are the Names
+//                       of the unitigs of the node's first triangle in triangle order, Parent a node index or -1, Triangles
+//                       the node's number of triangles, Shell those of nucleus number exactly Theta among them, Edges and
+//                       Vertices the distinct edges and unitigs of its triangles (komb_nucleus_hierarchy_nuclei, one call per
+//                       populated level).  nucleus_hierarchy_triangles.tsv: #Name_A, Name_B, Name_C, Theta, Node -- one row
+//                       per triangle of nucleus number >= 1 in triangle order with the node it belongs to at its own Theta.
+//                       0 is off; any other value than 0 or 1 is a usage error.  VIDs depend on -t, so only the forest by
+//                       Name compares between runs.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -792,6 +803,80 @@ void write_nucleus(komb_ctx *ctx, const std::string &outdir, const Names &names,
     fclose(fp);
 }
 
+// KOMB_NUCLEUS_HIERARCHY: komb_nucleus_hierarchy_run on the nucleus decomposition of the truss stage's result as two tables (nodes in
+// node order, member triangles in triangle order)
+void write_nucleus_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads, bool have_nucleus)
+{
+    int rc = have_nucleus ? KOMB_OK : komb_nucleus_run(ctx);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_run", rc);
+    rc = komb_nucleus_hierarchy_run(ctx);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_hierarchy_run", rc);
+    int64_t nt = 0, n = 0;
+    rc = komb_nucleus_count(ctx, &nt);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_count", rc);
+    rc = komb_nucleus_hierarchy_count(ctx, &n);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_hierarchy_count", rc);
+    std::vector<int32_t> a((size_t)nt), b((size_t)nt), c((size_t)nt), theta((size_t)nt), node((size_t)nt);
+    std::vector<int32_t> k((size_t)n), rep((size_t)n), parent((size_t)n), size((size_t)n), shell((size_t)n), edges((size_t)n, 0), verts((size_t)n, 0);
+    rc = komb_nucleus_fetch(ctx, a.data(), b.data(), c.data(), nullptr, theta.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_fetch", rc);
+    rc = komb_nucleus_hierarchy_fetch_nodes(ctx, k.data(), rep.data(), parent.data(), size.data(), shell.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_hierarchy_fetch_nodes", rc);
+    rc = komb_nucleus_hierarchy_fetch_triangles(ctx, node.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_hierarchy_fetch_triangles", rc);
+    // Edges and Vertices: the nodes of level K are among the K-nuclei, matched by rep (both lists ascend in rep)
+    for (int64_t lo = 0; lo < n;) {
+        int64_t hi = lo;
+        while (hi < n && k[(size_t)hi] == k[(size_t)lo]) ++hi;
+        int64_t cnt = 0;
+        rc = komb_nucleus_hierarchy_nuclei(ctx, k[(size_t)lo], 0, &cnt, nullptr, nullptr, nullptr, nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_hierarchy_nuclei", rc);
+        std::vector<int32_t> nrep((size_t)cnt), nedge((size_t)cnt), nvert((size_t)cnt);
+        rc = komb_nucleus_hierarchy_nuclei(ctx, k[(size_t)lo], cnt, &cnt, nrep.data(), nullptr, nedge.data(), nvert.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_nucleus_hierarchy_nuclei", rc);
+        for (int64_t i = lo, j = 0; i < hi; ++i) {
+            while (j < cnt && nrep[(size_t)j] < rep[(size_t)i]) ++j;
+            if (j < cnt && nrep[(size_t)j] == rep[(size_t)i]) { edges[(size_t)i] = nedge[(size_t)j]; verts[(size_t)i] = nvert[(size_t)j]; }
+        }
+        lo = hi;
+    }
+    std::string path = outdir + "/nucleus_hierarchy.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Node\tTheta\tRep_A\tRep_B\tRep_C\tParent\tTriangles\tShell\tEdges\tVertices\n");
+    write_rows(fp, n, threads, [&](int64_t i, std::string &buf) {
+        const size_t r = (size_t)rep[(size_t)i];
+        char tmp[96];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t%d\t", (int)i, (int)k[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)a[r]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)b[r]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)c[r]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\t%d\t%d\t%d\n", (int)parent[(size_t)i], (int)size[(size_t)i], (int)shell[(size_t)i],
+                       (int)edges[(size_t)i], (int)verts[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    path = outdir + "/nucleus_hierarchy_triangles.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Name_A\tName_B\tName_C\tTheta\tNode\n");
+    write_rows(fp, nt, threads, [&](int64_t i, std::string &buf) {
+        if (theta[(size_t)i] < 1) return;
+        buf.append(names.name[(size_t)a[(size_t)i]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)b[(size_t)i]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)c[(size_t)i]]);
+        char tmp[48];
+        const int len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)theta[(size_t)i], (int)node[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_COMMUNITY_HIERARCHY: komb_community_hierarchy_run as two tables (nodes in node order, member edges in canonical order)
 void write_community_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads,
                                const std::vector<int32_t> &eu, const std::vector<int32_t> &ev, const std::vector<int32_t> &tr)
@@ -1144,6 +1229,14 @@ int main(int argc, const char **argv)
         leave(EXIT_FAILURE);
     }
 
+    // the nuclei of that decomposition and their forest (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
+    const char *nh_env = getenv("KOMB_NUCLEUS_HIERARCHY");
+    const bool nh_on = nh_env && !strcmp(nh_env, "1");
+    if (nh_env && *nh_env && !nh_on && strcmp(nh_env, "0") != 0) {
+        fprintf(stderr, "komb2: KOMB_NUCLEUS_HIERARCHY=%s: expected 0 or 1\n", nh_env);
+        leave(EXIT_FAILURE);
+    }
+
     // structural clustering of the whole graph (no counterpart in the reference; opt-in): KOMB_STRUCTURAL=<num>/<den>,<mu>.  It
     // makes a whole-graph k-truss run of its own, before the truss stage below replaces that result with the max core's.
     const char *sc_env = getenv("KOMB_STRUCTURAL");
@@ -1205,6 +1298,7 @@ int main(int argc, const char **argv)
         if (env_on("KOMB_COMMUNITY_HIERARCHY"))            // the forest of the communities of the truss stage's result
             write_community_hierarchy(ctx, args.outdir, names, args.threads, eu, ev, tr);
         if (nuc_on) write_nucleus(ctx, args.outdir, names, nv, args.threads, eu, ev);
+        if (nh_on) write_nucleus_hierarchy(ctx, args.outdir, names, args.threads, nuc_on);
         if (hier_on) {                                     // the forest of the truss stage's result
             std::vector<int32_t> lvl((size_t)nv, 0);
             for (int64_t e = 0; e < ne_sub; ++e) {
