@@ -115,7 +115,8 @@ int         komb_abi_version(void);
  * longer reads: ambient environment cannot change which engine a drop-in runs).  None changes a result.  name: FINISH
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
- * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), and the
+ * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
+ * (komb_max_clique_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -497,6 +498,61 @@ int komb_nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t
                                   int32_t *n_triangles, int32_t *n_edges, int32_t *n_vertices);   /* [cap] each, any may be NULL */
 int komb_nucleus_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *theta_max, int32_t *depth,
                                 int64_t *n_member_triangles, double *ms);      /* any may be NULL */
+
+/* ---- maximum-clique search with a certified bound ------------------------- */
+/* The object every rung above relaxes: the largest set of vertices that are pairwise adjacent.  For the unitig graph, a union of
+ * per-read cliques, it is the largest set of unitigs that pairwise co-occur.
+ * Input: the last COMPLETE k-truss result on the resident graph, whole graph or vmask run alike -- its ne_sub canonical edges
+ * (eu[i], ev[i]), eu < ev, sorted by (eu, ev), original vertex ids, with their trussness t[i].  Call their graph H.  Trussness
+ * here is support + 2, so K_n has trussness n: a clique of s vertices uses only edges of trussness >= s, and omega <= t_max, the
+ * largest trussness of the result (0 without an edge).
+ * A CLIQUE is a set of >= 2 vertices, pairwise adjacent in H.  OMEGA is the size of a largest clique of H, 0 when H has no edge
+ * (singletons are not reported).  A MAXIMUM CLIQUE is a clique of omega vertices, written as its ascending id tuple.
+ * The search is a branch and bound from every canonical edge (a, b) as the two smallest ids of a clique (DESIGN.md section
+ * 4.6j).  A NODE is one candidate set taken off a search stack, a root's own included; every reported clique costs at least one.
+ * komb_max_clique_run(ctx, budget): budget caps the nodes of the whole run -- the search for omega and the enumeration of all
+ * maximum cliques.  0 means the default, 2^30; a negative value is KOMB_ERR_ARG; a value above 2^31 - 1 - KOMB_MAXCLQ_OVERSHOOT
+ * runs as that (every count then fits int32).  The wavefronts add to one counter in batches of at most 256 nodes and stop
+ * taking nodes once it has reached the budget: nodes <= budget + KOMB_MAXCLQ_OVERSHOOT always, so no launch runs unbounded.
+ * flags: KOMB_MAXCLQ_EXACT -- omega is proven; KOMB_MAXCLQ_ENUMERATED -- every maximum clique was visited (implies EXACT);
+ * KOMB_MAXCLQ_LISTED -- the sorted list is held (implies ENUMERATED).  With all three set every output is unique: nothing then
+ * depends on the run, on an option or on scheduling.  A budget that runs out in the search clears all three (unless the clique
+ * held has t_max vertices, which proves it); one that runs out in the enumeration leaves EXACT.
+ * komb_max_clique_info: omega = the size of the witness, a clique whose every pair was checked against H on the device;
+ * upper = a certified bound, omega <= the true omega <= upper <= t_max, equal to omega exactly when EXACT is set, t_max
+ * otherwise -- it uses this k-truss result only (a nucleus decomposition that happens to exist does not tighten it: the bound
+ * does not depend on call history); n_max_cliques = the number of maximum cliques with ENUMERATED, else -1; n_roots = the
+ * canonical edges whose subproblem was opened; nodes = the nodes spent; ms = the device time of the run on the context's
+ * HIP-event timer.  Any pointer may be NULL.
+ * komb_max_clique_fetch: count[v] = the maximum cliques that contain v with ENUMERATED, else 1 on the witness' vertices and 0
+ * elsewhere; witness[omega] ascending = the first clique of the list with LISTED, else whichever clique the search holds (NOT
+ * unique: it depends on scheduling).  Either may be NULL.
+ * komb_max_clique_list: all maximum cliques as ascending tuples in lexicographic order, verts[n_cliques * omega]; verts == NULL
+ * returns the count only; cap < the count with verts given is KOMB_ERR_ARG and nothing is written; without LISTED:
+ * KOMB_ERR_LIMIT.
+ * H without an edge: omega = upper = t_max = 0, no witness, every count 0, n_max_cliques = 0, flags = 7.
+ * No context or no graph loaded: KOMB_ERR_ARG, nothing is written.  Without a completed k-truss result on this graph, after
+ * komb_truss_run_slice / a sharded run that materialised only part of the canonical edges, after komb_truss_unprepare, fetch /
+ * list / info before a run: KOMB_ERR_STATE.  A root edge with more than 4096 candidates of the trussness the phase asks for:
+ * KOMB_ERR_LIMIT (a candidate set is one 64-bit word per lane of a wavefront), checked before the phase starts.  A pool failure:
+ * KOMB_ERR_NOMEM.
+ * The result lives in storage of its own, installed when a run has succeeded: a refused or failed run leaves the previous result
+ * readable.  It describes one k-truss result: whatever replaces or drops that result -- a new k-truss run of any kind,
+ * komb_truss_unprepare, a graph load -- drops it too.  No other call changes or drops it; a run changes no other result, no
+ * komb_stats field and not the resident k-truss preparation.  Options (none changes a result that carries all three flags):
+ * MAXCLQ_SEED=0 skips the greedy seed (dives from edges of the largest trussness), so the search starts from lower bound 1;
+ * MAXCLQ_LDS=<n>, 0 .. 512 (default 512): the largest candidate set whose bit matrix lives in LDS -- larger ones use the
+ * workgroup's slot of global scratch, 0 sends everything there; MAXCLQ_LIST=<n> keeps the list only up to n maximum cliques
+ * (default 65536); MAXCLQ_DEBUG=1 prints one stderr line with the counts, the nodes and the device time of each phase. */
+#define KOMB_MAXCLQ_EXACT      1
+#define KOMB_MAXCLQ_ENUMERATED 2
+#define KOMB_MAXCLQ_LISTED     4
+#define KOMB_MAXCLQ_OVERSHOOT  262144   /* 1024 wavefronts x 256 nodes */
+int komb_max_clique_run(komb_ctx *ctx, int64_t budget);
+int komb_max_clique_fetch(komb_ctx *ctx, int32_t *count /*[nv]*/, int32_t *witness /*[omega]*/);   /* either may be NULL */
+int komb_max_clique_list(komb_ctx *ctx, int64_t cap, int64_t *n_cliques, int32_t *verts /*[cap * omega]*/);
+int komb_max_clique_info(komb_ctx *ctx, int32_t *omega, int32_t *upper, int32_t *flags, int32_t *t_max, int64_t *n_max_cliques,
+                         int64_t *n_roots, int64_t *nodes, double *ms);   /* any may be NULL */
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

@@ -42,7 +42,7 @@ FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
-                "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "POISON")
+                "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -573,6 +573,47 @@ class KombAccel:
         """(nodes, node): the dict of nucleus_hierarchy_fetch_nodes and the per-triangle node array."""
         self.nucleus_hierarchy_run()
         return self.nucleus_hierarchy_fetch_nodes(), self.nucleus_hierarchy_fetch_triangles()
+
+    # ---- maximum-clique search with a certified bound on the last k-truss result (include/komb_accel.h)
+    MAX_CLIQUE_INFO_FIELDS = ("omega", "upper", "flags", "t_max", "n_max_cliques", "n_roots", "nodes", "ms")
+
+    def max_clique_run(self, budget=0):
+        """Needs a complete k-truss result on this graph.  budget: the node cap of the whole run, 0 for the default."""
+        self._sync_env_options()
+        self._check(self._lib.komb_max_clique_run(self._ctx, budget))
+
+    def max_clique_info(self):
+        """{"omega", "upper", "flags", "t_max", "n_max_cliques", "n_roots", "nodes", "ms"} of the last komb_max_clique_run."""
+        i32 = [ctypes.c_int32() for _ in range(4)]
+        i64 = [ctypes.c_int64() for _ in range(3)]
+        ms = ctypes.c_double()
+        self._check(self._lib.komb_max_clique_info(self._ctx, *(ctypes.byref(x) for x in i32 + i64), ctypes.byref(ms)))
+        return dict(zip(self.MAX_CLIQUE_INFO_FIELDS, [x.value for x in i32 + i64] + [ms.value]))
+
+    def max_clique_fetch(self):
+        """(count int32[nv], witness int32[omega]): the maximum cliques through every vertex (1 on the witness without the
+        ENUMERATED flag) and one clique of omega vertices, ascending."""
+        omega = self.max_clique_info()["omega"]
+        count = _out_i32(max(self.nv, 0))
+        witness = _out_i32(omega)
+        self._check(self._lib.komb_max_clique_fetch(self._ctx, ptr(count), ptr(witness)))
+        return count, witness
+
+    def max_clique_list(self):
+        """int32[n_max_cliques, omega]: every maximum clique as an ascending tuple, in lexicographic order (KOMB_ERR_LIMIT
+        when the list was not kept)."""
+        omega = self.max_clique_info()["omega"]
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_max_clique_list(self._ctx, 0, ctypes.byref(n), None))
+        verts = _out_i32(n.value * omega)
+        self._check(self._lib.komb_max_clique_list(self._ctx, n.value, ctypes.byref(n), ptr(verts)))
+        return verts.reshape(n.value, omega)
+
+    def run_max_clique(self, budget=0):
+        """(info, count, witness) of a maximum-clique search of the last k-truss result."""
+        self.max_clique_run(budget)
+        count, witness = self.max_clique_fetch()
+        return self.max_clique_info(), count, witness
 
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):

@@ -522,6 +522,57 @@ int komb_nucleus_info(komb_ctx *ctx, int64_t *n_triangles, int64_t *n_cliques4, 
     return KOMB_OK;
 }
 
+int komb_max_clique_run(komb_ctx *ctx, int64_t budget)
+{
+    KOMB_HIER_ENTER(ctx, "komb_max_clique_run");
+    if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_max_clique_run: bad node budget %lld", (long long)budget);
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    return max_clique_run(ctx, budget);
+}
+
+int komb_max_clique_fetch(komb_ctx *ctx, int32_t *count, int32_t *witness)
+{
+    KOMB_HIER_ENTER(ctx, "komb_max_clique_fetch");
+    if (!ctx->mc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_fetch: no maximum-clique search of the current k-truss result");
+    if (ctx->nv > 0 && count) KOMB_HIP(ctx, staged_copy(ctx, count, ctx->d_mc_count, (size_t)ctx->nv * sizeof(int32_t), false));
+    if (witness && !ctx->mc.witness.empty()) memcpy(witness, ctx->mc.witness.data(), ctx->mc.witness.size() * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_max_clique_list(komb_ctx *ctx, int64_t cap, int64_t *n_cliques, int32_t *verts)
+{
+    KOMB_HIER_ENTER(ctx, "komb_max_clique_list");
+    if (!ctx->mc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_list: no maximum-clique search of the current k-truss result");
+    const komb_ctx::MaxClique &r = ctx->mc;
+    if (!(r.flags & KOMB_MAXCLQ_LISTED))
+        KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_max_clique_list: the list was not kept (flags %d, %lld maximum cliques; option MAXCLQ_LIST, the node budget)",
+                  r.flags, (long long)r.n_max);
+    if (verts && cap < r.n_max) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_max_clique_list: room for %lld of %lld cliques", (long long)cap, (long long)r.n_max);
+    if (n_cliques) *n_cliques = r.n_max;
+    if (verts && !r.list.empty()) memcpy(verts, r.list.data(), r.list.size() * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_max_clique_info(komb_ctx *ctx, int32_t *omega, int32_t *upper, int32_t *flags, int32_t *t_max, int64_t *n_max_cliques,
+                         int64_t *n_roots, int64_t *nodes, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_max_clique_info");
+    if (!ctx->mc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_info: no maximum-clique search of the current k-truss result");
+    const komb_ctx::MaxClique &r = ctx->mc;
+    if (omega) *omega = r.omega;
+    if (upper) *upper = r.upper;
+    if (flags) *flags = r.flags;
+    if (t_max) *t_max = r.t_max;
+    if (n_max_cliques) *n_max_cliques = r.n_max;
+    if (n_roots) *n_roots = r.n_roots;
+    if (nodes) *nodes = r.nodes;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_nucleus_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_run");

@@ -364,6 +364,18 @@ struct komb_ctx {
     } nh;
     bool nh_done = false;
 
+    // ---- maximum-clique search (max_clique.hip): the per-vertex counts in a pool block of their own, the witness and the sorted list
+    // on the host; they describe the k-truss result they were computed from and are dropped with it (truss_free)
+    int32_t *d_mc_count = nullptr;           // [nv] maximum cliques through the vertex (not enumerated: 1 on the witness)
+    struct MaxClique {
+        int32_t omega = 0, upper = 0, flags = 0, t_max = 0;
+        int64_t n_max = -1, n_roots = 0, nodes = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        std::vector<int32_t> witness;        // [omega] ascending
+        std::vector<int32_t> list;           // [n_max * omega] with KOMB_MAXCLQ_LISTED: ascending tuples in lexicographic order
+    } mc;
+    bool mc_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                      // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -539,6 +551,8 @@ int nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *
 int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_nuclei, int32_t *rep, int32_t *n_triangles,
                              int32_t *n_edges, int32_t *n_vertices);   // k checked and resolved by the caller; host outputs
 void nucleus_hierarchy_drop(komb_ctx *ctx);                   // nucleus_hierarchy.hip: the result goes with the nucleus result it indexes
+int max_clique_run(komb_ctx *ctx, int64_t budget);            // max_clique.hip: the k-truss result it needs and the budget checked by the caller
+void max_clique_drop(komb_ctx *ctx);                          // max_clique.hip: the result goes with the k-truss result it describes
 int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);

@@ -1,0 +1,580 @@
+// max_clique.hip -- maximum-clique search with a certified bound (komb_max_clique_run): omega, one witness, and -- budget
+// permitting -- every maximum clique of the last complete k-truss result.  DESIGN.md section 4.6j.
+//
+// Input: the canonical edges (eu[i] < ev[i], sorted by (eu, ev), original ids) of that result with their trussness t[i]; their
+// graph is H.  As in nucleus.hip the list is an oriented CSR: row a = the positions [rs[a], re[a]) with eu == a, ev ascending.
+// K_n has trussness n on every edge, so a clique of s vertices uses only edges of trussness >= s, and omega <= t_max.
+//
+// A clique is searched from its ROOT, the canonical edge (a, b) of its two smallest ids: its other vertices are in
+// P = {c > b : (a, c) and (b, c) in H, both of trussness >= need}, where need is the size a clique must have to matter (the
+// search: best + 1; the enumeration: omega).  One wavefront owns one root at a time:
+//   * P is cut from the tail of row a behind (a, b) and row b: the shorter is walked 64 entries at a time, the other bisected.
+//   * The |P| x |P| adjacency (edges of trussness >= need only) becomes a bit matrix, rows of W = ceil(|P| / 64) 64-bit words,
+//     in LDS up to MAXCLQ_LDS candidates and in the workgroup's slot of global scratch above.  Lane w owns word w of every row
+//     and of every candidate set: |P| <= 4096 is the design limit (KOMB_ERR_LIMIT above it, checked by a count launch first).
+//   * An iterative depth-first search over an explicit stack of candidate sets.  Level d holds the candidates that are adjacent
+//     to the d vertices chosen so far; a NODE is one evaluation of the top set R at clique size s = d + 2:
+//       - R empty: a leaf (the search: raise best; the enumeration: s == omega is a maximum clique); pop.
+//       - k_need = the colours R must need for a clique through it to matter (search: best - s + 1; enumeration: omega - s).
+//         |R| < k_need: pop.  Else k_need - 1 independent sets are taken off R greedily (Tomita-Seki colouring, sequential:
+//         first vertex of the rest, minus its row, and again).  Nothing left: R is (k_need - 1)-colourable, pop.
+//       - else the first vertex v that is left is the branch: it leaves R (the level is evaluated again when the search comes
+//         back to it, as a node of its own), and R & row(v) is pushed.
+//     Every subset of P that is a clique is reached at most once (with v | without v), so the enumeration counts each maximum
+//     clique exactly once, at its root.
+//   * best is one word: read at every node with an agent-scope atomic load, raised with atomicMax.  The wave that raises it to
+//     s owns row s of the witness table if it wins the compare-and-swap on that row's owner word: one writer per row, read by the
+//     host after the launch.  A stale best only costs nodes.
+//   * nodes: every wave adds its nodes to one counter in batches of at most 256 and reads the counter at every node; once it has
+//     reached the budget the wave stops.  The overshoot is at most 256 per wave (KOMB_MAXCLQ_OVERSHOOT in all).
+// The launches of a run: k_mc_rows, k_mc_tmax; then per phase (seed, search, enumeration) k_mc_search in count mode (the
+// largest |P|, which sizes the scratch slots and the LDS) and in the phase's mode; k_mc_verify on the witness; k_mc_mark when
+// the counts are the witness' own.  No workgroup waits for another; every loop runs over a row part, a candidate set or a
+// stack that is bounded before it starts, and the node counter bounds the search as a whole.
+#include "common.h"
+#include "nucleus_search_dev.h"
+
+#include <algorithm>
+
+namespace komb {
+
+namespace {
+
+constexpr int kMcGrid = 1024;                         // wavefronts (workgroups of one) of a launch
+constexpr uint32_t kMcBatch = 256;                    // nodes a wave adds to the counter at once, at most
+static_assert((long long)kMcGrid * kMcBatch == KOMB_MAXCLQ_OVERSHOOT, "the documented overshoot");
+constexpr uint32_t kMcMaxCand = 4096;                 // candidates of one root: one 64-bit word per lane
+constexpr uint32_t kMcLdsCand = 512;                  // default and largest MAXCLQ_LDS: 512 x 8 words = 32 KiB
+constexpr size_t kMcLdsBytes = 56u << 10;             // LDS of a workgroup (below the 64 KiB a launch gets without asking)
+constexpr size_t kMcScratchBytes = 512ull << 20;      // all scratch slots of a launch together
+constexpr int kMcSeedWaves = 64;                      // greedy dives of the seed
+constexpr long long kMcDefaultBudget = 1ll << 30;
+constexpr long long kMcMaxBudget = 0x7FFFFFFFll - KOMB_MAXCLQ_OVERSHOOT;   // nodes (and so every count[v]) fit int32
+constexpr long long kMcListDefault = 65536;
+
+enum McMode : int { MC_COUNT = 0, MC_SEED = 1, MC_SEARCH = 2, MC_ENUM = 3 };
+
+struct McCtl {                                        // 64 bytes, zeroed before every run
+    unsigned long long nodes;                         // nodes spent, all phases
+    unsigned long long n_cliques;                     // enumeration: leaves of size omega
+    unsigned long long n_roots;                       // roots opened
+    uint32_t cursor;                                  // next chunk of 64 canonical edges (zeroed before every launch)
+    uint32_t best;                                    // the largest clique found
+    uint32_t t_max;
+    uint32_t max_p;                                   // count mode: the largest |P|
+    uint32_t bad;                                     // an inconsistency (cannot happen; checked)
+    uint32_t stopped;                                 // a wave found the budget spent
+    uint32_t pad[4];
+};
+static_assert(sizeof(McCtl) == 64, "McCtl layout");
+
+struct McArgs {
+    const int32_t *eu, *ev, *tr;
+    const uint32_t *rs, *re;
+    uint32_t m, n_chunks;
+    McCtl *ctl;
+    int mode;
+    uint32_t need;                                    // count / seed / enumeration: the threshold of roots and edges (the search reads best)
+    unsigned long long budget;
+    unsigned char *scratch;                           // slot b: P[cap_p] | mat[cap_p * w_max] | stk[levels * w_max]
+    size_t slot_bytes, off_mat, off_stk;
+    uint32_t cap_p, levels;
+    uint32_t lds_cand, lds_levels, lds_off_mat, lds_off_stk;   // LDS: cur[levels] | mat | stk (offsets in 64-bit words); lds_levels == 0: the stack is global
+    int32_t *wit;                                     // witness table: row s = a clique of s vertices
+    uint32_t *wit_owner, wit_stride;
+    int32_t *count, *list;                            // enumeration
+    unsigned long long list_cap;
+    uint32_t omega;
+};
+
+__global__ void k_mc_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    const int32_t u = eu[j];
+    if (j == 0 || eu[j - 1] != u) rs[u] = j;
+    if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
+}
+
+__global__ void k_mc_tmax(const int32_t *__restrict__ tr, uint32_t m, McCtl *ctl, uint32_t best0)
+{
+    int32_t hi = 0;
+    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock) { const int32_t t = tr[j]; hi = t > hi ? t : hi; }
+    for (int off = kWave / 2; off > 0; off >>= 1) { const int32_t other = __shfl_xor(hi, off); hi = other > hi ? other : hi; }
+    if ((threadIdx.x & (kWave - 1)) == 0 && hi > 0) atomicMax(&ctl->t_max, (uint32_t)hi);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&ctl->best, best0);
+}
+
+__device__ __forceinline__ unsigned long long mc_shfl64(unsigned long long x, int src)
+{
+    const uint32_t lo = (uint32_t)__shfl((int32_t)(uint32_t)x, src), hi = (uint32_t)__shfl((int32_t)(uint32_t)(x >> 32), src);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ int mc_sum(int x)
+{
+    for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+// the first position of [lo, hi) whose entry is not below x
+__device__ __forceinline__ uint32_t mc_lower(const int32_t *__restrict__ a, int32_t x, uint32_t lo, uint32_t hi)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint32_t mc_best(McCtl *ctl) { return __hip_atomic_load(&ctl->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long mc_nodes(McCtl *ctl) { return __hip_atomic_load(&ctl->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct McWave { uint32_t nodes, roots, max_p; bool stop; };
+
+__device__ __forceinline__ void mc_flush(McCtl *ctl, McWave &w, int lane)
+{
+    if (lane == 0 && w.nodes) atomicAdd(&ctl->nodes, (unsigned long long)w.nodes);
+    w.nodes = 0;
+}
+
+// One root: canonical edge rj = (a, b).  Every branch below is uniform over the wave.
+__device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned long long *smem, McWave &w, int lane)
+{
+    McCtl *ctl = A.ctl;
+    const int32_t *__restrict__ ev = A.ev;
+    const int32_t *__restrict__ tr = A.tr;
+    const int32_t a = A.eu[rj], b = ev[rj];
+    // ---- P: the shorter of (row a behind rj, row b) is walked, the other bisected; both ascending, so P is
+    const uint32_t ab = rj + 1, ae = A.re[a], bb = A.rs[b], be = A.re[b];
+    const bool walk_a = ae - ab <= be - bb;
+    const uint32_t it = walk_a ? ab : bb, len = walk_a ? ae - ab : be - bb, lo = walk_a ? bb : ab, hi = walk_a ? be : ae;
+    unsigned char *slot = A.scratch + (size_t)blockIdx.x * A.slot_bytes;
+    int32_t *P = (int32_t *)slot;
+    const bool fill = A.mode != MC_COUNT;
+    uint32_t n = 0;
+    if (hi > lo)
+        for (uint32_t x0 = it; x0 < it + len; x0 += kWave) {
+            const uint32_t x = x0 + (uint32_t)lane;
+            bool ok = false;
+            int32_t c = 0;
+            if (x < it + len && (uint32_t)tr[x] >= need) {
+                c = ev[x];
+                const uint32_t hit = nuc_find(ev, c, lo, hi);
+                ok = hit != kNucNone && (uint32_t)tr[hit] >= need;
+            }
+            const unsigned long long hits = __ballot(ok);
+            if (ok && fill) {
+                const uint32_t pos = n + (uint32_t)__popcll(hits & nuc_below(lane));
+                if (pos < A.cap_p) P[pos] = c;
+            }
+            n += (uint32_t)__popcll(hits);
+        }
+    if (!fill) { w.max_p = n > w.max_p ? n : w.max_p; return; }
+    ++w.roots;
+    if (n > A.cap_p || n > kMcMaxCand) { if (lane == 0) ctl->bad = 1u; return; }   // (the count launch saw every root with a need not above this one)
+    if (n + 2u < (A.mode == MC_ENUM ? A.omega : mc_best(ctl) + 1u)) {            // too few candidates: closed at once, one node, no matrix
+        if (w.nodes >= kMcBatch) mc_flush(ctl, w, lane);
+        ++w.nodes;
+        return;
+    }
+    const uint32_t W = (n + 63u) >> 6;
+    const bool in_lds = n <= A.lds_cand;
+    int32_t *cur = (int32_t *)smem;
+    unsigned long long *mat = in_lds ? smem + A.lds_off_mat : (unsigned long long *)(slot + A.off_mat);
+    const bool stk_lds = in_lds && A.lds_levels > 0;
+    unsigned long long *stk = stk_lds ? smem + A.lds_off_stk : (unsigned long long *)(slot + A.off_stk);
+    const uint32_t levels = stk_lds ? A.lds_levels : A.levels;
+    __threadfence();                                     // (P: written by some lanes, read by all)
+    __syncthreads();
+    // ---- the bit matrix: bit j of row i <=> P[i] and P[j] are joined by an edge of trussness >= need
+    if (n > 0) {                                         // (a single candidate still needs its zero row)
+        for (uint32_t i = (uint32_t)lane; i < n * W; i += kWave) mat[i] = 0ull;
+        __threadfence();
+        __syncthreads();
+        uint32_t *m32 = (uint32_t *)mat;
+        const int32_t p_last = P[n - 1];
+        for (uint32_t i = 0; i + 1 < n; ++i) {
+            const int32_t c = P[i];
+            const uint32_t ce = A.re[c];
+            const uint32_t cs = mc_lower(ev, P[i + 1], A.rs[c], ce);   // (row c is above c; what is below P[i + 1] is not in P)
+            for (uint32_t x0 = cs; x0 < ce; x0 += kWave) {
+                const uint32_t x = x0 + (uint32_t)lane;
+                bool past = false;
+                if (x < ce) {
+                    const int32_t dd = ev[x];
+                    if (dd > p_last) past = true;
+                    else if ((uint32_t)tr[x] >= need) {
+                        const uint32_t pos = mc_lower(P, dd, i + 1, n);
+                        if (pos < n && P[pos] == dd) {
+                            atomicOr(m32 + ((size_t)i * W * 2 + (pos >> 5)), 1u << (pos & 31u));
+                            atomicOr(m32 + ((size_t)pos * W * 2 + (i >> 5)), 1u << (i & 31u));
+                        }
+                    }
+                }
+                if (__any(past)) break;
+            }
+        }
+        __threadfence();                                 // (the atomics went to L2: the rows are read with plain loads from here on)
+        __syncthreads();
+    }
+    // ---- the search
+    const bool mine = (uint32_t)lane < W;
+    if (mine) {
+        const uint32_t base = (uint32_t)lane * 64u;
+        stk[lane] = n - base >= 64u ? ~0ull : (1ull << (n - base)) - 1ull;
+    }
+    uint32_t d = 0;
+    for (;;) {
+        if (w.nodes >= kMcBatch) mc_flush(ctl, w, lane);
+        if (mc_nodes(ctl) + w.nodes >= A.budget) { w.stop = true; break; }
+        ++w.nodes;
+        unsigned long long R = mine ? stk[(size_t)d * W + lane] : 0ull;
+        const int cnt = mc_sum(__popcll(R));
+        const int s = (int)d + 2;
+        const uint32_t best = mc_best(ctl);
+        bool pop = false;
+        unsigned long long U = R;
+        if (cnt == 0) {
+            pop = true;
+            if (A.mode == MC_ENUM) {
+                if ((uint32_t)s == A.omega) {                        // a maximum clique: a, b and the d chosen candidates
+                    unsigned long long idx = 0;
+                    if (lane == 0) idx = atomicAdd(&ctl->n_cliques, 1ull);
+                    idx = mc_shfl64(idx, 0);
+                    const bool keep = idx < A.list_cap;
+                    for (int i = lane; i < s; i += kWave) {
+                        const int32_t v = i == 0 ? a : (i == 1 ? b : P[cur[i - 2]]);
+                        atomicAdd(A.count + v, 1);
+                        if (keep) A.list[idx * A.omega + (uint32_t)i] = v;
+                    }
+                } else if ((uint32_t)s > A.omega && lane == 0) ctl->bad = 1u;
+            } else if ((uint32_t)s > best) {
+                uint32_t won = 0;
+                if (lane == 0 && atomicMax(&ctl->best, (uint32_t)s) < (uint32_t)s && (uint32_t)s < A.wit_stride + 1u)
+                    won = atomicCAS(A.wit_owner + s, 0u, 1u) == 0u ? 1u : 0u;
+                if (__shfl((int32_t)won, 0))
+                    for (int i = lane; i < s; i += kWave)
+                        A.wit[(size_t)s * A.wit_stride + (uint32_t)i] = i == 0 ? a : (i == 1 ? b : P[cur[i - 2]]);
+            }
+        } else {
+            const int k_need = A.mode == MC_ENUM ? (int)A.omega - s : (int)best - s + 1;
+            if (cnt < k_need) pop = true;
+            for (int k = 1; k < k_need && !pop; ++k) {               // one independent set off U per round
+                unsigned long long Q = U;
+                for (;;) {
+                    const unsigned long long nz = __ballot(Q != 0ull);
+                    if (!nz) break;
+                    const int src = __ffsll((long long)nz) - 1;
+                    const unsigned long long word = mc_shfl64(Q, src);
+                    const int bit = __ffsll((long long)word) - 1;
+                    const uint32_t v = (uint32_t)src * 64u + (uint32_t)bit;
+                    if (mine) Q &= ~mat[(size_t)v * W + lane];
+                    if (lane == src) { Q &= ~(1ull << bit); U &= ~(1ull << bit); }
+                }
+                if (!__ballot(U != 0ull)) pop = true;
+            }
+        }
+        if (!pop) {
+            const unsigned long long nz = __ballot(U != 0ull);       // (not empty: cnt > 0, or the colouring left something)
+            const int src = __ffsll((long long)nz) - 1;
+            const unsigned long long word = mc_shfl64(U, src);
+            const int bit = __ffsll((long long)word) - 1;
+            const uint32_t v = (uint32_t)src * 64u + (uint32_t)bit;
+            if (d + 1 >= levels) { if (lane == 0) ctl->bad = 1u; break; }   // (a clique of more than t_max vertices)
+            if (mine) {
+                const unsigned long long child = R & mat[(size_t)v * W + lane];
+                if (lane == src) R &= ~(1ull << bit);
+                stk[(size_t)d * W + lane] = R;
+                stk[(size_t)(d + 1) * W + lane] = child;
+            }
+            if (lane == 0) cur[d] = (int32_t)v;
+            ++d;
+            continue;
+        }
+        if (A.mode == MC_SEED || d == 0) break;                      // (the seed is one greedy dive)
+        --d;
+    }
+    __syncthreads();                                     // (the next root writes P, mat and the stack again)
+}
+
+__global__ __launch_bounds__(kWave) void k_mc_search(McArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
+    const int lane = threadIdx.x;
+    McCtl *ctl = A.ctl;
+    McWave w{0u, 0u, 0u, false};
+    bool done = false;                                   // the seed: one root per wave
+    while (!w.stop && !done) {
+        uint32_t chunk = 0;
+        if (lane == 0) chunk = atomicAdd(&ctl->cursor, 1u);
+        chunk = (uint32_t)__shfl((int32_t)chunk, 0);
+        if (chunk >= A.n_chunks) break;
+        const uint32_t j = chunk * kWave + (uint32_t)lane;
+        const uint32_t tj = j < A.m ? (uint32_t)A.tr[j] : 0u;
+        unsigned long long todo = __ballot(tj >= (A.mode == MC_SEARCH ? mc_best(ctl) + 1u : A.need));
+        while (todo && !w.stop && !done) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            uint32_t need = A.need;
+            if (A.mode == MC_SEARCH) {                               // (best may have risen since the chunk was read)
+                need = mc_best(ctl) + 1u;
+                if ((uint32_t)__shfl((int32_t)tj, src) < need) continue;
+            }
+            if (A.mode != MC_COUNT && mc_nodes(ctl) >= A.budget) { w.stop = true; break; }
+            mc_root(A, chunk * kWave + (uint32_t)src, need, smem, w, lane);
+            done = A.mode == MC_SEED;
+        }
+    }
+    mc_flush(ctl, w, lane);
+    if (lane == 0) {
+        if (w.roots) atomicAdd(&ctl->n_roots, (unsigned long long)w.roots);
+        if (w.max_p) atomicMax(&ctl->max_p, w.max_p);
+        if (w.stop) ctl->stopped = 1u;
+    }
+}
+
+// every pair of the witness is an edge of H (and its vertices are distinct)
+__global__ void k_mc_verify(const int32_t *__restrict__ wit, uint32_t omega, const int32_t *__restrict__ ev, const uint32_t *__restrict__ rs,
+                            const uint32_t *__restrict__ re, McCtl *ctl)
+{
+    const uint32_t id = blockIdx.x * kBlock + threadIdx.x;
+    if (id >= omega * omega) return;
+    const uint32_t i = id / omega, j = id % omega;
+    if (i >= j) return;
+    const int32_t u = wit[i] < wit[j] ? wit[i] : wit[j], v = wit[i] < wit[j] ? wit[j] : wit[i];
+    if (u == v || nuc_find(ev, v, rs[u], re[u]) == kNucNone) ctl->bad = 1u;
+}
+
+__global__ void k_mc_mark(const int32_t *__restrict__ wit, uint32_t omega, int32_t *__restrict__ count)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < omega) count[wit[i]] = 1;
+}
+
+inline size_t mc_align16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+struct McRun {                                          // what the phases of one run share
+    komb_ctx *ctx;
+    McArgs A;
+    McCtl h;
+    uint32_t t_max, lds_opt;
+    int launch(int mode, uint32_t need, int grid_cap);
+};
+
+// One phase: a count launch for the largest |P| at this need, then the launch itself with the slots and the LDS sized from it.
+int McRun::launch(int mode, uint32_t need, int grid_cap)
+{
+    hipStream_t s = ctx->stream;
+    A.need = need;
+    A.mode = MC_COUNT;
+    A.scratch = nullptr; A.slot_bytes = 0; A.cap_p = 0;
+    const int count_grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kMcGrid);
+    KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->cursor, 0, sizeof(uint32_t), s));
+    KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->max_p, 0, sizeof(uint32_t), s));
+    k_mc_search<<<count_grid, kWave, 0, s>>>(A);
+    KOMB_HIP(ctx, hipGetLastError());
+    KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(McCtl)));
+    const uint32_t max_p = h.max_p;
+    if (max_p > kMcMaxCand)
+        KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_max_clique_run: a root edge has %u candidates of trussness >= %u; the limit is %u (one 64-bit word per lane)",
+                  max_p, need, kMcMaxCand);
+    const uint32_t depth = t_max >= 2 ? t_max - 2 : 0;
+    const uint32_t w_max = std::max<uint32_t>(1u, (max_p + 63u) >> 6);
+    A.cap_p = max_p;
+    A.levels = std::min(max_p, depth) + 2;
+    A.off_mat = mc_align16((size_t)max_p * sizeof(int32_t));
+    A.off_stk = A.off_mat + (size_t)max_p * w_max * 8;
+    A.slot_bytes = mc_align16(A.off_stk + (size_t)A.levels * w_max * 8);
+    // LDS: cur | the matrix of a root of up to lds_cand candidates | its stack, when that still fits
+    const size_t cur_words = mc_align16((size_t)A.levels * sizeof(int32_t)) / 8;
+    uint32_t n_l = std::min(max_p, lds_opt);
+    while (n_l > 0 && (cur_words + (size_t)n_l * ((n_l + 63u) >> 6)) * 8 > kMcLdsBytes) n_l -= 1;
+    const uint32_t w_l = (n_l + 63u) >> 6;
+    A.lds_cand = n_l;
+    A.lds_off_mat = (uint32_t)cur_words;
+    A.lds_off_stk = A.lds_off_mat + n_l * w_l;
+    A.lds_levels = std::min(n_l, depth) + 2;
+    size_t lds_words = A.lds_off_stk;
+    if (n_l > 0 && (lds_words + (size_t)A.lds_levels * w_l) * 8 <= kMcLdsBytes) lds_words += (size_t)A.lds_levels * w_l;
+    else A.lds_levels = 0;
+    int grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)grid_cap);
+    const size_t fit = kMcScratchBytes / A.slot_bytes;
+    if ((size_t)grid > fit) grid = fit < 1 ? 1 : (int)fit;
+    DevBufs bufs(ctx);
+    KOMB_HIP(ctx, bufs.alloc(&A.scratch, (size_t)grid * A.slot_bytes));
+    A.mode = mode;
+    KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->cursor, 0, sizeof(uint32_t), s));
+    k_mc_search<<<grid, kWave, lds_words * 8, s>>>(A);
+    KOMB_HIP(ctx, hipGetLastError());
+    KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(McCtl)));
+    if (h.bad) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: the search is inconsistent (mode %d, need %u, largest candidate set %u)", mode, need, max_p);
+    return KOMB_OK;
+}
+
+long long mc_opt(const komb_ctx *ctx, const char *name, long long dflt, long long lo, long long hi)
+{
+    const char *e = ctx_opt(ctx, name);
+    if (!e) return dflt;
+    const long long v = strtoll(e, nullptr, 10);
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+
+} // namespace
+
+void max_clique_drop(komb_ctx *ctx)
+{
+    ctx->pool.put(ctx->d_mc_count);
+    ctx->d_mc_count = nullptr;
+    ctx->mc = komb_ctx::MaxClique{};
+    ctx->mc_done = false;
+}
+
+// the k-truss result it needs and the budget's sign are checked by the caller (api.cpp).  The result is built on the side and
+// replaces the previous one only when the run has succeeded.
+int max_clique_run(komb_ctx *ctx, int64_t budget)
+{
+    hipStream_t s = ctx->stream;
+    const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv > 0 ? ctx->nv : 0;
+    if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
+    Range r_all("komb_max_clique_run");
+    struct Fresh { komb_ctx *c; int32_t *count; ~Fresh() { c->pool.put(count); } } fresh{ctx, nullptr};
+    komb_ctx::MaxClique res;
+    const long long limit = budget == 0 ? kMcDefaultBudget : std::min<long long>(budget, kMcMaxBudget);
+    const bool seed = !ctx_opt(ctx, "MAXCLQ_SEED") || ctx_flag(ctx, "MAXCLQ_SEED");
+    const long long list_cap = mc_opt(ctx, "MAXCLQ_LIST", kMcListDefault, 0, 1ll << 24);
+    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.count, (size_t)nv * sizeof(int32_t)));
+    DevBufs bufs(ctx);
+    EventSet evs;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+    KOMB_HIP(ctx, evs.make(&e0)); KOMB_HIP(ctx, evs.make(&e1)); KOMB_HIP(ctx, evs.make(&e2)); KOMB_HIP(ctx, evs.make(&e3));
+    uint64_t nodes_seed = 0, nodes_search = 0;
+    bool timed = false;
+
+    ctx->timer.start(s);
+    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.count, 0, (size_t)nv * sizeof(int32_t), s));
+    if (m == 0) {                                        // no edge: omega = 0, nothing to list, all of it proven
+        res.flags = KOMB_MAXCLQ_EXACT | KOMB_MAXCLQ_ENUMERATED | KOMB_MAXCLQ_LISTED;
+        res.n_max = 0;
+    } else {
+        McRun run{};
+        run.ctx = ctx;
+        McArgs &A = run.A;
+        uint32_t *d_rs = nullptr, *d_re = nullptr;
+        KOMB_HIP(ctx, bufs.alloc(&A.ctl, 1));
+        KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
+        KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
+        KOMB_HIP(ctx, hipMemsetAsync(A.ctl, 0, sizeof(McCtl), s));
+        KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
+        KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
+        const uint32_t um = (uint32_t)m;
+        const int g = (int)((m + kBlock - 1) / kBlock);
+        k_mc_rows<<<g, kBlock, 0, s>>>(ctx->d_t_eu, um, d_rs, d_re);
+        k_mc_tmax<<<g < 1024 ? g : 1024, kBlock, 0, s>>>(ctx->d_t_truss, um, A.ctl, 1u);
+        KOMB_HIP(ctx, hipGetLastError());
+        KOMB_HIP(ctx, d2h(ctx, &run.h, A.ctl, sizeof(McCtl)));
+        const uint32_t t_max = run.h.t_max;
+        if (t_max < 2) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: %lld edges and a largest trussness of %u", (long long)m, t_max);
+        run.t_max = t_max;
+        run.lds_opt = (uint32_t)mc_opt(ctx, "MAXCLQ_LDS", kMcLdsCand, 0, kMcLdsCand);
+        A.eu = ctx->d_t_eu; A.ev = ctx->d_t_ev; A.tr = ctx->d_t_truss; A.rs = d_rs; A.re = d_re;
+        A.m = um; A.n_chunks = (um + kWave - 1) / kWave;
+        A.budget = (unsigned long long)limit;
+        A.wit_stride = t_max;
+        KOMB_HIP(ctx, bufs.alloc(&A.wit, ((size_t)t_max + 1) * t_max));
+        KOMB_HIP(ctx, bufs.alloc(&A.wit_owner, (size_t)t_max + 1));
+        KOMB_HIP(ctx, hipMemsetAsync(A.wit_owner, 0, ((size_t)t_max + 1) * sizeof(uint32_t), s));
+        res.t_max = (int32_t)t_max;
+
+        // ---- seed: greedy dives from edges of the largest trussness
+        (void)hipEventRecord(e0, s);
+        if (seed) KOMB_TRY(run.launch(MC_SEED, t_max, kMcSeedWaves));
+        nodes_seed = run.h.nodes;
+        (void)hipEventRecord(e1, s);
+        // ---- search: omega
+        if (!run.h.stopped && run.h.best < t_max) KOMB_TRY(run.launch(MC_SEARCH, run.h.best + 1, kMcGrid));
+        nodes_search = run.h.nodes - nodes_seed;
+        (void)hipEventRecord(e2, s);
+        uint32_t omega = run.h.best;
+        const bool exact = !run.h.stopped || omega == t_max;
+        const int32_t *d_wit = A.wit + (size_t)omega * A.wit_stride;
+        std::vector<int32_t> &wit = res.witness;
+        if (omega < 2) {                                 // (the budget ran out before the first leaf: an edge is a clique)
+            omega = 2;
+            wit.resize(2);
+            KOMB_HIP(ctx, d2h(ctx, &wit[0], ctx->d_t_eu, sizeof(int32_t)));
+            KOMB_HIP(ctx, d2h(ctx, &wit[1], ctx->d_t_ev, sizeof(int32_t)));
+            KOMB_HIP(ctx, hipMemcpyAsync(A.wit, wit.data(), 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            KOMB_HIP(ctx, hipStreamSynchronize(s));
+            d_wit = A.wit;
+        } else {
+            k_mc_verify<<<(int)(((size_t)omega * omega + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_wit, omega, ctx->d_t_ev, d_rs, d_re, A.ctl);
+            KOMB_HIP(ctx, hipGetLastError());
+            wit.resize(omega);
+            KOMB_HIP(ctx, staged_copy(ctx, wit.data(), d_wit, (size_t)omega * sizeof(int32_t), false));
+            KOMB_HIP(ctx, d2h(ctx, &run.h, A.ctl, sizeof(McCtl)));
+            if (run.h.bad) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: the clique of %u vertices the search holds is not one", omega);
+            std::sort(wit.begin(), wit.end());
+        }
+        res.omega = (int32_t)omega;
+        res.flags = exact ? KOMB_MAXCLQ_EXACT : 0;
+        res.upper = exact ? (int32_t)omega : (int32_t)t_max;
+        // ---- enumeration: every maximum clique, each at its root
+        bool enumerated = false;
+        if (exact && !run.h.stopped) {
+            A.omega = omega;
+            A.count = fresh.count;
+            A.list_cap = (unsigned long long)list_cap;
+            KOMB_HIP(ctx, bufs.alloc(&A.list, (size_t)list_cap * omega));
+            KOMB_TRY(run.launch(MC_ENUM, omega, kMcGrid));
+            enumerated = !run.h.stopped;
+            if (enumerated && run.h.n_cliques < 1)
+                KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: the enumeration found no clique of %u vertices", omega);
+        }
+        if (enumerated) {
+            res.flags |= KOMB_MAXCLQ_ENUMERATED;
+            res.n_max = (int64_t)run.h.n_cliques;
+            if (run.h.n_cliques <= (unsigned long long)list_cap) {
+                res.flags |= KOMB_MAXCLQ_LISTED;
+                const size_t n = (size_t)run.h.n_cliques;
+                std::vector<int32_t> raw(n * omega);
+                KOMB_HIP(ctx, staged_copy(ctx, raw.data(), A.list, raw.size() * sizeof(int32_t), false));
+                std::vector<size_t> order(n);
+                for (size_t i = 0; i < n; ++i) { order[i] = i; std::sort(raw.begin() + i * omega, raw.begin() + (i + 1) * omega); }
+                std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+                    return std::lexicographical_compare(raw.begin() + x * omega, raw.begin() + (x + 1) * omega, raw.begin() + y * omega, raw.begin() + (y + 1) * omega);
+                });
+                res.list.resize(n * omega);
+                for (size_t i = 0; i < n; ++i) std::copy(raw.begin() + order[i] * omega, raw.begin() + (order[i] + 1) * omega, res.list.begin() + i * omega);
+                wit.assign(res.list.begin(), res.list.begin() + omega);
+            }
+        } else {                                         // the counts are the witness' own
+            res.n_max = -1;
+            KOMB_HIP(ctx, hipMemsetAsync(fresh.count, 0, (size_t)nv * sizeof(int32_t), s));
+            k_mc_mark<<<(int)((omega + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_wit, omega, fresh.count);
+            KOMB_HIP(ctx, hipGetLastError());
+        }
+        (void)hipEventRecord(e3, s);
+        timed = true;
+        res.n_roots = (int64_t)run.h.n_roots;
+        res.nodes = (int64_t)run.h.nodes;
+    }
+    res.ms = ctx->timer.stop(s);
+    KOMB_HIP(ctx, hipGetLastError());
+    if (ctx_flag(ctx, "MAXCLQ_DEBUG")) {
+        float f[3] = {0.f, 0.f, 0.f};
+        if (timed) { (void)hipEventElapsedTime(&f[0], e0, e1); (void)hipEventElapsedTime(&f[1], e1, e2); (void)hipEventElapsedTime(&f[2], e2, e3); }
+        fprintf(stderr, "komb max clique: %lld edges, t_max %d, omega %d, upper %d, flags %d, %lld maximum cliques, %lld roots, nodes %llu seed + %llu search + "
+                "%llu enumeration of %lld, run %.3f ms, seed %.3f ms, search %.3f ms, verify + enumeration %.3f ms\n", (long long)m, res.t_max, res.omega,
+                res.upper, res.flags, (long long)res.n_max, (long long)res.n_roots, (unsigned long long)nodes_seed, (unsigned long long)nodes_search,
+                (unsigned long long)((uint64_t)res.nodes - nodes_seed - nodes_search), limit, res.ms, f[0], f[1], f[2]);
+    }
+    max_clique_drop(ctx);
+    ctx->d_mc_count = fresh.count;
+    fresh.count = nullptr;
+    ctx->mc = std::move(res);
+    ctx->mc_done = true;
+    return KOMB_OK;
+}
+
+} // namespace komb

@@ -81,6 +81,14 @@
 //                       per triangle of nucleus number >= 1 in triangle order with the node it belongs to at its own Theta.
 //                       0 is off; any other value than 0 or 1 is a usage error.  VIDs depend on -t, so only the forest by
 //                       Name compares between runs.  Nothing else changes.
+//   KOMB_MAX_CLIQUE=1|<budget>  with KOMB_TRUSS=1: also write, after the truss stage, the maximum cliques of its result
+//                       (komb_max_clique_run; 1 is the default node budget, a larger number is the budget itself).
+//                       max_cliques.tsv: a header comment "# omega <n> upper <n> flags <n> cliques <n>", then one line per
+//                       maximum clique in list order, the Names of its unitigs in ascending VID order, tab separated -- or
+//                       the witness alone when the list is not held (flags without 4).  max_clique_unitigs.tsv: #Name, Count
+//                       -- the unitigs in VID order that lie in at least one maximum clique, with their number (1 on the
+//                       witness when the cliques were not enumerated).  0 is off; anything else is a usage error.  VIDs depend
+//                       on -t, so only the cliques as sets of Names compare between runs.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -88,6 +96,7 @@
 //   KOMB_STOP_AFTER_EDGES=1  write edgelist.txt + vertex_names.txt and stop
 //                       before touching the device (host-logic tests)
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -803,6 +812,56 @@ void write_nucleus(komb_ctx *ctx, const std::string &outdir, const Names &names,
     fclose(fp);
 }
 
+// KOMB_MAX_CLIQUE: komb_max_clique_run on the truss stage's result as two tables (the cliques in list order, the unitigs in VID order)
+void write_max_clique(komb_ctx *ctx, int64_t budget, const std::string &outdir, const Names &names, int64_t nv, int threads)
+{
+    int rc = komb_max_clique_run(ctx, budget);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_max_clique_run", rc);
+    int32_t omega = 0, upper = 0, flags = 0;
+    int64_t n_max = 0;
+    rc = komb_max_clique_info(ctx, &omega, &upper, &flags, nullptr, &n_max, nullptr, nullptr, nullptr);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_max_clique_info", rc);
+    std::vector<int32_t> count((size_t)nv), verts;
+    int64_t rows = 0;
+    if (flags & KOMB_MAXCLQ_LISTED) {
+        rows = n_max;
+        verts.resize((size_t)rows * (size_t)omega);
+        rc = komb_max_clique_fetch(ctx, count.data(), nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_max_clique_fetch", rc);
+        rc = komb_max_clique_list(ctx, rows, &rows, verts.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_max_clique_list", rc);
+    } else {
+        rows = omega > 0 ? 1 : 0;
+        verts.resize((size_t)omega);
+        rc = komb_max_clique_fetch(ctx, count.data(), verts.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_max_clique_fetch", rc);
+    }
+    std::string path = outdir + "/max_cliques.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "# omega %d upper %d flags %d cliques %lld\n", (int)omega, (int)upper, (int)flags, (long long)n_max);
+    write_rows(fp, rows, threads, [&](int64_t i, std::string &buf) {
+        for (int32_t k = 0; k < omega; ++k) {
+            if (k) buf.push_back('\t');
+            buf.append(names.name[(size_t)verts[(size_t)i * (size_t)omega + (size_t)k]]);
+        }
+        buf.push_back('\n');
+    });
+    fclose(fp);
+    path = outdir + "/max_clique_unitigs.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Name\tCount\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (count[(size_t)i] <= 0) return;
+        buf.append(names.name[(size_t)i]);
+        char tmp[32];
+        const int len = snprintf(tmp, sizeof(tmp), "\t%d\n", (int)count[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_NUCLEUS_HIERARCHY: komb_nucleus_hierarchy_run on the nucleus decomposition of the truss stage's result as two tables (nodes in
 // node order, member triangles in triangle order)
 void write_nucleus_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads, bool have_nucleus)
@@ -1237,6 +1296,21 @@ int main(int argc, const char **argv)
         leave(EXIT_FAILURE);
     }
 
+    // the maximum cliques of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
+    const char *mc_env = getenv("KOMB_MAX_CLIQUE");
+    const bool mc_on = mc_env && *mc_env && strcmp(mc_env, "0") != 0;
+    long long mc_budget = 0;
+    if (mc_on) {
+        char *end = nullptr;
+        errno = 0;
+        mc_budget = strtoll(mc_env, &end, 10);
+        if (*end || mc_budget < 1 || errno) {
+            fprintf(stderr, "komb2: KOMB_MAX_CLIQUE=%s: expected 0, 1 or a node budget\n", mc_env);
+            leave(EXIT_FAILURE);
+        }
+        if (mc_budget == 1) mc_budget = 0;                 // (1: on, with the library's default budget)
+    }
+
     // structural clustering of the whole graph (no counterpart in the reference; opt-in): KOMB_STRUCTURAL=<num>/<den>,<mu>.  It
     // makes a whole-graph k-truss run of its own, before the truss stage below replaces that result with the max core's.
     const char *sc_env = getenv("KOMB_STRUCTURAL");
@@ -1299,6 +1373,7 @@ int main(int argc, const char **argv)
             write_community_hierarchy(ctx, args.outdir, names, args.threads, eu, ev, tr);
         if (nuc_on) write_nucleus(ctx, args.outdir, names, nv, args.threads, eu, ev);
         if (nh_on) write_nucleus_hierarchy(ctx, args.outdir, names, args.threads, nuc_on);
+        if (mc_on) write_max_clique(ctx, (int64_t)mc_budget, args.outdir, names, nv, args.threads);
         if (hier_on) {                                     // the forest of the truss stage's result
             std::vector<int32_t> lvl((size_t)nv, 0);
             for (int64_t e = 0; e < ne_sub; ++e) {
