@@ -37,6 +37,18 @@ constexpr int kWave = 64;
 constexpr int32_t kAlive = 0x7FFFFFFF;
 constexpr int32_t kAliveMin = 0x40000000;   // every alive marker is >= this; every round / level number is below it
 
+// sum / maximum over the lanes of a wave, in every lane; every lane of the wave calls them
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (int o = kWave / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int32_t)v, o);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v)
+{
+    for (int o = kWave / 2; o > 0; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int32_t)v, o); v = other > v ? other : v; }
+    return v;
+}
+
 // Device-side control block of a peel loop.  One 128-byte record; the fields a
 // launch reads at entry are written only by the workgroup that finalises a step.
 // `seq` is the index of the launch the state is meant for: every launch carries its
@@ -529,6 +541,38 @@ int prim_sort_pairs_u32_u32(komb_ctx *ctx, uint32_t *keys, uint32_t *keys_alt, u
                             int64_t n, int end_bit, uint32_t **sorted_keys, uint32_t **sorted_vals);
 int prim_sort_pairs_u64_u32(komb_ctx *ctx, uint64_t *keys, uint64_t *keys_alt, uint32_t *vals, uint32_t *vals_alt,
                             int64_t n, int end_bit, uint64_t **sorted_keys, uint32_t **sorted_vals);
+
+// ---- the forest builder (forest.hip): what the three nesting forests share -- hierarchy.hip, community_hierarchy.hip and
+// nucleus_hierarchy.hip.  Each brings its items, its LINK kernels and its output kernels; the header comment of forest.hip
+// has the rest.
+struct ForestNodes { int32_t *k, *rep, *par; uint32_t *size, *shell; };   // nodes in the order they were made / in final order
+struct ForestCtl {                           // the first 16 bytes of a forest's control block (64 bytes, zeroed before every run)
+    uint32_t log_n;                          // hooked items so far
+    uint32_t n_nodes;                        // nodes so far
+    uint32_t n_roots;                        // tail: nodes without a parent
+    int32_t  depth;                          // tail: most nodes on a path from a root down
+};
+struct ForestState {                         // the working arrays of a run, one word per item (pool blocks of the caller)
+    int32_t *parent, *log, *claimk, *cur;    // the union-find | the hook log | the level a root's node was made at | that node
+    uint32_t *cnt, *seg;                     // items per root | seg[i]: where the i-th populated level's hooks start in the log
+    int32_t *node;                           // out: the node of every item, in the numbering of `made`
+    ForestNodes made;                        // the nodes in the order they were made
+    ForestCtl *ctl;
+    uint32_t cap;                            // items = entries of the log = the most nodes there can be
+};
+constexpr int kForestStepGrid = 2048;        // CLAIM / ADOPT: at most this many workgroups, each striding
+inline int forest_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
+inline int forest_bits(uint32_t levels) { int b = 1; while (b < 32 && (1u << b) < levels) ++b; return b; }
+// off[k] = the first position of the ascending keys[n] with a key >= k, for k = 0 .. levels (queued; reads nothing back)
+void forest_offsets(komb_ctx *ctx, uint32_t n, const uint32_t *keys, uint32_t levels, uint32_t *off);
+// CLAIM + ADOPT of the li-th populated level k, queued behind its LINK launches: order[sh_b .. sh_b + sh_n) are the level's
+// items, `hooks` bounds what LINK can have logged; isolated: nothing was linked, every item of the level makes its own node
+void forest_level(komb_ctx *ctx, const ForestState &f, int32_t k, uint32_t li, bool isolated, const uint32_t *order, uint32_t sh_b,
+                  uint32_t sh_n, uint64_t hooks);
+// the tail: the n nodes of f.made into (k, rep) order in `out` (rep through rep_map when it is given), rank[made] = final
+// number, roots and depth into f.ctl.  vals / vals_alt: n words each that have served.  Queued; reads nothing back.
+int forest_tail(komb_ctx *ctx, DevBufs &bufs, const ForestState &f, uint32_t n, int bits, ForestNodes out, int32_t *rank,
+                const int32_t *rep_map, uint32_t *vals, uint32_t *vals_alt);
 
 // ---- stages (each in its own translation unit)
 int core_run(komb_ctx *ctx, int rank = 0, int world = 1, komb_allreduce_fn fn = nullptr, void *user = nullptr, bool sharded = false);

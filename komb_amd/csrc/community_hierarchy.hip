@@ -2,34 +2,20 @@
 // community of C_k lies inside which community of C_(k-1).  DESIGN.md section 4.6e; the definition is in include/komb_accel.h.
 //
 // communities.hip's member list and triangle search (the edges of trussness >= 3 compacted in canonical order, an oriented
-// CSR of its own; walk the shorter side, bisect the longer; the same three length classes) joined to hierarchy.hip's
-// level-descending LINK / CLAIM / ADOPT, with the names moved one step: the ITEMS are the member edges, bucketed by their own
-// trussness, the LINKS are triangle records (j, x) and (j, y) of weight w = the smallest trussness of the triangle's three
-// edges -- the level at which the triangle starts to bind.  The triangles are enumerated ONCE into a record stream (a
-// counting launch of the same search sizes it: 2 T records), the stream is sorted by w, and the boundaries of the buckets are
-// read by the host once: they size every launch of the loop, which reads nothing back and waits for nothing.  Nothing is
-// linked during the enumeration -- a union made at the wrong level cannot be undone.
+// CSR of its own; walk the shorter side, bisect the longer; the same three length classes) joined to the forest builder
+// (forest.hip; its header comment has CLAIM, ADOPT, the tail and why they are right).  What is this file's: the ITEMS are the
+// member edges, by position in the member list (kept[] is monotone, so kept[root] is the smallest canonical index), bucketed
+// by their own trussness; the LINKS are triangle records (j, x) and (j, y) of weight w = the smallest trussness of the
+// triangle's three edges -- the level at which the triangle starts to bind.  The triangles are enumerated ONCE into a record
+// stream (a counting launch of the same search sizes it: 2 T records), the stream is sorted by w, and the boundaries of the
+// buckets are read by the host once: they size every launch of the loop, which reads nothing back and waits for nothing.
+// Nothing is linked during the enumeration -- a union made at the wrong level cannot be undone.  LINK (k_ch_link) is one lane
+// per record of the level; the hooks go to the log, slots taken per WAVE.
 //
-// One union-find over member positions (unionfind_dev.h: a root is the smallest position of its tree, kept[] is monotone,
-// so kept[root] is the smallest canonical index) takes the levels from the largest k down: after the records of weight >= k
-// are linked its trees are the communities of C_k.  What a level changes is told by its HOOKS, as in hierarchy.hip: a member
-// is hooked at most once in the whole run, so one log of n_members entries holds all levels.  A member of trussness k lies
-// in a triangle of the k-truss, so it has a record of weight exactly k; it was alone before, so the tree it ends the level in
-// holds a member hooked at this level.  Hence the roots of the hooked members are this level's nodes, every node owns a hooked
-// member, there are at most n_members nodes, and nothing is counted first.
-//
-// Per populated level three launches, a kernel boundary between them:
-//   LINK   one lane per record of the level; the hooks go to the log, slots taken per WAVE
-//   CLAIM  for every hooked x: cnt[root] += cnt[x]; one lane per root makes the node (k, root); for every member of the
-//          level: cnt[root] += 1.  What goes to the root the workgroup's first entry has (the giant community's, nearly
-//          always) is summed in LDS first: one global atomic per workgroup (k_comm_count's scheme)
-//   ADOPT  parents of the nodes the hooked members stood for; node and shell of the level's members (shell through LDS
-//          likewise); a node's size is its root's count
-// The tail is hierarchy.hip's: nodes sorted by (k, rep), ranks, parents, roots and a guarded depth walk.
-// Every ballot sits in a loop whose bounds are uniform over its wave; every access to parent[] is a relaxed agent-scope
-// atomic (the header comment of components.hip says why that suffices).
-#include "common.h"
-#include "unionfind_dev.h"
+// Why every node has a hooked member: a member of trussness k lies in a triangle of the k-truss, so it has a record of weight
+// exactly k; it was alone before, so the tree it ends the level in holds a member hooked at this level.
+// Every ballot sits in a loop whose bounds are uniform over its wave.
+#include "forest_dev.h"
 
 namespace komb {
 
@@ -38,38 +24,18 @@ namespace {
 constexpr uint32_t kChShort = 16;           // shorter side up to this long: the edge's own lane (communities.hip's classes)
 constexpr uint32_t kChHeavy = 2048;         // from this length on: several workgroups of k_ch_heavy (between: the edge's wave)
 constexpr int kChHeavyGrid = 256, kChHeavyChunks = 8;
-constexpr int kChStepGrid = 2048;           // k_ch_claim / k_ch_adopt: at most this many workgroups, each striding
 constexpr uint64_t kChMaxRecords = 0x7FFFFFFFull;   // the record stream is indexed with 32 bits
 
 struct ChCtl {                              // 64 bytes, zeroed before every run
+    ForestCtl f;
     uint32_t n_heavy;                       // members queued for k_ch_heavy
     uint32_t n_members;
     uint32_t rec_n;                         // records written so far
-    uint32_t log_n;                         // hooked members so far
-    uint32_t n_nodes;                       // nodes so far
-    uint32_t n_roots;                       // tail: nodes without a parent
-    int32_t  depth;                         // tail: most nodes on a path from a root down
     uint32_t pad0;
     unsigned long long n_tri;               // the counting launch: triangles
     uint32_t pad[6];
 };
-static_assert(sizeof(ChCtl) == 64, "ChCtl layout");
-
-struct ChNodes { int32_t *k, *rep, *par; uint32_t *size, *shell; };   // nodes in the order they were made / in final order
-
-inline int ch_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-inline int ch_bits(uint32_t levels) { int b = 1; while (b < 32 && (1u << b) < levels) ++b; return b; }
-
-__device__ __forceinline__ uint32_t ch_wave_sum(uint32_t v)
-{
-    for (int o = kWave / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int32_t)v, o);
-    return v;
-}
-__device__ __forceinline__ uint32_t ch_wave_max(uint32_t v)
-{
-    for (int o = kWave / 2; o > 0; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int32_t)v, o); v = other > v ? other : v; }
-    return v;
-}
+static_assert(sizeof(ChCtl) == 64 && offsetof(ChCtl, f) == 0, "ChCtl layout");
 
 // ---- members: the edges of trussness >= 3 in canonical order
 
@@ -196,7 +162,7 @@ __global__ void k_ch_tri(const int32_t *__restrict__ mu, const int32_t *__restri
     const bool mid = act && s.n > n_short;
     uint32_t found = 0;
     const uint32_t own = act && !mid ? s.n : 0u;
-    const uint32_t top = ch_wave_max(own);                       // (uniform: the ballots of ch_emit see the whole wave)
+    const uint32_t top = wave_max(own);                       // (uniform: the ballots of ch_emit see the whole wave)
     for (uint32_t i = 0; i < top; ++i) ch_entry<kEmit>(i < own, j, s.it + i, s.lo, s.hi, mv, mt, ctl, st, found);
     unsigned long long m = __ballot(mid);
     while (m) {
@@ -208,7 +174,7 @@ __global__ void k_ch_tri(const int32_t *__restrict__ mu, const int32_t *__restri
             ch_entry<kEmit>(base + (uint32_t)lane < rn, rj, rit + base + (uint32_t)lane, rlo, rhi, mv, mt, ctl, st, found);
     }
     if (!kEmit) {
-        found = ch_wave_sum(found);
+        found = wave_sum(found);
         if (lane == 0 && found) atomicAdd(&ctl->n_tri, (unsigned long long)found);
         if (j == 0) ctl->n_members = *n_mem;
     }
@@ -231,19 +197,9 @@ __global__ void k_ch_heavy(const int32_t *__restrict__ mu, const int32_t *__rest
             ch_entry<kEmit>(base + t < s.n, j, s.it + base + t, s.lo, s.hi, mv, mt, ctl, st, found);
     }
     if (!kEmit) {
-        found = ch_wave_sum(found);
+        found = wave_sum(found);
         if ((threadIdx.x & (kWave - 1)) == 0 && found) atomicAdd(&ctl->n_tri, (unsigned long long)found);
     }
-}
-
-// off[k] = the first position of the sorted keys with a key >= k, for k = 0 .. levels (every word written exactly once)
-__global__ void k_ch_offsets(uint32_t n, const uint32_t *__restrict__ keys, uint32_t levels, uint32_t *__restrict__ off)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i > n) return;
-    const uint32_t first = i > 0 ? keys[i - 1] + 1u : 0u;
-    const uint32_t last = i < n ? keys[i] : levels;
-    for (uint32_t k = first; k <= last && k <= levels; ++k) off[k] = i;
 }
 
 // ---- the levels
@@ -253,175 +209,13 @@ __global__ void k_ch_link(const unsigned long long *__restrict__ recs, uint32_t 
                           ChCtl *ctl, int32_t *__restrict__ log, uint32_t cap)
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    const int lane = threadIdx.x & (kWave - 1);
     int32_t hooked = -1;
     if (i < r_n) {
         const unsigned long long r = recs[r_b + i];
         const uint32_t j = (uint32_t)(r >> 32), x = (uint32_t)r;
         if (j < n_mem && x < n_mem) hooked = comp_link_hooked(parent, (int32_t)j, (int32_t)x);
     }
-    const unsigned long long m = __ballot(hooked >= 0);
-    if (!m) return;
-    const int lead = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == lead) base = atomicAdd(&ctl->log_n, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int32_t)base, lead);
-    if (hooked < 0) return;
-    const uint32_t slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (slot < cap) log[slot] = hooked;      // (cannot overflow: a member is hooked once)
-}
-
-// arr[key] += 1 for every lane with key >= 0: the lanes of a wave that share a key add once, and what goes to `first` is
-// summed in *s_sum (LDS) for the workgroup's one global atomic.  Every lane of the wave calls it.
-__device__ __forceinline__ void ch_group_add(uint32_t *arr, int32_t key, int32_t first, uint32_t *s_sum)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const bool act = key >= 0;
-    unsigned long long m = __ballot(act);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        const int32_t lead = __shfl(key, src);
-        const unsigned long long same = __ballot(act && key == lead);
-        if (lane == src) {
-            if (lead == first) atomicAdd(s_sum, (uint32_t)__popcll(same));
-            else atomicAdd(arr + lead, (uint32_t)__popcll(same));
-        }
-        m &= ~same;
-    }
-}
-
-// the node (k, r) of root r, made by the first lane that asks for it at this level (levels descend: the atomicMin tells it)
-__device__ __forceinline__ void ch_claim(int32_t r, int32_t k, ChCtl *ctl, int32_t *claimk, int32_t *cur, const ChNodes &t, uint32_t cap)
-{
-    if (pload(claimk + r) <= k) return;      // (the word only falls: a stale read costs the atomic, no more)
-    if (atomicMin(claimk + r, k) <= k) return;
-    const uint32_t id = atomicAdd(&ctl->n_nodes, 1u);
-    if (id >= cap) return;                   // (cannot happen: every node has a hooked member of its own; the host checks n_nodes)
-    t.k[id] = k; t.rep[id] = r; t.par[id] = -1; t.size[id] = 0u; t.shell[id] = 0u;
-    const int32_t prev = cur[r];             // cur[r] belongs to this lane: r is a root, and only its claimer touches it in this launch
-    if (prev >= 0) t.par[prev] = (int32_t)id;    // the same root stood for a community of a higher level: now a child
-    cur[r] = (int32_t)id;
-}
-
-// CLAIM (after the level's LINK; hooks nothing: a member read as a root is one.  Its walks still split the paths they pass).
-// seg[li] .. log_n is the level's segment of the log; mord[sh_b .. sh_b + sh_n) are the level's members.
-__global__ void k_ch_claim(int32_t k, uint32_t li, const uint32_t *__restrict__ mord, uint32_t sh_b, uint32_t sh_n, int32_t *parent,
-                           const int32_t *__restrict__ log, uint32_t *seg, ChCtl *ctl, int32_t *claimk, int32_t *cur, uint32_t *cnt,
-                           ChNodes t, uint32_t cap)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const uint32_t lb = seg[li];
-    uint32_t le = ctl->log_n;
-    if (le > cap) le = cap;
-    const uint32_t b0 = blockIdx.x * kBlock, stride = gridDim.x * kBlock;
-    if (b0 + threadIdx.x == 0) seg[li + 1] = le;                 // (read by later launches only)
-    const int lane = threadIdx.x & (kWave - 1);
-    if (threadIdx.x == 0) {                                      // the root this workgroup's first entry has
-        s_first = lb + b0 < le ? comp_find(parent, log[lb + b0]) : (b0 < sh_n ? comp_find(parent, (int32_t)mord[sh_b + b0]) : -1);
-        s_sum = 0u;
-    }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t base = lb + b0; base < le; base += stride) {   // (uniform per workgroup: the ballots see whole waves)
-        const uint32_t i = base + threadIdx.x;
-        int32_t r = -1;
-        uint32_t mine = 0;
-        if (i < le) {
-            const int32_t x = log[i];
-            r = comp_find(parent, x);
-            const uint32_t c = cnt[x];       // x is no root any more: nobody adds to cnt[x] now
-            if (r == first) mine = c;
-            else if (c) atomicAdd(cnt + r, c);
-        }
-        mine = ch_wave_sum(mine);
-        if (lane == 0 && mine) atomicAdd(&s_sum, mine);
-        unsigned long long m = __ballot(r >= 0);                 // one lane per distinct root of the wave asks for its node
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(r, src);
-            const unsigned long long same = __ballot(r == lead);
-            if (lane == src) ch_claim(lead, k, ctl, claimk, cur, t, cap);
-            m &= ~same;
-        }
-    }
-    for (uint32_t base = b0; base < sh_n; base += stride) {
-        const uint32_t j = base + threadIdx.x;
-        const int32_t r = j < sh_n ? comp_find(parent, (int32_t)mord[sh_b + j]) : -1;
-        ch_group_add(cnt, r, first, &s_sum);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(cnt + first, s_sum);
-}
-
-// ADOPT (after CLAIM: cur[] of this level's roots is settled)
-__global__ void k_ch_adopt(uint32_t li, const uint32_t *__restrict__ mord, uint32_t sh_b, uint32_t sh_n, const int32_t *parent,
-                           const int32_t *__restrict__ log, const uint32_t *__restrict__ seg, const int32_t *__restrict__ cur,
-                           const uint32_t *__restrict__ cnt, ChNodes t, int32_t *__restrict__ mnode)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const uint32_t lb = seg[li], le = seg[li + 1];
-    const uint32_t b0 = blockIdx.x * kBlock, stride = gridDim.x * kBlock;
-    if (threadIdx.x == 0) {                                      // the node this workgroup's first member goes to
-        s_first = b0 < sh_n ? cur[comp_find_ro(parent, (int32_t)mord[sh_b + b0])] : -1;
-        s_sum = 0u;
-    }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t i = lb + b0 + threadIdx.x; i < le; i += stride) {
-        const int32_t x = log[i];
-        const int32_t r = comp_find_ro(parent, x);
-        const int32_t nr = cur[r], nx = cur[x];
-        if (nr < 0) continue;
-        if (nx >= 0) t.par[nx] = nr;         // x was the root of a community of a higher level
-        t.size[nr] = cnt[r];                 // (every writer stores the same word)
-    }
-    for (uint32_t base = b0; base < sh_n; base += stride) {      // (uniform per workgroup)
-        const uint32_t j = base + threadIdx.x;
-        int32_t nr = -1;
-        if (j < sh_n) {
-            const int32_t e = (int32_t)mord[sh_b + j];
-            const int32_t r = comp_find_ro(parent, e);
-            nr = cur[r];
-            mnode[e] = nr;
-            if (nr >= 0) t.size[nr] = cnt[r];
-        }
-        ch_group_add(t.shell, nr, first, &s_sum);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum && first >= 0) atomicAdd(t.shell + first, s_sum);
-}
-
-// ---- the tail: nodes into (k, rep) order
-__global__ void k_ch_node_keys(uint32_t n, ChNodes t, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = ((uint64_t)(uint32_t)t.k[i] << 32) | (uint32_t)t.rep[i];      // (rep: a member position, ordered as the canonical indices are)
-    vals[i] = i;
-}
-
-__global__ void k_ch_ranks(uint32_t n, const uint32_t *__restrict__ order, int32_t *__restrict__ rank)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j < n) rank[order[j]] = (int32_t)j;
-}
-
-__global__ void k_ch_nodes_out(uint32_t n, const uint32_t *__restrict__ order, const int32_t *__restrict__ rank, const int32_t *__restrict__ kept,
-                               ChNodes t, ChNodes out, ChCtl *ctl)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    bool root = false;
-    if (j < n) {
-        const uint32_t i = order[j];
-        const int32_t p = t.par[i];
-        out.k[j] = t.k[i]; out.rep[j] = kept[t.rep[i]]; out.par[j] = p >= 0 ? rank[p] : -1;
-        out.size[j] = t.size[i]; out.shell[j] = t.shell[i];
-        root = p < 0;
-    }
-    const unsigned long long m = __ballot(root);
-    if ((threadIdx.x & (kWave - 1)) == 0 && m) atomicAdd(&ctl->n_roots, (uint32_t)__popcll(m));
+    forest_log_wave(hooked, &ctl->f, log, cap);
 }
 
 // node[] in canonical order; mnode == nullptr: no members
@@ -438,21 +232,8 @@ __global__ void k_ch_edges_out(uint32_t m, const int32_t *__restrict__ truss, co
     out[i] = nd;
 }
 
-// the most nodes on a path from a root down (parents have smaller numbers: every walk ends)
-__global__ void k_ch_depth(uint32_t n, const int32_t *__restrict__ par, ChCtl *ctl)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    int32_t d = 0;
-    if (j < n) {
-        d = 1;
-        for (int32_t c = (int32_t)j, a = par[j]; a >= 0 && a < c; c = a, a = par[a]) ++d;
-    }
-    for (int o = kWave / 2; o > 0; o >>= 1) { const int32_t other = __shfl_xor(d, o); d = other > d ? other : d; }
-    if ((threadIdx.x & (kWave - 1)) == 0 && d) atomicMax(&ctl->depth, d);
-}
-
-// komb_community_hierarchy_labels: from node[i] up while the parent's level is still >= k (parents have smaller numbers:
-// every walk ends); k == 2: an edge without a node is a community of its own
+// komb_community_hierarchy_labels: from node[i] up while the parent's level is still >= k; k == 2: an edge without a node is
+// a community of its own
 __global__ void k_ch_labels(uint32_t m, int32_t k, const int32_t *__restrict__ enode, uint32_t n, const int32_t *__restrict__ nk,
                             const int32_t *__restrict__ rep, const int32_t *__restrict__ par, const int32_t *__restrict__ size,
                             int32_t *__restrict__ label, int32_t *__restrict__ lsize)
@@ -464,7 +245,7 @@ __global__ void k_ch_labels(uint32_t m, int32_t k, const int32_t *__restrict__ e
     if (c < 0 || (uint32_t)c >= n) {
         if (k <= 2) { lab = (int32_t)i; sz = 1; }
     } else if (nk[c] >= k) {
-        for (int32_t a = par[c]; a >= 0 && a < c && nk[a] >= k; a = par[a]) c = a;
+        c = forest_walk_up(c, k, nk, par);
         lab = rep[c]; sz = size[c];
     }
     label[i] = lab; lsize[i] = sz;
@@ -510,7 +291,7 @@ int community_hierarchy_run(komb_ctx *ctx)
         DevBufs bufs(ctx);
         const int32_t top = ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
         const uint32_t levels = (uint32_t)top + 1u;              // level numbers 0 .. levels - 1
-        const int bits = ch_bits(levels);
+        const int bits = forest_bits(levels);
         const uint32_t heavy_cap = (uint32_t)m;                  // every member could be queued
         const uint32_t n_short = ch_opt_u32(ctx, "COMM_SHORT", kChShort);      // (tests: every edge through the wave / the queued path)
         uint32_t n_heavy = ch_opt_u32(ctx, "COMM_HEAVY", kChHeavy);
@@ -540,12 +321,12 @@ int community_hierarchy_run(komb_ctx *ctx)
         const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *truss = ctx->d_t_truss;
         const uint32_t *d_nm = d_pos + m;                        // the number of members, on the device
         uint32_t *cnt = d_flag;
-        const int grid = ch_grid(m);
+        const int grid = forest_grid(m);
         ctx->timer.start(s);
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(ChCtl), s));
         KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
         KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
-        k_ch_flag<<<ch_grid(m + 1), kBlock, 0, s>>>(truss, (uint32_t)m, d_flag);
+        k_ch_flag<<<forest_grid(m + 1), kBlock, 0, s>>>(truss, (uint32_t)m, d_flag);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
         k_ch_compact<<<grid, kBlock, 0, s>>>(eu, ev, truss, (uint32_t)m, levels, d_pos, kept, mu, mv, mt, mkeys, mvals, parent, cnt, cur, claimk);
         k_ch_rows<<<grid, kBlock, 0, s>>>(mu, d_nm, d_rs, d_re);
@@ -570,7 +351,7 @@ int community_hierarchy_run(komb_ctx *ctx)
             uint32_t *rkeys2 = nullptr, *d_tab = nullptr, *seg = nullptr;
             unsigned long long *rvals2 = nullptr;
             int32_t *log = nullptr;
-            ChNodes t{};
+            ForestNodes t{};
             KOMB_HIP(ctx, bufs.alloc(&st.keys, (size_t)n_rec));
             KOMB_HIP(ctx, bufs.alloc(&rkeys2, (size_t)n_rec));
             KOMB_HIP(ctx, bufs.alloc(&st.vals, (size_t)n_rec));
@@ -588,16 +369,16 @@ int community_hierarchy_run(komb_ctx *ctx)
             uint32_t *d_moff = d_tab, *d_roff = d_tab + levels + 1;
             KOMB_HIP(ctx, hipMemsetAsync(d_tab, 0, tab_words * sizeof(uint32_t), s));
 
-            const int mgrid = ch_grid(nm);
+            const int mgrid = forest_grid(nm);
             k_ch_tri<true><<<mgrid, kBlock, 0, s>>>(mu, mv, mt, d_rs, d_re, d_nm, d_ctl, d_heavy, heavy_cap, n_short, n_heavy, st);
             if (h.n_heavy)
                 k_ch_heavy<true><<<dim3(kChHeavyGrid, kChHeavyChunks), kBlock, 0, s>>>(mu, mv, mt, d_rs, d_re, d_ctl, d_heavy, heavy_cap, st);
             uint32_t *rsorted = nullptr, *msorted = nullptr, *mord = nullptr;
             unsigned long long *recs = nullptr;
             KOMB_TRY(prim_sort_pairs_u32_u64(ctx, st.keys, rkeys2, st.vals, rvals2, n_rec, 0, bits, &rsorted, &recs));
-            k_ch_offsets<<<ch_grid((int64_t)n_rec + 1), kBlock, 0, s>>>(n_rec, rsorted, levels, d_roff);
+            forest_offsets(ctx, n_rec, rsorted, levels, d_roff);
             KOMB_TRY(prim_sort_pairs_u32_u32(ctx, mkeys, mkeys2, mvals, mvals2, nm, bits, &msorted, &mord));
-            k_ch_offsets<<<ch_grid((int64_t)nm + 1), kBlock, 0, s>>>(nm, msorted, levels, d_moff);
+            forest_offsets(ctx, nm, msorted, levels, d_moff);
             KOMB_HIP(ctx, hipGetLastError());
             std::vector<uint32_t> tab(tab_words);
             KOMB_HIP(ctx, d2h(ctx, tab.data(), d_tab, tab_words * sizeof(uint32_t)));     // the one read before the loop
@@ -611,40 +392,29 @@ int community_hierarchy_run(komb_ctx *ctx)
             KOMB_HIP(ctx, bufs.alloc(&seg, (size_t)n_levels + 1));                      // seg[i]: where the i-th populated level's hooks start in the log
             KOMB_HIP(ctx, hipMemsetAsync(seg, 0, ((size_t)n_levels + 1) * sizeof(uint32_t), s));
 
+            const ForestState f{parent, log, claimk, cur, cnt, seg, mnode, t, &d_ctl->f, nm};
             uint32_t li = 0;
             for (int32_t k = (int32_t)levels - 1; k >= 3; --k) {                        // no read and no wait in this loop
                 const uint32_t sh_b = moff[k], sh_n = moff[k + 1] - moff[k];
                 const uint32_t r_b = roff[k], r_n = roff[k + 1] - roff[k];
                 if (!sh_n) continue;                                                    // (a record of weight k has an edge of trussness k)
                 if (li == 0) k_max = k;
-                if (r_n) k_ch_link<<<ch_grid(r_n), kBlock, 0, s>>>(recs, r_b, r_n, nm, parent, d_ctl, log, nm);
-                const uint64_t hooks = r_n < nm ? r_n : nm;                             // at most this many hooks at this level
-                const uint64_t work = hooks > sh_n ? hooks : sh_n;
-                const int g = (int)((work + kBlock - 1) / kBlock < (uint64_t)kChStepGrid ? (work + kBlock - 1) / kBlock : (uint64_t)kChStepGrid);
-                k_ch_claim<<<g > 0 ? g : 1, kBlock, 0, s>>>(k, li, mord, sh_b, sh_n, parent, log, seg, d_ctl, claimk, cur, cnt, t, nm);
-                k_ch_adopt<<<g > 0 ? g : 1, kBlock, 0, s>>>(li, mord, sh_b, sh_n, parent, log, seg, cur, cnt, t, mnode);
+                if (r_n) k_ch_link<<<forest_grid(r_n), kBlock, 0, s>>>(recs, r_b, r_n, nm, parent, d_ctl, log, nm);
+                forest_level(ctx, f, k, li, false, mord, sh_b, sh_n, r_n < nm ? r_n : nm);      // at most this many hooks at this level
                 ++li;
             }
             KOMB_HIP(ctx, hipGetLastError());
             KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(ChCtl)));                          // the number of nodes sizes the tail
-            if (h.n_nodes > nm || h.log_n > nm || h.rec_n != n_rec)
+            if (h.f.n_nodes > nm || h.f.log_n > nm || h.rec_n != n_rec)
                 KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_community_hierarchy_run: inconsistent state (%u nodes, %u hooks, %u members, %u of %u records)",
-                          h.n_nodes, h.log_n, nm, h.rec_n, n_rec);
-            n = h.n_nodes;
+                          h.f.n_nodes, h.f.log_n, nm, h.rec_n, n_rec);
+            n = h.f.n_nodes;
             if (n > 0) {
                 cap_nodes = n;
                 KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.nodes, 5 * cap_nodes * sizeof(int32_t)));
-                ChNodes out{fresh.nodes, fresh.nodes + cap_nodes, fresh.nodes + 2 * cap_nodes,
-                            (uint32_t *)fresh.nodes + 3 * cap_nodes, (uint32_t *)fresh.nodes + 4 * cap_nodes};
-                uint64_t *nkeys = nullptr, *nkeys2 = nullptr, *nsorted = nullptr;
-                uint32_t *order = nullptr;
-                KOMB_HIP(ctx, bufs.alloc(&nkeys, (size_t)n));
-                KOMB_HIP(ctx, bufs.alloc(&nkeys2, (size_t)n));
-                k_ch_node_keys<<<ch_grid(n), kBlock, 0, s>>>(n, t, nkeys, mvals);       // (the members' sort has served: n <= nm)
-                KOMB_TRY(prim_sort_pairs_u64_u32(ctx, nkeys, nkeys2, mvals, mvals2, n, 32 + bits, &nsorted, &order));
-                k_ch_ranks<<<ch_grid(n), kBlock, 0, s>>>(n, order, rank);
-                k_ch_nodes_out<<<ch_grid(n), kBlock, 0, s>>>(n, order, rank, kept, t, out, d_ctl);
-                k_ch_depth<<<ch_grid(n), kBlock, 0, s>>>(n, out.par, d_ctl);
+                ForestNodes out{fresh.nodes, fresh.nodes + cap_nodes, fresh.nodes + 2 * cap_nodes,
+                                (uint32_t *)fresh.nodes + 3 * cap_nodes, (uint32_t *)fresh.nodes + 4 * cap_nodes};
+                KOMB_TRY(forest_tail(ctx, bufs, f, n, bits, out, rank, kept, mvals, mvals2));    // (the members' sort has served: n <= nm)
             }
             k_ch_edges_out<<<grid, kBlock, 0, s>>>((uint32_t)m, truss, d_pos, mnode, rank, n, fresh.enode);
         } else {
@@ -653,7 +423,7 @@ int community_hierarchy_run(komb_ctx *ctx)
         ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(ChCtl)));
-        n_nodes = (int64_t)n; n_roots = (int64_t)h.n_roots; depth = h.depth; n_members = (int64_t)nm;
+        n_nodes = (int64_t)n; n_roots = (int64_t)h.f.n_roots; depth = h.f.depth; n_members = (int64_t)nm;
         if (n == 0) k_max = 2;
     }
     if (!fresh.nodes) KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.nodes, 5 * cap_nodes * sizeof(int32_t)));
@@ -680,7 +450,7 @@ int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t
     KOMB_HIP(ctx, bufs.alloc(&d_size, (size_t)m));
     const int32_t *nodes = ctx->d_ch_nodes;
     const size_t c = (size_t)ctx->ch_cap;
-    k_ch_labels<<<ch_grid(m), kBlock, 0, s>>>((uint32_t)m, k, ctx->d_ch_enode, (uint32_t)ctx->ch_nodes, nodes, nodes + c, nodes + 2 * c,
+    k_ch_labels<<<forest_grid(m), kBlock, 0, s>>>((uint32_t)m, k, ctx->d_ch_enode, (uint32_t)ctx->ch_nodes, nodes, nodes + c, nodes + 2 * c,
                                               nodes + 3 * c, d_label, d_size);
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, hipStreamSynchronize(s));

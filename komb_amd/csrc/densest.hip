@@ -62,12 +62,6 @@ __device__ __forceinline__ bool den_equal(unsigned long long m1, unsigned long l
     return m1 * n2 == m2 * n1;
 }
 
-__device__ __forceinline__ uint32_t den_wave_max(uint32_t x)
-{
-    for (int o = kWave / 2; o > 0; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int32_t)x, o); x = other > x ? other : x; }
-    return x;
-}
-
 // ---- the three row passes: what they do with a row.  lane_row: the whole row by one lane.  row_begin / wave_part / row_end:
 // a row walked by a wave (every lane of the wave calls them, i < re says whether the lane holds an entry); kHeavy: several
 // waves of several workgroups share the row.
@@ -120,7 +114,7 @@ struct DenCount {
     __device__ void begin(uint32_t *) { mx = 0u; }
     __device__ void end(uint32_t *, DenCtl *ctl)
     {
-        const uint32_t m = den_wave_max(mx);
+        const uint32_t m = wave_max(mx);
         if ((threadIdx.x & (kWave - 1)) == 0 && m > ctl->max_deg_p) atomicMax(&ctl->max_deg_p, m);   // (the word only grows: a stale read costs the atomic)
     }
     __device__ __forceinline__ bool member(const DenCtl *ctl, uint32_t v) const { return core[v] >= ctl->k_prune; }
@@ -310,7 +304,7 @@ __global__ void __launch_bounds__(kBlock) k_den_total(uint32_t nv, const uint32_
     if (n > heavy_cap) n = heavy_cap;
     uint32_t mx = 0;
     for (uint32_t h = threadIdx.x; h < n; h += kBlock) { const uint32_t d = hdeg[h]; mx = d > mx ? d : mx; }
-    mx = den_wave_max(mx);
+    mx = wave_max(mx);
     if ((threadIdx.x & (kWave - 1)) == 0 && mx) atomicMax(&ctl->max_deg_p, mx);
     if (threadIdx.x == 0) {
         ctl->n_p = pid[nv - 1] + flag[nv - 1];
@@ -395,7 +389,7 @@ __global__ void __launch_bounds__(kBlock) k_den_keys(uint32_t n, const uint32_t 
         keys[i] = ((uint64_t)(0xFFFFFFFFu - l) << 32) | (uint32_t)i;
         mx = l > mx ? l : mx;
     }
-    mx = den_wave_max(mx);
+    mx = wave_max(mx);
     if ((threadIdx.x & (kWave - 1)) == 0 && mx > ctl->load_max) atomicMax(&ctl->load_max, mx);
 }
 

@@ -2,71 +2,42 @@
 // (komb_nucleus_hierarchy_run): which k-nucleus lies inside which (k-1)-nucleus.  DESIGN.md section 4.6i; the definition is
 // in include/komb_accel.h.
 //
-// community_hierarchy.hip's level-descending LINK / CLAIM / ADOPT one rung up: the ITEMS are the triangles of the stored
-// nucleus result (ids in ascending (a, b, c) order), bucketed by their own theta; the LINKS are 4-clique records of weight
+// The forest builder (forest.hip; its header comment has CLAIM, ADOPT, the tail and why they are right) one rung above
+// community_hierarchy.hip.  What is this file's: the ITEMS are the triangles of the stored nucleus result (ids in ascending
+// (a, b, c) order: the root of a tree is its rep), bucketed by their own theta; the LINKS are 4-clique records of weight
 // w = the smallest theta of the clique's four triangles -- the level at which the clique starts to bind.  komb_nucleus_run
 // drops its clique records with its scratch, so the cliques are enumerated ONCE more here, by nucleus.hip's search
 // (nucleus_search_dev.h: the shortest of three tails walked, the other two bisected, the ids of the other three triangles by
 // bisection in c[] through a rebuilt tri_ptr), into a record stream whose length the stored result gives exactly
 // (n_cliques4): there is no counting pass, a wave takes its slots with one returning atomic, and a cursor that does not end
 // on n_cliques4 fails the run.  The stream is sorted by w (a sort of (w, slot) pairs; LINK reads its records through the
-// sorted slots), the bucket boundaries are read by the host once, and the loop behind them reads nothing back.
+// sorted slots), the bucket boundaries are read by the host once, and the loop behind them reads nothing back.  LINK
+// (k_nh_link) is one lane per record of the level: (t0, t1), (t0, t2), (t0, t3); the hooks go to the log, slots taken per WAVE.
 //
-// One union-find over triangle ids (unionfind_dev.h: a root is the smallest id of its tree, so it is the rep) takes the levels
-// from theta_max down to 1: after the records of weight >= k are linked its trees are the k-nuclei.  A triangle of theta = k
-// lies in at least k cliques whose other triangles all have theta >= k, records of weight exactly k; it was alone before, so
-// the tree it ends the level in holds a triangle hooked at this level.  Hence the roots of the hooked triangles are this
-// level's nodes, every node owns a hooked triangle, there are at most n_members nodes, and nothing is counted first.
-//
-// Per populated level three launches, a kernel boundary between them (the names and the LDS sums are community_hierarchy.hip's):
-//   LINK   one lane per record of the level: (t0, t1), (t0, t2), (t0, t3); the hooks go to the log, slots taken per WAVE
-//   CLAIM  for every hooked x: cnt[root] += cnt[x]; one lane per root makes the node (k, root); for every triangle of the
-//          level: cnt[root] += 1.  What goes to the root the workgroup's first entry has is summed in LDS first
-//   ADOPT  parents of the nodes the hooked triangles stood for; node and shell of the level's triangles; a node's size
-// The tail: nodes sorted by (k, rep), ranks, parents, roots and a guarded depth walk.
+// Why every node has a hooked triangle: a triangle of theta = k lies in at least k cliques whose other triangles all have
+// theta >= k, records of weight exactly k; it was alone before, so the tree it ends the level in holds a triangle hooked at
+// this level.  The levels run from theta_max down to 1.
 // Every ballot sits in a loop whose bounds are uniform over its wave; every device loop runs over a row part or a length
-// fixed before its launch; every access to parent[] is a relaxed agent-scope atomic, and the labels are read by a later
-// store-free launch (the header comment of components.hip says why).
-#include "common.h"
+// fixed before its launch; the labels are read by a later store-free launch (the header comment of components.hip says why).
+#include "forest_dev.h"
 #include "nucleus_search_dev.h"
-#include "unionfind_dev.h"
 
 namespace komb {
 
 namespace {
 
 constexpr uint32_t kNhShort = 16;           // walked tail up to this long: the triangle's own lane (option NUC_SHORT, as in nucleus.hip)
-constexpr int kNhStepGrid = 2048;           // k_nh_claim / k_nh_adopt: at most this many workgroups, each striding
 
 struct NhCtl {                              // 64 bytes, zeroed before every run
+    ForestCtl f;
     uint32_t rec_n;                         // clique records written so far
     uint32_t n_members;                     // triangles with theta >= 1
-    uint32_t log_n;                         // hooked triangles so far
-    uint32_t n_nodes;                       // nodes so far
-    uint32_t n_roots;                       // tail: nodes without a parent
-    int32_t  depth;                         // tail: most nodes on a path from a root down
     uint32_t bad;                           // a position or a triangle id that a bisection did not find (cannot happen; checked)
     uint32_t pad[9];
 };
-static_assert(sizeof(NhCtl) == 64, "NhCtl layout");
-
-struct NhNodes { int32_t *k, *rep, *par; uint32_t *size, *shell; };   // nodes in the order they were made / in final order
+static_assert(sizeof(NhCtl) == 64 && offsetof(NhCtl, f) == 0, "NhCtl layout");
 
 struct NhStream { uint32_t *keys, *idx; uint4 *recs; uint32_t cap; };  // record slot q: weight | q | the four triangle ids
-
-inline int nh_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-inline int nh_bits(uint32_t levels) { int b = 1; while (b < 32 && (1u << b) < levels) ++b; return b; }
-
-__device__ __forceinline__ uint32_t nh_wave_sum(uint32_t v)
-{
-    for (int o = kWave / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int32_t)v, o);
-    return v;
-}
-__device__ __forceinline__ uint32_t nh_wave_max(uint32_t v)
-{
-    for (int o = kWave / 2; o > 0; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int32_t)v, o); v = other > v ? other : v; }
-    return v;
-}
 
 // ---- the search structures of nucleus.hip, rebuilt from the stored a, b, c and the canonical edge list
 
@@ -175,7 +146,7 @@ __global__ void k_nh_clq(const int32_t *__restrict__ ev, const uint32_t *__restr
     if (t < n_tri && o.j[t] != kNucNone) s = nuc_tails(o, rs, re, t);
     const bool act = s.n > 0, mid = act && s.n > n_short;
     const uint32_t own = act && !mid ? s.n : 0u;
-    const uint32_t top = nh_wave_max(own);                               // (uniform per wave)
+    const uint32_t top = wave_max(own);                               // (uniform per wave)
     for (uint32_t i = 0; i < top; ++i) {
         const bool hit = i < own && nuc_clq_entry(ev, s, s.it + i);
         nh_emit(hit, t, s.it + i, ev, o, tri_ptr, theta, ctl, st);
@@ -210,32 +181,7 @@ __global__ void k_nh_compact(uint32_t n_tri, const int32_t *__restrict__ theta, 
     mvals[j] = t;
 }
 
-// off[k] = the first position of the sorted keys with a key >= k, for k = 0 .. levels (every word written exactly once)
-__global__ void k_nh_offsets(uint32_t n, const uint32_t *__restrict__ keys, uint32_t levels, uint32_t *__restrict__ off)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i > n) return;
-    const uint32_t first = i > 0 ? keys[i - 1] + 1u : 0u;
-    const uint32_t last = i < n ? keys[i] : levels;
-    for (uint32_t k = first; k <= last && k <= levels; ++k) off[k] = i;
-}
-
-// ---- the levels
-
-// a wave's hooks into the log, its slots taken at once.  Every lane of the wave calls it.
-__device__ __forceinline__ void nh_log(int32_t hooked, NhCtl *ctl, int32_t *__restrict__ log, uint32_t cap)
-{
-    const unsigned long long m = __ballot(hooked >= 0);
-    if (!m) return;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lead = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == lead) base = atomicAdd(&ctl->log_n, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int32_t)base, lead);
-    if (hooked < 0) return;
-    const uint32_t slot = base + (uint32_t)__popcll(m & nuc_below(lane));
-    if (slot < cap) log[slot] = hooked;      // (cannot overflow: a triangle is hooked once, and only members are linked)
-}
+// ---- the levels: LINK
 
 // LINK: one lane per record of the level (the slots order[r_b .. r_b + r_n)); three links, each hook logged
 __global__ void k_nh_link(const uint4 *__restrict__ recs, const uint32_t *__restrict__ order, uint32_t r_b, uint32_t r_n, uint32_t n_rec,
@@ -254,159 +200,7 @@ __global__ void k_nh_link(const uint4 *__restrict__ recs, const uint32_t *__rest
             }
         }
     }
-    nh_log(h0, ctl, log, cap); nh_log(h1, ctl, log, cap); nh_log(h2, ctl, log, cap);
-}
-
-// arr[key] += 1 for every lane with key >= 0: the lanes of a wave that share a key add once, and what goes to `first` is
-// summed in *s_sum (LDS) for the workgroup's one global atomic.  Every lane of the wave calls it.
-__device__ __forceinline__ void nh_group_add(uint32_t *arr, int32_t key, int32_t first, uint32_t *s_sum)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const bool act = key >= 0;
-    unsigned long long m = __ballot(act);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        const int32_t lead = __shfl(key, src);
-        const unsigned long long same = __ballot(act && key == lead);
-        if (lane == src) {
-            if (lead == first) atomicAdd(s_sum, (uint32_t)__popcll(same));
-            else atomicAdd(arr + lead, (uint32_t)__popcll(same));
-        }
-        m &= ~same;
-    }
-}
-
-// the node (k, r) of root r, made by the first lane that asks for it at this level (levels descend: the atomicMin tells it)
-__device__ __forceinline__ void nh_claim(int32_t r, int32_t k, NhCtl *ctl, int32_t *claimk, int32_t *cur, const NhNodes &t, uint32_t cap)
-{
-    if (pload(claimk + r) <= k) return;      // (the word only falls: a stale read costs the atomic, no more)
-    if (atomicMin(claimk + r, k) <= k) return;
-    const uint32_t id = atomicAdd(&ctl->n_nodes, 1u);
-    if (id >= cap) return;                   // (cannot happen: every node has a hooked triangle of its own; the host checks n_nodes)
-    t.k[id] = k; t.rep[id] = r; t.par[id] = -1; t.size[id] = 0u; t.shell[id] = 0u;
-    const int32_t prev = cur[r];             // cur[r] belongs to this lane: r is a root, and only its claimer touches it in this launch
-    if (prev >= 0) t.par[prev] = (int32_t)id;    // the same root stood for a nucleus of a higher level: now a child
-    cur[r] = (int32_t)id;
-}
-
-// CLAIM (after the level's LINK; hooks nothing: a triangle read as a root is one.  Its walks still split the paths they pass).
-// seg[li] .. log_n is the level's segment of the log; mord[sh_b .. sh_b + sh_n) are the level's triangles.
-__global__ void k_nh_claim(int32_t k, uint32_t li, const uint32_t *__restrict__ mord, uint32_t sh_b, uint32_t sh_n, int32_t *parent,
-                           const int32_t *__restrict__ log, uint32_t *seg, NhCtl *ctl, int32_t *claimk, int32_t *cur, uint32_t *cnt,
-                           NhNodes t, uint32_t cap)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const uint32_t lb = seg[li];
-    uint32_t le = ctl->log_n;
-    if (le > cap) le = cap;
-    const uint32_t b0 = blockIdx.x * kBlock, stride = gridDim.x * kBlock;
-    if (b0 + threadIdx.x == 0) seg[li + 1] = le;                 // (read by later launches only)
-    const int lane = threadIdx.x & (kWave - 1);
-    if (threadIdx.x == 0) {                                      // the root this workgroup's first entry has
-        s_first = lb + b0 < le ? comp_find(parent, log[lb + b0]) : (b0 < sh_n ? comp_find(parent, (int32_t)mord[sh_b + b0]) : -1);
-        s_sum = 0u;
-    }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t base = lb + b0; base < le; base += stride) {   // (uniform per workgroup: the ballots see whole waves)
-        const uint32_t i = base + threadIdx.x;
-        int32_t r = -1;
-        uint32_t mine = 0;
-        if (i < le) {
-            const int32_t x = log[i];
-            r = comp_find(parent, x);
-            const uint32_t c = cnt[x];       // x is no root any more: nobody adds to cnt[x] now
-            if (r == first) mine = c;
-            else if (c) atomicAdd(cnt + r, c);
-        }
-        mine = nh_wave_sum(mine);
-        if (lane == 0 && mine) atomicAdd(&s_sum, mine);
-        unsigned long long m = __ballot(r >= 0);                 // one lane per distinct root of the wave asks for its node
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(r, src);
-            const unsigned long long same = __ballot(r == lead);
-            if (lane == src) nh_claim(lead, k, ctl, claimk, cur, t, cap);
-            m &= ~same;
-        }
-    }
-    for (uint32_t base = b0; base < sh_n; base += stride) {
-        const uint32_t j = base + threadIdx.x;
-        const int32_t r = j < sh_n ? comp_find(parent, (int32_t)mord[sh_b + j]) : -1;
-        nh_group_add(cnt, r, first, &s_sum);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(cnt + first, s_sum);
-}
-
-// ADOPT (after CLAIM: cur[] of this level's roots is settled)
-__global__ void k_nh_adopt(uint32_t li, const uint32_t *__restrict__ mord, uint32_t sh_b, uint32_t sh_n, const int32_t *parent,
-                           const int32_t *__restrict__ log, const uint32_t *__restrict__ seg, const int32_t *__restrict__ cur,
-                           const uint32_t *__restrict__ cnt, NhNodes t, int32_t *__restrict__ mnode)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const uint32_t lb = seg[li], le = seg[li + 1];
-    const uint32_t b0 = blockIdx.x * kBlock, stride = gridDim.x * kBlock;
-    if (threadIdx.x == 0) {                                      // the node this workgroup's first triangle goes to
-        s_first = b0 < sh_n ? cur[comp_find_ro(parent, (int32_t)mord[sh_b + b0])] : -1;
-        s_sum = 0u;
-    }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t i = lb + b0 + threadIdx.x; i < le; i += stride) {
-        const int32_t x = log[i];
-        const int32_t r = comp_find_ro(parent, x);
-        const int32_t nr = cur[r], nx = cur[x];
-        if (nr < 0) continue;
-        if (nx >= 0) t.par[nx] = nr;         // x was the root of a nucleus of a higher level
-        t.size[nr] = cnt[r];                 // (every writer stores the same word)
-    }
-    for (uint32_t base = b0; base < sh_n; base += stride) {      // (uniform per workgroup)
-        const uint32_t j = base + threadIdx.x;
-        int32_t nr = -1;
-        if (j < sh_n) {
-            const int32_t e = (int32_t)mord[sh_b + j];
-            const int32_t r = comp_find_ro(parent, e);
-            nr = cur[r];
-            mnode[e] = nr;
-            if (nr >= 0) t.size[nr] = cnt[r];
-        }
-        nh_group_add(t.shell, nr, first, &s_sum);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum && first >= 0) atomicAdd(t.shell + first, s_sum);
-}
-
-// ---- the tail: nodes into (k, rep) order
-__global__ void k_nh_node_keys(uint32_t n, NhNodes t, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = ((uint64_t)(uint32_t)t.k[i] << 32) | (uint32_t)t.rep[i];
-    vals[i] = i;
-}
-
-__global__ void k_nh_ranks(uint32_t n, const uint32_t *__restrict__ order, int32_t *__restrict__ rank)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j < n) rank[order[j]] = (int32_t)j;
-}
-
-__global__ void k_nh_nodes_out(uint32_t n, const uint32_t *__restrict__ order, const int32_t *__restrict__ rank, NhNodes t, NhNodes out, NhCtl *ctl)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    bool root = false;
-    if (j < n) {
-        const uint32_t i = order[j];
-        const int32_t p = t.par[i];
-        out.k[j] = t.k[i]; out.rep[j] = t.rep[i]; out.par[j] = p >= 0 ? rank[p] : -1;
-        out.size[j] = t.size[i]; out.shell[j] = t.shell[i];
-        root = p < 0;
-    }
-    const unsigned long long m = __ballot(root);
-    if ((threadIdx.x & (kWave - 1)) == 0 && m) atomicAdd(&ctl->n_roots, (uint32_t)__popcll(m));
+    forest_log_wave(h0, &ctl->f, log, cap); forest_log_wave(h1, &ctl->f, log, cap); forest_log_wave(h2, &ctl->f, log, cap);
 }
 
 // node[] in triangle order
@@ -423,23 +217,9 @@ __global__ void k_nh_tri_out(uint32_t n_tri, const int32_t *__restrict__ theta, 
     out[t] = nd;
 }
 
-// the most nodes on a path from a root down (parents have smaller numbers: every walk ends)
-__global__ void k_nh_depth(uint32_t n, const int32_t *__restrict__ par, NhCtl *ctl)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    int32_t d = 0;
-    if (j < n) {
-        d = 1;
-        for (int32_t c = (int32_t)j, a = par[j]; a >= 0 && a < c; c = a, a = par[a]) ++d;
-    }
-    for (int o = kWave / 2; o > 0; o >>= 1) { const int32_t other = __shfl_xor(d, o); d = other > d ? other : d; }
-    if ((threadIdx.x & (kWave - 1)) == 0 && d) atomicMax(&ctl->depth, d);
-}
-
 // ---- readers of the stored forest
 
-// komb_nucleus_hierarchy_labels: from node[t] up while the parent's level is still >= k (parents have smaller numbers:
-// every walk ends)
+// komb_nucleus_hierarchy_labels: from node[t] up while the parent's level is still >= k
 __global__ void k_nh_labels(uint32_t n_tri, int32_t k, const int32_t *__restrict__ tnode, uint32_t n, const int32_t *__restrict__ nk,
                             const int32_t *__restrict__ rep, const int32_t *__restrict__ par, const int32_t *__restrict__ size,
                             int32_t *__restrict__ label, int32_t *__restrict__ lsize)
@@ -449,7 +229,7 @@ __global__ void k_nh_labels(uint32_t n_tri, int32_t k, const int32_t *__restrict
     int32_t lab = -1, sz = 0;
     int32_t c = tnode[t];
     if (c >= 0 && (uint32_t)c < n && nk[c] >= k) {
-        for (int32_t a = par[c]; a >= 0 && a < c && nk[a] >= k; a = par[a]) c = a;
+        c = forest_walk_up(c, k, nk, par);
         lab = rep[c]; sz = size[c];
     }
     label[t] = lab; lsize[t] = sz;
@@ -540,7 +320,7 @@ int nh_labels_dev(komb_ctx *ctx, int32_t k, int32_t *d_label, int32_t *d_size)
     const int64_t T = ctx->nuc.n_tri;
     const int32_t *nodes = ctx->d_nh_nodes;
     const size_t c = (size_t)ctx->nh.cap;
-    k_nh_labels<<<nh_grid(T), kBlock, 0, ctx->stream>>>((uint32_t)T, k, ctx->d_nh_tnode, (uint32_t)ctx->nh.n_nodes, nodes, nodes + c, nodes + 2 * c,
+    k_nh_labels<<<forest_grid(T), kBlock, 0, ctx->stream>>>((uint32_t)T, k, ctx->d_nh_tnode, (uint32_t)ctx->nh.n_nodes, nodes, nodes + c, nodes + 2 * c,
                                                         nodes + 3 * c, d_label, d_size);
     KOMB_HIP(ctx, hipGetLastError());
     return KOMB_OK;
@@ -581,7 +361,7 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         DevBufs bufs(ctx);
         const uint32_t um = (uint32_t)m, uT = (uint32_t)T, uQ = (uint32_t)Q;
         const uint32_t levels = (uint32_t)res.theta_max + 1u;    // level numbers 0 .. levels - 1
-        const int bits = nh_bits(levels);
+        const int bits = forest_bits(levels);
         const uint32_t n_short = nh_opt_u32(ctx, "NUC_SHORT", kNhShort);      // (tests: every triangle through the wave / its lane)
         const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *theta = ctx->d_nuc_theta;
 
@@ -615,11 +395,11 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(NhCtl), s));
         KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
         KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
-        k_nh_rows<<<nh_grid(m), kBlock, 0, s>>>(eu, um, d_rs, d_re);
-        k_nh_tri<<<nh_grid(T + 1), kBlock, 0, s>>>(uT, (uint32_t)nv, o, ev, d_rs, d_re, theta, d_flag, parent, cnt, cur, claimk, d_ctl);
-        k_nh_tri_ptr<<<nh_grid(m + 1), kBlock, 0, s>>>(um, uT, o.j, tri_ptr);
+        k_nh_rows<<<forest_grid(m), kBlock, 0, s>>>(eu, um, d_rs, d_re);
+        k_nh_tri<<<forest_grid(T + 1), kBlock, 0, s>>>(uT, (uint32_t)nv, o, ev, d_rs, d_re, theta, d_flag, parent, cnt, cur, claimk, d_ctl);
+        k_nh_tri_ptr<<<forest_grid(m + 1), kBlock, 0, s>>>(um, uT, o.j, tri_ptr);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, T + 1));
-        k_nh_clq<<<nh_grid(T), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, theta, d_nm, d_ctl, n_short, st);
+        k_nh_clq<<<forest_grid(T), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, theta, d_nm, d_ctl, n_short, st);
         KOMB_HIP(ctx, hipGetLastError());
         NhCtl h;
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NhCtl)));       // the cursor, read once: it ends on the stored count or the run fails
@@ -631,7 +411,7 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         // ---- buckets: records by weight, members by theta; one table for the host
         uint32_t *mkeys = nullptr, *mkeys2 = nullptr, *mvals = nullptr, *mvals2 = nullptr, *d_tab = nullptr, *seg = nullptr;
         int32_t *log = nullptr;
-        NhNodes t{};
+        ForestNodes t{};
         KOMB_HIP(ctx, bufs.alloc(&mkeys, (size_t)nm));
         KOMB_HIP(ctx, bufs.alloc(&mkeys2, (size_t)nm));
         KOMB_HIP(ctx, bufs.alloc(&mvals, (size_t)nm));
@@ -647,12 +427,12 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         KOMB_HIP(ctx, bufs.alloc(&d_tab, tab_words));
         uint32_t *d_moff = d_tab, *d_roff = d_tab + levels + 1;
         KOMB_HIP(ctx, hipMemsetAsync(d_tab, 0, tab_words * sizeof(uint32_t), s));
-        k_nh_compact<<<nh_grid(T), kBlock, 0, s>>>(uT, theta, levels, d_pos, nm, mkeys, mvals);
+        k_nh_compact<<<forest_grid(T), kBlock, 0, s>>>(uT, theta, levels, d_pos, nm, mkeys, mvals);
         uint32_t *rsorted = nullptr, *order = nullptr, *msorted = nullptr, *mord = nullptr;
         KOMB_TRY(prim_sort_pairs_u32_u32(ctx, st.keys, rkeys2, st.idx, ridx2, Q, bits, &rsorted, &order));
-        k_nh_offsets<<<nh_grid(Q + 1), kBlock, 0, s>>>(uQ, rsorted, levels, d_roff);
+        forest_offsets(ctx, uQ, rsorted, levels, d_roff);
         KOMB_TRY(prim_sort_pairs_u32_u32(ctx, mkeys, mkeys2, mvals, mvals2, nm, bits, &msorted, &mord));
-        k_nh_offsets<<<nh_grid((int64_t)nm + 1), kBlock, 0, s>>>(nm, msorted, levels, d_moff);
+        forest_offsets(ctx, nm, msorted, levels, d_moff);
         KOMB_HIP(ctx, hipGetLastError());
         std::vector<uint32_t> tab(tab_words);
         KOMB_HIP(ctx, d2h(ctx, tab.data(), d_tab, tab_words * sizeof(uint32_t)));     // the one read before the loop
@@ -669,46 +449,35 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         KOMB_HIP(ctx, hipMemsetAsync(seg, 0, ((size_t)n_levels + 1) * sizeof(uint32_t), s));
 
         // ---- the levels, from theta_max down
+        const ForestState f{parent, log, claimk, cur, cnt, seg, mnode, t, &d_ctl->f, nm};
         uint32_t li = 0;
         for (int32_t k = (int32_t)levels - 1; k >= 1; --k) {                        // no read and no wait in this loop
             const uint32_t sh_b = moff[k], sh_n = moff[k + 1] - moff[k];
             const uint32_t r_b = roff[k], r_n = roff[k + 1] - roff[k];
             if (!sh_n) continue;                                                    // (a record of weight k has a triangle of theta k)
-            if (r_n) k_nh_link<<<nh_grid(r_n), kBlock, 0, s>>>(st.recs, order, r_b, r_n, uQ, uT, parent, d_ctl, log, nm);
-            const uint64_t hooks = 3ull * r_n < nm ? 3ull * r_n : nm;               // at most this many hooks at this level
-            const uint64_t work = hooks > sh_n ? hooks : sh_n;
-            const int g = (int)((work + kBlock - 1) / kBlock < (uint64_t)kNhStepGrid ? (work + kBlock - 1) / kBlock : (uint64_t)kNhStepGrid);
-            k_nh_claim<<<g > 0 ? g : 1, kBlock, 0, s>>>(k, li, mord, sh_b, sh_n, parent, log, seg, d_ctl, claimk, cur, cnt, t, nm);
-            k_nh_adopt<<<g > 0 ? g : 1, kBlock, 0, s>>>(li, mord, sh_b, sh_n, parent, log, seg, cur, cnt, t, mnode);
+            if (r_n) k_nh_link<<<forest_grid(r_n), kBlock, 0, s>>>(st.recs, order, r_b, r_n, uQ, uT, parent, d_ctl, log, nm);
+            forest_level(ctx, f, k, li, false, mord, sh_b, sh_n, 3ull * r_n < nm ? 3ull * r_n : nm);      // at most this many hooks at this level
             ++li;
         }
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NhCtl)));                          // the number of nodes sizes the tail
-        if (h.n_nodes < 1 || h.n_nodes > nm || h.log_n > nm || h.bad)
+        if (h.f.n_nodes < 1 || h.f.n_nodes > nm || h.f.log_n > nm || h.bad)
             KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_nucleus_hierarchy_run: inconsistent state (%u nodes, %u hooks, %u members, bad %u)",
-                      h.n_nodes, h.log_n, nm, h.bad);
+                      h.f.n_nodes, h.f.log_n, nm, h.bad);
 
         // ---- the tail
-        const uint32_t n = h.n_nodes;
+        const uint32_t n = h.f.n_nodes;
         int32_t *rank = cur;                                     // (cur[] has served when the ranks are made; nodes <= members <= triangles)
         cap_nodes = n;
         KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.nodes, 5 * cap_nodes * sizeof(int32_t)));
-        NhNodes out{fresh.nodes, fresh.nodes + cap_nodes, fresh.nodes + 2 * cap_nodes,
-                    (uint32_t *)fresh.nodes + 3 * cap_nodes, (uint32_t *)fresh.nodes + 4 * cap_nodes};
-        uint64_t *nkeys = nullptr, *nkeys2 = nullptr, *nsorted = nullptr;
-        uint32_t *norder = nullptr;
-        KOMB_HIP(ctx, bufs.alloc(&nkeys, (size_t)n));
-        KOMB_HIP(ctx, bufs.alloc(&nkeys2, (size_t)n));
-        k_nh_node_keys<<<nh_grid(n), kBlock, 0, s>>>(n, t, nkeys, mvals);           // (the members' sort has served: n <= nm)
-        KOMB_TRY(prim_sort_pairs_u64_u32(ctx, nkeys, nkeys2, mvals, mvals2, n, 32 + bits, &nsorted, &norder));
-        k_nh_ranks<<<nh_grid(n), kBlock, 0, s>>>(n, norder, rank);
-        k_nh_nodes_out<<<nh_grid(n), kBlock, 0, s>>>(n, norder, rank, t, out, d_ctl);
-        k_nh_depth<<<nh_grid(n), kBlock, 0, s>>>(n, out.par, d_ctl);
-        k_nh_tri_out<<<nh_grid(T), kBlock, 0, s>>>(uT, theta, mnode, rank, n, fresh.tnode);
+        ForestNodes out{fresh.nodes, fresh.nodes + cap_nodes, fresh.nodes + 2 * cap_nodes,
+                        (uint32_t *)fresh.nodes + 3 * cap_nodes, (uint32_t *)fresh.nodes + 4 * cap_nodes};
+        KOMB_TRY(forest_tail(ctx, bufs, f, n, bits, out, rank, nullptr, mvals, mvals2));   // (the members' sort has served: n <= nm)
+        k_nh_tri_out<<<forest_grid(T), kBlock, 0, s>>>(uT, theta, mnode, rank, n, fresh.tnode);
         res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NhCtl)));
-        res.n_nodes = (int64_t)n; res.n_roots = (int64_t)h.n_roots; res.depth = h.depth; res.n_members = (int64_t)nm;
+        res.n_nodes = (int64_t)n; res.n_roots = (int64_t)h.f.n_roots; res.depth = h.f.depth; res.n_members = (int64_t)nm;
     } else {
         if (T > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.tnode, 0xFF, (size_t)T * sizeof(int32_t), s));   // no clique: no nucleus
         res.ms = ctx->timer.stop(s);
@@ -760,7 +529,7 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
         KOMB_HIP(ctx, bufs.alloc(&d_flag, (size_t)T + 1));
         KOMB_HIP(ctx, bufs.alloc(&d_pos, (size_t)T + 1));
         KOMB_TRY(nh_labels_dev(ctx, k, d_label, d_size));
-        k_nh_rep_flag<<<nh_grid(T + 1), kBlock, 0, s>>>((uint32_t)T, d_label, d_flag);
+        k_nh_rep_flag<<<forest_grid(T + 1), kBlock, 0, s>>>((uint32_t)T, d_label, d_flag);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, T + 1));
         KOMB_HIP(ctx, hipGetLastError());
         uint32_t total = 0;
@@ -781,7 +550,7 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
         KOMB_HIP(ctx, bufs.alloc(&vuniq, n_keys));
         KOMB_HIP(ctx, bufs.alloc(&euniq, n_keys));
         KOMB_HIP(ctx, bufs.alloc(&d_out, 4 * (size_t)n_nuc));
-        k_nh_keys<<<nh_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_t_eu, ctx->d_t_ev,
+        k_nh_keys<<<forest_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_t_eu, ctx->d_t_ev,
                                                 (uint32_t)m, vkeys, ekeys);
         KOMB_HIP(ctx, hipGetLastError());
         int64_t n_v = 0, n_e = 0;
@@ -793,7 +562,7 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
             KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_nucleus_hierarchy_nuclei: inconsistent key counts (%lld vertices, %lld edges of %zu keys)",
                       (long long)n_v, (long long)n_e, n_keys);
         int32_t *o_rep = d_out, *o_tri = d_out + n_nuc, *o_edge = d_out + 2 * n_nuc, *o_vert = d_out + 3 * n_nuc;
-        k_nh_nuclei_out<<<nh_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, d_size, d_pos, (uint32_t)n_nuc, vuniq, (uint32_t)n_v, euniq, (uint32_t)n_e,
+        k_nh_nuclei_out<<<forest_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, d_size, d_pos, (uint32_t)n_nuc, vuniq, (uint32_t)n_v, euniq, (uint32_t)n_e,
                                                       o_rep, o_tri, o_edge, o_vert);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, hipStreamSynchronize(s));

@@ -112,11 +112,7 @@ __device__ __forceinline__ int32_t wave_min(int32_t v)
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
     return v;
 }
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
+// (wave_sum: common.h)
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
 {
     const int lane = lane_id();

@@ -132,3 +132,27 @@ def check_invariants(h, core_kind):
     assert np.array_equal(order, np.arange(n))
     if core_kind:
         assert (h["shell"] >= 1).all()
+
+
+# ---- graphs that both the CPU tests of this reference and the GPU tests use: (nv, raw pairs)
+
+STRIDE_ISOLATED = 2048 * 256 + 257                          # the most workgroups CLAIM / ADOPT get, 256 items each, and 257 more
+
+
+def strided_claim_graph():
+    """STRIDE_ISOLATED isolated vertices, then a K_4 on the last four ids: level 0 takes the whole grid, whose workgroups
+    0 and 1 go round a second time (256 items and 1) and meet roots that are not their first one's."""
+    n = STRIDE_ISOLATED
+    return n + 4, np.stack(np.triu_indices(4, 1), 1) + n
+
+
+def shell_first_graph():
+    """300 disjoint edges (level 1: 600 vertices but 300 hooks), two stars of 2 100 leaves whose hubs are joined to every
+    vertex of a K_5 and of a K_30: level 1 has more vertices than hooks, so its last workgroups take their first root from
+    the vertex list, and the hubs' rows (>= 2048 entries) are linked at two different core levels, 30 and 5."""
+    parts, off = [np.stack([np.arange(0, 600, 2), np.arange(1, 600, 2)], 1)], 600
+    for n in (5, 30):
+        hub, clique, leaves = off, off + 1 + np.arange(n), off + 1 + n + np.arange(2100)
+        parts += [np.stack(np.triu_indices(n, 1), 1) + off + 1, np.stack([np.full(n, hub), clique], 1), np.stack([np.full(2100, hub), leaves], 1)]
+        off += 1 + n + 2100
+    return off, np.concatenate(parts)

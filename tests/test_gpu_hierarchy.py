@@ -210,6 +210,39 @@ def test_long_rows(K):
         _check_both(K, nv, ids[uv])
 
 
+@pytest.mark.parametrize("nv", [255, 256, 257, 513])
+def test_isolated_vertices(K, nv):
+    """No edges, up to and past one and two workgroups of CLAIM / ADOPT: every vertex makes its own node, and only a
+    workgroup's first lane has the root whose counts are summed in LDS."""
+    with K.KombAccel() as a:
+        a.from_edges(nv, np.zeros((0, 2)))
+        nodes, node, info = _check_core(a, [0] * nv)
+        assert nodes["k"].tolist() == [0] * nv and nodes["rep"].tolist() == list(range(nv)) and nodes["parent"].tolist() == [-1] * nv
+        assert nodes["size"].tolist() == [1] * nv and nodes["shell"].tolist() == [1] * nv and node.tolist() == list(range(nv))
+        assert (info["n_nodes"], info["n_roots"], info["k_max"], info["depth"]) == (nv, nv, 0, 1)
+        _check_truss(a)
+
+
+def test_strided_claim(K):
+    """Level 0 takes the most workgroups CLAIM / ADOPT get, and the first two go round a second time."""
+    nv, uv = H.strided_claim_graph()
+    (cn, cnode, cinfo), (tn, _, _) = _check_both(K, nv, uv)
+    n = H.STRIDE_ISOLATED
+    assert (cinfo["n_nodes"], cinfo["n_roots"], cinfo["k_max"], cinfo["depth"]) == (n + 1, n + 1, 3, 1)
+    assert (cn["size"][:n] == 1).all() and (cn["shell"][:n] == 1).all() and (cn["size"][n], cn["shell"][n]) == (4, 4)
+    assert np.array_equal(cnode, np.minimum(np.arange(nv), n)) and tn["size"].tolist() == [4]
+
+
+def test_shell_before_hooks_and_heavy_rows_at_two_levels(K):
+    """A level with more vertices than hooks (workgroups whose first root comes from the vertex list), and rows of the
+    grid-wide class at two core levels (each level's rows queued behind the earlier levels'), ids in order and permuted."""
+    nv, uv = H.shell_first_graph()
+    for ids in (np.arange(nv), np.random.default_rng(12).permutation(nv)):
+        (cn, _, _), (tn, _, _) = _check_both(K, nv, ids[uv])
+        assert cn["k"].tolist() == [1] * 302 + [5, 30] and sorted(cn["size"].tolist()[:302]) == [2] * 300 + [2106, 2131]
+        assert sorted(tn["k"].tolist()) == [2] * 302 + [6, 31]
+
+
 @pytest.mark.parametrize("seed", [1, 2])
 def test_composite(K, seed):
     nv, uv = R.composite(K.gen_hug_edges, seed)

@@ -94,3 +94,37 @@ def test_composite(K, O):
     eu, ev = O.edge_list(rowptr, col)
     h = _check_truss(nv, eu, ev, O.trussness(rowptr, col))
     assert (h["shell"] == 0).any()                         # cliques joined by a bridge edge: a node that only merges
+
+
+def _core_and_truss(O, nv, uv):
+    rowptr, col = R.simple_csr(nv, uv)
+    hc = _check_core(rowptr, col, O.coreness(rowptr, col))
+    eu, ev = O.edge_list(rowptr, col)
+    return hc, _check_truss(nv, eu, ev, O.trussness(rowptr, col))
+
+
+@pytest.mark.parametrize("nv", [255, 256, 257, 513])
+def test_isolated_vertices(O, nv):
+    hc, ht = _core_and_truss(O, nv, np.zeros((0, 2), np.int64))
+    assert hc["k"].tolist() == [0] * nv and hc["rep"].tolist() == list(range(nv)) and hc["parent"].tolist() == [-1] * nv
+    assert hc["size"].tolist() == [1] * nv and hc["shell"].tolist() == [1] * nv and hc["node"].tolist() == list(range(nv))
+    assert len(ht["k"]) == 0 and ht["node"].tolist() == [-1] * nv
+
+
+def test_strided_claim_graph(O):
+    nv, uv = H.strided_claim_graph()
+    n = H.STRIDE_ISOLATED
+    hc, ht = _core_and_truss(O, nv, uv)
+    assert len(hc["k"]) == n + 1 and (hc["k"][:n] == 0).all() and (hc["size"][:n] == 1).all() and (hc["shell"][:n] == 1).all()
+    assert (hc["k"][n], hc["rep"][n], hc["parent"][n], hc["size"][n], hc["shell"][n]) == (3, n, -1, 4, 4)
+    assert np.array_equal(hc["node"], np.minimum(np.arange(nv), n))
+    assert {f: ht[f].tolist() for f in H.FIELDS} == {"k": [4], "rep": [n], "parent": [-1], "size": [4], "shell": [4]}
+
+
+def test_shell_first_graph(O):
+    nv, uv = H.shell_first_graph()
+    for ids in (np.arange(nv), np.random.default_rng(12).permutation(nv)):
+        hc, ht = _core_and_truss(O, nv, ids[uv])
+        k, size = hc["k"].tolist(), hc["size"].tolist()
+        assert k == [1] * 302 + [5, 30] and sorted(size[:302]) == [2] * 300 + [2106, 2131] and sorted(size[302:]) == [6, 31]
+        assert sorted(ht["k"].tolist()) == [2] * 302 + [6, 31]
