@@ -116,7 +116,7 @@ int         komb_abi_version(void);
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
  * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
- * (komb_max_clique_run, below), and the
+ * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -553,6 +553,52 @@ int komb_max_clique_fetch(komb_ctx *ctx, int32_t *count /*[nv]*/, int32_t *witne
 int komb_max_clique_list(komb_ctx *ctx, int64_t cap, int64_t *n_cliques, int32_t *verts /*[cap * omega]*/);
 int komb_max_clique_info(komb_ctx *ctx, int32_t *omega, int32_t *upper, int32_t *flags, int32_t *t_max, int64_t *n_max_cliques,
                          int64_t *n_roots, int64_t *nodes, double *ms);   /* any may be NULL */
+
+/* ---- clique census: exact k-clique counts for every k ---------------------- */
+/* What lies between the triangle and 4-clique counts of komb_nucleus_info and the maximum cliques above: the number of k-cliques
+ * of H for every k of a window, and the k-cliques through every vertex for one k.  H, CLIQUE and t_max are those of the
+ * maximum-clique search: the last COMPLETE k-truss result on the resident graph, whole graph or vmask run alike.
+ * komb_clique_census_run(ctx, k_lo, k_hi, k_local, budget) computes total[k] = the number of k-cliques of H for every k in
+ * [k_lo, k_hi] and, if k_local != 0, local[v] = the number of k_local-cliques of H that contain vertex v.  2 <= k_lo <= k_hi;
+ * k_hi = -1 means t_max, and a k_hi above t_max runs as t_max, for no clique has more than t_max vertices -- but never below
+ * k_lo, so the window always has an entry (a window that lies above t_max is all zeros); komb_clique_census_info reports the
+ * k_hi the run used.  k_local is 0 or lies in [k_lo, k_hi] as used.  Anything else is KOMB_ERR_ARG.  A clique of >= k_lo
+ * vertices uses only edges of trussness >= k_lo, so a high k_lo is cheap on a large graph.
+ * Every count is a uint64_t and SATURATES: an entry is exactly min(the true value, 2^64 - 1).  Saturating adds of non-negative
+ * numbers commute, so every output of a complete run is unique: nothing depends on the run, on an option or on scheduling.
+ * The cliques are not enumerated but counted by pivoting (Jain and Seshadhri, WSDM 2020) from every
+ * canonical edge (a, b) as the two smallest ids of a clique.  A NODE is one candidate set evaluated, a root's own included.
+ * budget caps the nodes of the run exactly as komb_max_clique_run's does: 0 means the default, 2^30; a negative value is
+ * KOMB_ERR_ARG; a value above 2^31 - 1 - KOMB_MAXCLQ_OVERSHOOT runs as that; nodes <= budget + KOMB_MAXCLQ_OVERSHOOT always.
+ * flags: KOMB_CENSUS_COMPLETE -- the budget did not run out; KOMB_CENSUS_SATURATED -- some total or local entry equals
+ * 2^64 - 1.  Without COMPLETE every entry is a lower bound of the true value: every clique counted is one, and none is counted
+ * twice.
+ * komb_clique_census_fetch: total[k_hi - k_lo + 1], entry i for k = k_lo + i, and local[nv].  Either may be NULL; local given
+ * after a run with k_local == 0 is KOMB_ERR_STATE.
+ * komb_clique_census_info: the window and k_local of the run; t_max; omega = the largest k of the window with total[k] > 0, 0
+ * if there is none -- it is the clique number of H only when COMPLETE is set and k_hi reached t_max (a window that stops below
+ * t_max, or a budget that ran out, sees only part of the cliques); flags; max_candidates = the largest candidate set of a root
+ * at trussness >= k_lo; n_roots = the canonical edges whose subproblem was opened; nodes = the nodes spent; ms = the device time
+ * of the run on the context's HIP-event timer.  Any pointer may be NULL.
+ * H without an edge: every total 0, every local 0, omega = t_max = 0, flags = 1.
+ * No context or no graph loaded: KOMB_ERR_ARG, nothing is written.  Without a completed k-truss result on this graph, after
+ * komb_truss_run_slice / a sharded run that materialised only part of the canonical edges, after komb_truss_unprepare, fetch /
+ * info before a run: KOMB_ERR_STATE.  A root edge with more than 4096 candidates of trussness >= k_lo: KOMB_ERR_LIMIT, checked
+ * before anything is counted.  A pool failure: KOMB_ERR_NOMEM.
+ * The result lives in storage of its own, installed when a run has succeeded: a refused or failed run leaves the previous result
+ * readable.  It describes one k-truss result: whatever replaces or drops that result -- a new k-truss run of any kind,
+ * komb_truss_unprepare, a graph load -- drops it too.  No other call changes or drops it; a run changes no other result, no
+ * komb_stats field and not the resident k-truss preparation.  Options (none changes a result):
+ * CENSUS_LDS=<n>, 0 .. 512 (default 512): the largest candidate set whose bit matrix lives in LDS -- larger ones use the
+ * workgroup's slot of global scratch, 0 sends everything there; CENSUS_PIVOT=first|max (default max): the pivot of a node is
+ * its first candidate, or the one with the most neighbours among the candidates; CENSUS_DEBUG=1 prints one stderr line with the
+ * counts, the nodes and the device time. */
+#define KOMB_CENSUS_COMPLETE  1
+#define KOMB_CENSUS_SATURATED 2
+int komb_clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local, int64_t budget);
+int komb_clique_census_fetch(komb_ctx *ctx, uint64_t *total /*[k_hi - k_lo + 1]*/, uint64_t *local /*[nv]*/);   /* either may be NULL */
+int komb_clique_census_info(komb_ctx *ctx, int32_t *k_lo, int32_t *k_hi, int32_t *k_local, int32_t *t_max, int32_t *omega,
+                            int32_t *flags, int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms);   /* any may be NULL */
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

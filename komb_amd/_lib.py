@@ -56,6 +56,7 @@ KOMB_DENSEST_CORE, KOMB_DENSEST_PREFIX = 0, 1
 KOMB_SC_OUTLIER, KOMB_SC_HUB, KOMB_SC_BORDER, KOMB_SC_CORE = 0, 1, 2, 3
 KOMB_MAXCLQ_EXACT, KOMB_MAXCLQ_ENUMERATED, KOMB_MAXCLQ_LISTED = 1, 2, 4
 KOMB_MAXCLQ_OVERSHOOT = 262144
+KOMB_CENSUS_COMPLETE, KOMB_CENSUS_SATURATED = 1, 2
 
 
 # every symbol include/komb_accel.h declares: name -> (restype, argtypes)
@@ -137,6 +138,10 @@ SIGNATURES = {
     "komb_max_clique_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                     ctypes.POINTER(ctypes.c_double)]),
+    "komb_clique_census_run": (_i32, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i64]),
+    "komb_clique_census_fetch": (_i32, [_vp, _vp, _vp]),
+    "komb_clique_census_info": (_i32, [_vp] + [ctypes.POINTER(ctypes.c_int32)] * 7 + [ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                       ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

@@ -42,7 +42,8 @@ FORWARD_ENV_OPTIONS = False
 OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_DEFER_CHUNKS", "TAIL", "CORE_TAIL", "INDEX",
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
-                "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "POISON")
+                "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "CENSUS_LDS", "CENSUS_PIVOT",
+                "CENSUS_DEBUG", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -55,6 +56,13 @@ def _out_i32(n):
 
 def _out_f64(n):
     return np.full(n, np.nan, dtype=np.float64)
+
+
+SENTINEL_U64 = 0xA5A5A5A5A5A5A5A5
+
+
+def _out_u64(n):
+    return np.full(n, SENTINEL_U64, dtype=np.uint64)
 
 
 class KombAccel:
@@ -614,6 +622,39 @@ class KombAccel:
         self.max_clique_run(budget)
         count, witness = self.max_clique_fetch()
         return self.max_clique_info(), count, witness
+
+    # ---- clique census: exact k-clique counts of the last k-truss result for every k of a window (include/komb_accel.h)
+    CLIQUE_CENSUS_INFO_FIELDS = ("k_lo", "k_hi", "k_local", "t_max", "omega", "flags", "max_candidates", "n_roots", "nodes", "ms")
+
+    def clique_census_run(self, k_lo=2, k_hi=-1, k_local=0, budget=0):
+        """Needs a complete k-truss result on this graph.  k_hi = -1: up to t_max; k_local: 0, or the size whose cliques are
+        counted per vertex; budget: the node cap of the run, 0 for the default."""
+        self._sync_env_options()
+        self._check(self._lib.komb_clique_census_run(self._ctx, k_lo, k_hi, k_local, budget))
+
+    def clique_census_info(self):
+        """{"k_lo", "k_hi", "k_local", "t_max", "omega", "flags", "max_candidates", "n_roots", "nodes", "ms"} of the last
+        komb_clique_census_run; k_hi is the one the run used."""
+        i32 = [ctypes.c_int32() for _ in range(7)]
+        i64 = [ctypes.c_int64() for _ in range(2)]
+        ms = ctypes.c_double()
+        self._check(self._lib.komb_clique_census_info(self._ctx, *(ctypes.byref(x) for x in i32 + i64), ctypes.byref(ms)))
+        return dict(zip(self.CLIQUE_CENSUS_INFO_FIELDS, [x.value for x in i32 + i64] + [ms.value]))
+
+    def clique_census_fetch(self):
+        """(total uint64[k_hi - k_lo + 1], local uint64[nv] or None): the k-cliques for k = k_lo .. k_hi and, after a run with
+        a k_local, the k_local-cliques through every vertex; every entry saturates at 2^64 - 1."""
+        info = self.clique_census_info()
+        total = _out_u64(info["k_hi"] - info["k_lo"] + 1)
+        local = _out_u64(max(self.nv, 0)) if info["k_local"] else None
+        self._check(self._lib.komb_clique_census_fetch(self._ctx, ptr(total), ptr(local)))
+        return total, local
+
+    def run_clique_census(self, k_lo=2, k_hi=-1, k_local=0, budget=0):
+        """(total, local, info) of a clique census of the last k-truss result."""
+        self.clique_census_run(k_lo, k_hi, k_local, budget)
+        total, local = self.clique_census_fetch()
+        return total, local, self.clique_census_info()
 
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):

@@ -573,6 +573,48 @@ int komb_max_clique_info(komb_ctx *ctx, int32_t *omega, int32_t *upper, int32_t 
     return KOMB_OK;
 }
 
+int komb_clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local, int64_t budget)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_census_run");
+    if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_census_run: bad node budget %lld", (long long)budget);
+    if (k_lo < 2 || (k_hi != -1 && k_hi < k_lo) || k_local < 0)
+        KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_census_run: bad window k_lo %d, k_hi %d, k_local %d", (int)k_lo, (int)k_hi, (int)k_local);
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    return clique_census_run(ctx, k_lo, k_hi, k_local, budget);
+}
+
+int komb_clique_census_fetch(komb_ctx *ctx, uint64_t *total, uint64_t *local)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_census_fetch");
+    if (!ctx->cc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_fetch: no clique census of the current k-truss result");
+    if (local && ctx->cc.k_local == 0) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_fetch: the census ran without a k_local");
+    if (ctx->nv > 0 && local) KOMB_HIP(ctx, staged_copy(ctx, local, ctx->d_cc_local, (size_t)ctx->nv * sizeof(uint64_t), false));
+    if (total) memcpy(total, ctx->cc.total.data(), ctx->cc.total.size() * sizeof(uint64_t));
+    return KOMB_OK;
+}
+
+int komb_clique_census_info(komb_ctx *ctx, int32_t *k_lo, int32_t *k_hi, int32_t *k_local, int32_t *t_max, int32_t *omega, int32_t *flags,
+                            int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_census_info");
+    if (!ctx->cc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_info: no clique census of the current k-truss result");
+    const komb_ctx::CliqueCensus &r = ctx->cc;
+    if (k_lo) *k_lo = r.k_lo;
+    if (k_hi) *k_hi = r.k_hi;
+    if (k_local) *k_local = r.k_local;
+    if (t_max) *t_max = r.t_max;
+    if (omega) *omega = r.omega;
+    if (flags) *flags = r.flags;
+    if (max_candidates) *max_candidates = r.max_p;
+    if (n_roots) *n_roots = r.n_roots;
+    if (nodes) *nodes = r.nodes;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_nucleus_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_run");

@@ -388,6 +388,17 @@ struct komb_ctx {
     } mc;
     bool mc_done = false;
 
+    // ---- clique census (clique_census.hip): the per-vertex counts in a pool block of their own (only with a k_local), the totals on
+    // the host; they describe the k-truss result they were computed from and are dropped with it (truss_free)
+    unsigned long long *d_cc_local = nullptr;   // [nv] k_local-cliques through the vertex, saturating
+    struct CliqueCensus {
+        int32_t k_lo = 0, k_hi = 0, k_local = 0, t_max = 0, omega = 0, flags = 0, max_p = 0;
+        int64_t n_roots = 0, nodes = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        std::vector<uint64_t> total;         // [k_hi - k_lo + 1] k-cliques, saturating
+    } cc;
+    bool cc_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                      // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -597,6 +608,9 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
 void nucleus_hierarchy_drop(komb_ctx *ctx);                   // nucleus_hierarchy.hip: the result goes with the nucleus result it indexes
 int max_clique_run(komb_ctx *ctx, int64_t budget);            // max_clique.hip: the k-truss result it needs and the budget checked by the caller
 void max_clique_drop(komb_ctx *ctx);                          // max_clique.hip: the result goes with the k-truss result it describes
+// clique_census.hip: the k-truss result it needs, the budget's sign and 2 <= k_lo checked by the caller, the rest of the window here (it needs t_max)
+int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local, int64_t budget);
+void clique_census_drop(komb_ctx *ctx);                       // clique_census.hip: the result goes with the k-truss result it describes
 int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);

@@ -282,6 +282,7 @@ void truss_free(komb_ctx *ctx)
     structural_drop(ctx);                    // (and the structural clustering's similar[]; its d and sim_deg are this result's)
     nucleus_drop(ctx);                       // (and the nucleus decomposition's triangles and edge_theta[])
     max_clique_drop(ctx);                    // (and the maximum cliques: they are this result's)
+    clique_census_drop(ctx);                 // (and the clique census)
     if (ctx->t_own_edges) { ctx->pool.put(ctx->d_t_eu); ctx->pool.put(ctx->d_t_ev); }
     ctx->pool.put(ctx->d_t_truss);
     ctx->pool.put(ctx->d_t_sup);

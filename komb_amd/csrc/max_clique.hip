@@ -8,6 +8,7 @@
 // A clique is searched from its ROOT, the canonical edge (a, b) of its two smallest ids: its other vertices are in
 // P = {c > b : (a, c) and (b, c) in H, both of trussness >= need}, where need is the size a clique must have to matter (the
 // search: best + 1; the enumeration: omega).  One wavefront owns one root at a time:
+//   (P and the matrix are made by clique_root_dev.h, which the clique census shares.)
 //   * P is cut from the tail of row a behind (a, b) and row b: the shorter is walked 64 entries at a time, the other bisected.
 //   * The |P| x |P| adjacency (edges of trussness >= need only) becomes a bit matrix, rows of W = ceil(|P| / 64) 64-bit words,
 //     in LDS up to MAXCLQ_LDS candidates and in the workgroup's slot of global scratch above.  Lane w owns word w of every row
@@ -27,12 +28,11 @@
 //     host after the launch.  A stale best only costs nodes.
 //   * nodes: every wave adds its nodes to one counter in batches of at most 256 and reads the counter at every node; once it has
 //     reached the budget the wave stops.  The overshoot is at most 256 per wave (KOMB_MAXCLQ_OVERSHOOT in all).
-// The launches of a run: k_mc_rows, k_mc_tmax; then per phase (seed, search, enumeration) k_mc_search in count mode (the
+// The launches of a run: k_clq_rows, k_mc_tmax; then per phase (seed, search, enumeration) k_mc_search in count mode (the
 // largest |P|, which sizes the scratch slots and the LDS) and in the phase's mode; k_mc_verify on the witness; k_mc_mark when
 // the counts are the witness' own.  No workgroup waits for another; every loop runs over a row part, a candidate set or a
 // stack that is bounded before it starts, and the node counter bounds the search as a whole.
-#include "common.h"
-#include "nucleus_search_dev.h"
+#include "clique_root_dev.h"
 
 #include <algorithm>
 
@@ -43,7 +43,6 @@ namespace {
 constexpr int kMcGrid = 1024;                         // wavefronts (workgroups of one) of a launch
 constexpr uint32_t kMcBatch = 256;                    // nodes a wave adds to the counter at once, at most
 static_assert((long long)kMcGrid * kMcBatch == KOMB_MAXCLQ_OVERSHOOT, "the documented overshoot");
-constexpr uint32_t kMcMaxCand = 4096;                 // candidates of one root: one 64-bit word per lane
 constexpr uint32_t kMcLdsCand = 512;                  // default and largest MAXCLQ_LDS: 512 x 8 words = 32 KiB
 constexpr size_t kMcLdsBytes = 56u << 10;             // LDS of a workgroup (below the 64 KiB a launch gets without asking)
 constexpr size_t kMcScratchBytes = 512ull << 20;      // all scratch slots of a launch together
@@ -87,15 +86,6 @@ struct McArgs {
     uint32_t omega;
 };
 
-__global__ void k_mc_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= m) return;
-    const int32_t u = eu[j];
-    if (j == 0 || eu[j - 1] != u) rs[u] = j;
-    if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
-}
-
 __global__ void k_mc_tmax(const int32_t *__restrict__ tr, uint32_t m, McCtl *ctl, uint32_t best0)
 {
     int32_t hi = 0;
@@ -103,28 +93,6 @@ __global__ void k_mc_tmax(const int32_t *__restrict__ tr, uint32_t m, McCtl *ctl
     for (int off = kWave / 2; off > 0; off >>= 1) { const int32_t other = __shfl_xor(hi, off); hi = other > hi ? other : hi; }
     if ((threadIdx.x & (kWave - 1)) == 0 && hi > 0) atomicMax(&ctl->t_max, (uint32_t)hi);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&ctl->best, best0);
-}
-
-__device__ __forceinline__ unsigned long long mc_shfl64(unsigned long long x, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int32_t)(uint32_t)x, src), hi = (uint32_t)__shfl((int32_t)(uint32_t)(x >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ int mc_sum(int x)
-{
-    for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
-// the first position of [lo, hi) whose entry is not below x
-__device__ __forceinline__ uint32_t mc_lower(const int32_t *__restrict__ a, int32_t x, uint32_t lo, uint32_t hi)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 __device__ __forceinline__ uint32_t mc_best(McCtl *ctl) { return __hip_atomic_load(&ctl->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -142,37 +110,15 @@ __device__ __forceinline__ void mc_flush(McCtl *ctl, McWave &w, int lane)
 __device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned long long *smem, McWave &w, int lane)
 {
     McCtl *ctl = A.ctl;
-    const int32_t *__restrict__ ev = A.ev;
-    const int32_t *__restrict__ tr = A.tr;
-    const int32_t a = A.eu[rj], b = ev[rj];
-    // ---- P: the shorter of (row a behind rj, row b) is walked, the other bisected; both ascending, so P is
-    const uint32_t ab = rj + 1, ae = A.re[a], bb = A.rs[b], be = A.re[b];
-    const bool walk_a = ae - ab <= be - bb;
-    const uint32_t it = walk_a ? ab : bb, len = walk_a ? ae - ab : be - bb, lo = walk_a ? bb : ab, hi = walk_a ? be : ae;
+    const ClqGraph G{A.eu, A.ev, A.tr, A.rs, A.re};
+    const int32_t a = A.eu[rj], b = A.ev[rj];
     unsigned char *slot = A.scratch + (size_t)blockIdx.x * A.slot_bytes;
     int32_t *P = (int32_t *)slot;
     const bool fill = A.mode != MC_COUNT;
-    uint32_t n = 0;
-    if (hi > lo)
-        for (uint32_t x0 = it; x0 < it + len; x0 += kWave) {
-            const uint32_t x = x0 + (uint32_t)lane;
-            bool ok = false;
-            int32_t c = 0;
-            if (x < it + len && (uint32_t)tr[x] >= need) {
-                c = ev[x];
-                const uint32_t hit = nuc_find(ev, c, lo, hi);
-                ok = hit != kNucNone && (uint32_t)tr[hit] >= need;
-            }
-            const unsigned long long hits = __ballot(ok);
-            if (ok && fill) {
-                const uint32_t pos = n + (uint32_t)__popcll(hits & nuc_below(lane));
-                if (pos < A.cap_p) P[pos] = c;
-            }
-            n += (uint32_t)__popcll(hits);
-        }
+    const uint32_t n = clq_cut(G, rj, need, P, A.cap_p, fill, lane);
     if (!fill) { w.max_p = n > w.max_p ? n : w.max_p; return; }
     ++w.roots;
-    if (n > A.cap_p || n > kMcMaxCand) { if (lane == 0) ctl->bad = 1u; return; }   // (the count launch saw every root with a need not above this one)
+    if (n > A.cap_p || n > kClqMaxCand) { if (lane == 0) ctl->bad = 1u; return; }   // (the count launch saw every root with a need not above this one)
     if (n + 2u < (A.mode == MC_ENUM ? A.omega : mc_best(ctl) + 1u)) {            // too few candidates: closed at once, one node, no matrix
         if (w.nodes >= kMcBatch) mc_flush(ctl, w, lane);
         ++w.nodes;
@@ -185,39 +131,7 @@ __device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned lo
     const bool stk_lds = in_lds && A.lds_levels > 0;
     unsigned long long *stk = stk_lds ? smem + A.lds_off_stk : (unsigned long long *)(slot + A.off_stk);
     const uint32_t levels = stk_lds ? A.lds_levels : A.levels;
-    __threadfence();                                     // (P: written by some lanes, read by all)
-    __syncthreads();
-    // ---- the bit matrix: bit j of row i <=> P[i] and P[j] are joined by an edge of trussness >= need
-    if (n > 0) {                                         // (a single candidate still needs its zero row)
-        for (uint32_t i = (uint32_t)lane; i < n * W; i += kWave) mat[i] = 0ull;
-        __threadfence();
-        __syncthreads();
-        uint32_t *m32 = (uint32_t *)mat;
-        const int32_t p_last = P[n - 1];
-        for (uint32_t i = 0; i + 1 < n; ++i) {
-            const int32_t c = P[i];
-            const uint32_t ce = A.re[c];
-            const uint32_t cs = mc_lower(ev, P[i + 1], A.rs[c], ce);   // (row c is above c; what is below P[i + 1] is not in P)
-            for (uint32_t x0 = cs; x0 < ce; x0 += kWave) {
-                const uint32_t x = x0 + (uint32_t)lane;
-                bool past = false;
-                if (x < ce) {
-                    const int32_t dd = ev[x];
-                    if (dd > p_last) past = true;
-                    else if ((uint32_t)tr[x] >= need) {
-                        const uint32_t pos = mc_lower(P, dd, i + 1, n);
-                        if (pos < n && P[pos] == dd) {
-                            atomicOr(m32 + ((size_t)i * W * 2 + (pos >> 5)), 1u << (pos & 31u));
-                            atomicOr(m32 + ((size_t)pos * W * 2 + (i >> 5)), 1u << (i & 31u));
-                        }
-                    }
-                }
-                if (__any(past)) break;
-            }
-        }
-        __threadfence();                                 // (the atomics went to L2: the rows are read with plain loads from here on)
-        __syncthreads();
-    }
+    clq_matrix(G, need, P, n, W, mat, lane);
     // ---- the search
     const bool mine = (uint32_t)lane < W;
     if (mine) {
@@ -230,7 +144,7 @@ __device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned lo
         if (mc_nodes(ctl) + w.nodes >= A.budget) { w.stop = true; break; }
         ++w.nodes;
         unsigned long long R = mine ? stk[(size_t)d * W + lane] : 0ull;
-        const int cnt = mc_sum(__popcll(R));
+        const int cnt = clq_sum(__popcll(R));
         const int s = (int)d + 2;
         const uint32_t best = mc_best(ctl);
         bool pop = false;
@@ -241,7 +155,7 @@ __device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned lo
                 if ((uint32_t)s == A.omega) {                        // a maximum clique: a, b and the d chosen candidates
                     unsigned long long idx = 0;
                     if (lane == 0) idx = atomicAdd(&ctl->n_cliques, 1ull);
-                    idx = mc_shfl64(idx, 0);
+                    idx = clq_shfl64(idx, 0);
                     const bool keep = idx < A.list_cap;
                     for (int i = lane; i < s; i += kWave) {
                         const int32_t v = i == 0 ? a : (i == 1 ? b : P[cur[i - 2]]);
@@ -266,7 +180,7 @@ __device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned lo
                     const unsigned long long nz = __ballot(Q != 0ull);
                     if (!nz) break;
                     const int src = __ffsll((long long)nz) - 1;
-                    const unsigned long long word = mc_shfl64(Q, src);
+                    const unsigned long long word = clq_shfl64(Q, src);
                     const int bit = __ffsll((long long)word) - 1;
                     const uint32_t v = (uint32_t)src * 64u + (uint32_t)bit;
                     if (mine) Q &= ~mat[(size_t)v * W + lane];
@@ -278,7 +192,7 @@ __device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned lo
         if (!pop) {
             const unsigned long long nz = __ballot(U != 0ull);       // (not empty: cnt > 0, or the colouring left something)
             const int src = __ffsll((long long)nz) - 1;
-            const unsigned long long word = mc_shfl64(U, src);
+            const unsigned long long word = clq_shfl64(U, src);
             const int bit = __ffsll((long long)word) - 1;
             const uint32_t v = (uint32_t)src * 64u + (uint32_t)bit;
             if (d + 1 >= levels) { if (lane == 0) ctl->bad = 1u; break; }   // (a clique of more than t_max vertices)
@@ -376,9 +290,9 @@ int McRun::launch(int mode, uint32_t need, int grid_cap)
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(McCtl)));
     const uint32_t max_p = h.max_p;
-    if (max_p > kMcMaxCand)
+    if (max_p > kClqMaxCand)
         KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_max_clique_run: a root edge has %u candidates of trussness >= %u; the limit is %u (one 64-bit word per lane)",
-                  max_p, need, kMcMaxCand);
+                  max_p, need, kClqMaxCand);
     const uint32_t depth = t_max >= 2 ? t_max - 2 : 0;
     const uint32_t w_max = std::max<uint32_t>(1u, (max_p + 63u) >> 6);
     A.cap_p = max_p;
@@ -469,7 +383,7 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
         KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
         const uint32_t um = (uint32_t)m;
         const int g = (int)((m + kBlock - 1) / kBlock);
-        k_mc_rows<<<g, kBlock, 0, s>>>(ctx->d_t_eu, um, d_rs, d_re);
+        k_clq_rows<<<g, kBlock, 0, s>>>(ctx->d_t_eu, um, d_rs, d_re);
         k_mc_tmax<<<g < 1024 ? g : 1024, kBlock, 0, s>>>(ctx->d_t_truss, um, A.ctl, 1u);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &run.h, A.ctl, sizeof(McCtl)));

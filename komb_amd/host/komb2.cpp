@@ -89,6 +89,13 @@
 //                       -- the unitigs in VID order that lie in at least one maximum clique, with their number (1 on the
 //                       witness when the cliques were not enumerated).  0 is off; anything else is a usage error.  VIDs depend
 //                       on -t, so only the cliques as sets of Names compare between runs.  Nothing else changes.
+//   KOMB_CLIQUE_CENSUS=<k_lo>:<k_hi>[:<k_local>]  with KOMB_TRUSS=1: also write, after the truss stage, the clique census of its
+//                       result (komb_clique_census_run with the default node budget): the number of k-cliques for every k of
+//                       the window; <k_hi> may be "max" (the largest trussness).  clique_census.tsv: a header comment
+//                       "# k_lo <n> k_hi <n> k_local <n> flags <n> omega <n> nodes <n> roots <n>" (k_hi as used), then one
+//                       line k<TAB>count per k.  With a <k_local> also clique_census_unitigs.tsv: #Name, Count -- every unitig
+//                       in VID order with the number of k_local-cliques it lies in.  Counts saturate at 2^64 - 1 (flags 2).
+//                       0 or empty is off; anything else that is not of that form is a usage error.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -862,6 +869,39 @@ void write_max_clique(komb_ctx *ctx, int64_t budget, const std::string &outdir, 
     fclose(fp);
 }
 
+// KOMB_CLIQUE_CENSUS: komb_clique_census_run on the truss stage's result as one or two tables (the sizes ascending, the unitigs in VID order)
+void write_clique_census(komb_ctx *ctx, const int32_t window[3], const std::string &outdir, const Names &names, int64_t nv, int threads)
+{
+    int rc = komb_clique_census_run(ctx, window[0], window[1], window[2], 0);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_census_run", rc);
+    int32_t k_lo = 0, k_hi = 0, k_local = 0, omega = 0, flags = 0;
+    int64_t roots = 0, nodes = 0;
+    rc = komb_clique_census_info(ctx, &k_lo, &k_hi, &k_local, nullptr, &omega, &flags, nullptr, &roots, &nodes, nullptr);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_census_info", rc);
+    std::vector<uint64_t> total((size_t)(k_hi - k_lo + 1)), local(k_local ? (size_t)nv : 0);
+    rc = komb_clique_census_fetch(ctx, total.data(), k_local ? local.data() : nullptr);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_census_fetch", rc);
+    std::string path = outdir + "/clique_census.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "# k_lo %d k_hi %d k_local %d flags %d omega %d nodes %lld roots %lld\n", (int)k_lo, (int)k_hi, (int)k_local, (int)flags, (int)omega,
+            (long long)nodes, (long long)roots);
+    for (size_t i = 0; i < total.size(); ++i) fprintf(fp, "%d\t%llu\n", (int)k_lo + (int)i, (unsigned long long)total[i]);
+    fclose(fp);
+    if (!k_local) return;
+    path = outdir + "/clique_census_unitigs.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Name\tCount\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        buf.append(names.name[(size_t)i]);
+        char tmp[32];
+        const int len = snprintf(tmp, sizeof(tmp), "\t%llu\n", (unsigned long long)local[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_NUCLEUS_HIERARCHY: komb_nucleus_hierarchy_run on the nucleus decomposition of the truss stage's result as two tables (nodes in
 // node order, member triangles in triangle order)
 void write_nucleus_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads, bool have_nucleus)
@@ -1311,6 +1351,36 @@ int main(int argc, const char **argv)
         if (mc_budget == 1) mc_budget = 0;                 // (1: on, with the library's default budget)
     }
 
+    // the clique census of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1):
+    // KOMB_CLIQUE_CENSUS=<k_lo>:<k_hi>[:<k_local>], <k_hi> a number or "max"
+    const char *cc_env = getenv("KOMB_CLIQUE_CENSUS");
+    const bool cc_on = cc_env && *cc_env && strcmp(cc_env, "0") != 0;
+    int32_t cc_window[3] = {0, 0, 0};
+    if (cc_on) {
+        auto number = [](const char *&q) -> long long {   // a decimal number of at least 2 at q, -2 if there is none
+            if (*q < '0' || *q > '9') return -2;
+            char *end = nullptr;
+            errno = 0;
+            const long long v = strtoll(q, &end, 10);
+            q = end;
+            return errno || v < 2 || v > 0x7FFFFFFF ? -2 : v;
+        };
+        const char *q = cc_env;
+        const long long lo = number(q);
+        long long hi = -2, loc = 0;
+        if (*q == ':') {
+            ++q;
+            if (strncmp(q, "max", 3) == 0) { hi = -1; q += 3; }
+            else hi = number(q);
+            if (*q == ':') { ++q; loc = number(q); }
+        }
+        if (*q || lo == -2 || hi == -2 || (hi != -1 && hi < lo) || (loc != 0 && (loc < lo || (hi != -1 && loc > hi)))) {
+            fprintf(stderr, "komb2: KOMB_CLIQUE_CENSUS=%s: expected 0 or <k_lo>:<k_hi>[:<k_local>] with 2 <= k_lo <= k_hi, k_hi a number or max, k_local inside\n", cc_env);
+            leave(EXIT_FAILURE);
+        }
+        cc_window[0] = (int32_t)lo; cc_window[1] = (int32_t)hi; cc_window[2] = (int32_t)loc;
+    }
+
     // structural clustering of the whole graph (no counterpart in the reference; opt-in): KOMB_STRUCTURAL=<num>/<den>,<mu>.  It
     // makes a whole-graph k-truss run of its own, before the truss stage below replaces that result with the max core's.
     const char *sc_env = getenv("KOMB_STRUCTURAL");
@@ -1374,6 +1444,7 @@ int main(int argc, const char **argv)
         if (nuc_on) write_nucleus(ctx, args.outdir, names, nv, args.threads, eu, ev);
         if (nh_on) write_nucleus_hierarchy(ctx, args.outdir, names, args.threads, nuc_on);
         if (mc_on) write_max_clique(ctx, (int64_t)mc_budget, args.outdir, names, nv, args.threads);
+        if (cc_on) write_clique_census(ctx, cc_window, args.outdir, names, nv, args.threads);
         if (hier_on) {                                     // the forest of the truss stage's result
             std::vector<int32_t> lvl((size_t)nv, 0);
             for (int64_t e = 0; e < ne_sub; ++e) {
