@@ -116,7 +116,8 @@ int         komb_abi_version(void);
  * (local | lds | none), LOCAL_LIMIT, LOCAL_ITEMS, LOCAL_DENSITY, LOCAL_DEFER_CHUNKS, TAIL, CORE_TAIL, INDEX (stream |
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
  * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
- * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), and the
+ * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), MAXIMAL_LDS,
+ * MAXIMAL_PIVOT, MAXIMAL_LIST, MAXIMAL_DEBUG (komb_maximal_cliques_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -599,6 +600,63 @@ int komb_clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_
 int komb_clique_census_fetch(komb_ctx *ctx, uint64_t *total /*[k_hi - k_lo + 1]*/, uint64_t *local /*[nv]*/);   /* either may be NULL */
 int komb_clique_census_info(komb_ctx *ctx, int32_t *k_lo, int32_t *k_hi, int32_t *k_local, int32_t *t_max, int32_t *omega,
                             int32_t *flags, int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms);   /* any may be NULL */
+
+/* ---- maximal cliques: Bron-Kerbosch with pivoting ---------------------------- */
+/* What igraph_maximal_cliques / maximal_cliques_hist / maximal_cliques_count and networkx.find_cliques give: the cliques that
+ * cannot be extended.  For the unitig graph, a union of per-read cliques, they are the repeat families themselves: the groups of
+ * unitigs that all co-occur pairwise and to which no further unitig can be added.  H, CLIQUE, trussness (= support + 2) and
+ * t_max are those of the maximum-clique search: the last COMPLETE k-truss result on the resident graph, whole graph or vmask
+ * run alike.
+ * A MAXIMAL CLIQUE is a clique of H contained in no larger clique of H.  komb_maximal_cliques_run(ctx, k_min, budget) reports
+ * the maximal cliques of at least k_min vertices, k_min >= 2 (singletons are not reported; an edge in no triangle is a maximal
+ * clique of 2 vertices).  The cut by k_min is exact: a clique C of >= k_min vertices uses only edges of trussness >= k_min, and
+ * so does C + x for any vertex x adjacent to all of C -- so for such cliques maximal among the edges of trussness >= k_min is
+ * maximal in H, the run looks at those edges only (a high k_min touches a small part of a large graph), and the maximal cliques
+ * of that part with fewer than k_min vertices are simply not reported.
+ * The walk is Bron-Kerbosch with pivoting from every canonical edge (a, b) as the two smallest ids of a clique, with the common
+ * neighbours above b as candidates and those below b as excluded vertices.  A NODE is one pair of
+ * candidate and excluded set evaluated, a root's own included; every reported clique costs at least one.  budget caps the nodes
+ * of the run exactly as komb_max_clique_run's does: 0 means the default, 2^30; a negative value is KOMB_ERR_ARG; a value above
+ * 2^31 - 1 - KOMB_MAXCLQ_OVERSHOOT runs as that; nodes <= budget + KOMB_MAXCLQ_OVERSHOOT always.  So n_cliques and every count
+ * fit int32 and nothing saturates.
+ * flags: KOMB_MAXIMAL_COMPLETE -- the budget did not run out; KOMB_MAXIMAL_LISTED -- the sorted list is held (implies
+ * COMPLETE).  With COMPLETE every output is unique: nothing depends on the run, on an option or on scheduling.  Without it what
+ * was reported is a lower bound: every reported clique is maximal in H and none is reported twice.
+ * komb_maximal_cliques_fetch: hist[k_hi - k_min + 1], entry i = the number of reported cliques of k_min + i vertices, with
+ * k_hi = max(k_min, t_max), so there is always an entry; count[nv] = the reported cliques that contain the vertex;
+ * largest[nv] = the size of the largest of them, 0 if none.  Any may be NULL.
+ * komb_maximal_cliques_list: the reported cliques as ascending tuples in lexicographic tuple order, CSR style: clique i is
+ * verts[offset[i], offset[i + 1]), offset[n_cliques] = n_verts.  offset == NULL and verts == NULL returns the two counts only;
+ * an output given with its cap below its count is KOMB_ERR_ARG and nothing is written; without LISTED: KOMB_ERR_LIMIT.
+ * komb_maximal_cliques_info: k_min and k_hi of the run; t_max; omega = the largest size with a non-zero hist entry, 0 if none
+ * (the clique number of H when COMPLETE is set and k_min <= it); flags; n_cliques = the sum of hist; max_candidates = the largest
+ * number of candidates and excluded vertices of a root at trussness >= k_min; n_roots = the canonical edges whose subproblem
+ * was opened; nodes = the nodes spent; ms = the device time of the run on the context's HIP-event timer.  Any pointer may be
+ * NULL.
+ * H without an edge, or k_min above t_max: every hist, count and largest entry 0, omega 0, flags = 3, an empty list.
+ * No context or no graph loaded: KOMB_ERR_ARG, nothing is written.  k_min < 2 or a negative budget: KOMB_ERR_ARG.  Without a
+ * completed k-truss result on this graph, after komb_truss_run_slice / a sharded run that materialised only part of the
+ * canonical edges, after komb_truss_unprepare, fetch / list / info before a run: KOMB_ERR_STATE.  A root edge with more than 4096
+ * candidates and excluded vertices together, of trussness >= k_min: KOMB_ERR_LIMIT, checked before anything is reported (the
+ * census and the search count candidates only: this limit is this call's own).  A pool failure: KOMB_ERR_NOMEM.
+ * The result lives in storage of its own, installed when a run has succeeded: a refused or failed run leaves the previous result
+ * readable.  It describes one k-truss result: whatever replaces or drops that result -- a new k-truss run of any kind,
+ * komb_truss_unprepare, a graph load -- drops it too.  No other call changes or drops it; a run changes no other result, no
+ * komb_stats field and not the resident k-truss preparation.  Options (none changes a complete result, except that MAXIMAL_LIST
+ * decides whether the list is held):
+ * MAXIMAL_LDS=<n>, 0 .. 512 (default 512): the largest candidate list whose bit matrix lives in LDS -- larger ones use the
+ * workgroup's slot of global scratch, 0 sends everything there; MAXIMAL_PIVOT=first|max (default max): the pivot of a node is
+ * its first candidate, or the candidate or excluded vertex with the most neighbours among the candidates; MAXIMAL_LIST=<n>,
+ * 0 .. 2^24 (default 65536): the list is held when the run reports at most n cliques and their sizes + 1 sum to at most
+ * min(n * (t_max + 1), 2^24) words; MAXIMAL_DEBUG=1 prints one stderr line with the counts, the nodes and the device time. */
+#define KOMB_MAXIMAL_COMPLETE 1   /* the budget did not run out */
+#define KOMB_MAXIMAL_LISTED   2   /* the sorted list is held (implies COMPLETE) */
+int komb_maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget);
+int komb_maximal_cliques_fetch(komb_ctx *ctx, int64_t *hist /*[k_hi - k_min + 1]*/, int32_t *count /*[nv]*/, int32_t *largest /*[nv]*/);   /* any may be NULL */
+int komb_maximal_cliques_list(komb_ctx *ctx, int64_t cap_cliques, int64_t cap_verts, int64_t *n_cliques, int64_t *n_verts,
+                              int64_t *offset /*[cap_cliques + 1]*/, int32_t *verts /*[cap_verts]*/);
+int komb_maximal_cliques_info(komb_ctx *ctx, int32_t *k_min, int32_t *k_hi, int32_t *t_max, int32_t *omega, int32_t *flags,
+                              int64_t *n_cliques, int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms);   /* any may be NULL */
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

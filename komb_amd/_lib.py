@@ -57,6 +57,7 @@ KOMB_SC_OUTLIER, KOMB_SC_HUB, KOMB_SC_BORDER, KOMB_SC_CORE = 0, 1, 2, 3
 KOMB_MAXCLQ_EXACT, KOMB_MAXCLQ_ENUMERATED, KOMB_MAXCLQ_LISTED = 1, 2, 4
 KOMB_MAXCLQ_OVERSHOOT = 262144
 KOMB_CENSUS_COMPLETE, KOMB_CENSUS_SATURATED = 1, 2
+KOMB_MAXIMAL_COMPLETE, KOMB_MAXIMAL_LISTED = 1, 2
 
 
 # every symbol include/komb_accel.h declares: name -> (restype, argtypes)
@@ -142,6 +143,11 @@ SIGNATURES = {
     "komb_clique_census_fetch": (_i32, [_vp, _vp, _vp]),
     "komb_clique_census_info": (_i32, [_vp] + [ctypes.POINTER(ctypes.c_int32)] * 7 + [ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                        ctypes.POINTER(ctypes.c_double)]),
+    "komb_maximal_cliques_run": (_i32, [_vp, ctypes.c_int32, _i64]),
+    "komb_maximal_cliques_fetch": (_i32, [_vp, _vp, _vp, _vp]),
+    "komb_maximal_cliques_list": (_i32, [_vp, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _vp]),
+    "komb_maximal_cliques_info": (_i32, [_vp] + [ctypes.POINTER(ctypes.c_int32)] * 5 + [ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

@@ -43,7 +43,7 @@ OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
                 "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "CENSUS_LDS", "CENSUS_PIVOT",
-                "CENSUS_DEBUG", "POISON")
+                "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -655,6 +655,50 @@ class KombAccel:
         self.clique_census_run(k_lo, k_hi, k_local, budget)
         total, local = self.clique_census_fetch()
         return total, local, self.clique_census_info()
+
+    # ---- maximal cliques of the last k-truss result: Bron-Kerbosch with pivoting (include/komb_accel.h)
+    MAXIMAL_CLIQUES_INFO_FIELDS = ("k_min", "k_hi", "t_max", "omega", "flags", "n_cliques", "max_candidates", "n_roots", "nodes", "ms")
+
+    def maximal_cliques_run(self, k_min=2, budget=0):
+        """Needs a complete k-truss result on this graph.  k_min: the smallest clique reported; budget: the node cap of the
+        run, 0 for the default."""
+        self._sync_env_options()
+        self._check(self._lib.komb_maximal_cliques_run(self._ctx, k_min, budget))
+
+    def maximal_cliques_info(self):
+        """{"k_min", "k_hi", "t_max", "omega", "flags", "n_cliques", "max_candidates", "n_roots", "nodes", "ms"} of the last
+        komb_maximal_cliques_run."""
+        i32 = [ctypes.c_int32() for _ in range(5)]
+        n, mc = ctypes.c_int64(), ctypes.c_int32()
+        i64 = [ctypes.c_int64() for _ in range(2)]
+        ms = ctypes.c_double()
+        self._check(self._lib.komb_maximal_cliques_info(self._ctx, *(ctypes.byref(x) for x in i32 + [n, mc] + i64), ctypes.byref(ms)))
+        return dict(zip(self.MAXIMAL_CLIQUES_INFO_FIELDS, [x.value for x in i32 + [n, mc] + i64] + [ms.value]))
+
+    def maximal_cliques_fetch(self):
+        """(hist int64[k_hi - k_min + 1], count int32[nv], largest int32[nv]): the reported cliques of k_min + i vertices, the
+        ones through every vertex and the size of the largest of those."""
+        info = self.maximal_cliques_info()
+        hist = np.full(info["k_hi"] - info["k_min"] + 1, SENTINEL_I32, dtype=np.int64)
+        count = _out_i32(max(self.nv, 0))
+        largest = _out_i32(max(self.nv, 0))
+        self._check(self._lib.komb_maximal_cliques_fetch(self._ctx, ptr(hist), ptr(count), ptr(largest)))
+        return hist, count, largest
+
+    def maximal_cliques_list(self):
+        """(offset int64[n_cliques + 1], verts int32[n_verts]): every reported clique as an ascending tuple
+        verts[offset[i]:offset[i + 1]], in lexicographic order (KOMB_ERR_LIMIT when the list was not kept)."""
+        n, nw = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.komb_maximal_cliques_list(self._ctx, 0, 0, ctypes.byref(n), ctypes.byref(nw), None, None))
+        offset = np.full(n.value + 1, SENTINEL_I32, dtype=np.int64)
+        verts = _out_i32(nw.value)
+        self._check(self._lib.komb_maximal_cliques_list(self._ctx, n.value, nw.value, ctypes.byref(n), ctypes.byref(nw), ptr(offset), ptr(verts)))
+        return offset, verts
+
+    def run_maximal_cliques(self, k_min=2, budget=0):
+        """(hist, count, largest, info) of the maximal cliques of the last k-truss result."""
+        self.maximal_cliques_run(k_min, budget)
+        return self.maximal_cliques_fetch() + (self.maximal_cliques_info(),)
 
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):

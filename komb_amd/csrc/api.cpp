@@ -615,6 +615,67 @@ int komb_clique_census_info(komb_ctx *ctx, int32_t *k_lo, int32_t *k_hi, int32_t
     return KOMB_OK;
 }
 
+int komb_maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
+{
+    KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_run");
+    if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_maximal_cliques_run: bad node budget %lld", (long long)budget);
+    if (k_min < 2) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_maximal_cliques_run: bad k_min %d", (int)k_min);
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    return maximal_cliques_run(ctx, k_min, budget);
+}
+
+int komb_maximal_cliques_fetch(komb_ctx *ctx, int64_t *hist, int32_t *count, int32_t *largest)
+{
+    KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_fetch");
+    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_fetch: no maximal cliques of the current k-truss result");
+    const size_t bytes = (size_t)(ctx->nv > 0 ? ctx->nv : 0) * sizeof(int32_t);
+    if (bytes && count) KOMB_HIP(ctx, staged_copy(ctx, count, ctx->d_mx_count, bytes, false));
+    if (bytes && largest) KOMB_HIP(ctx, staged_copy(ctx, largest, ctx->d_mx_count + ctx->nv, bytes, false));
+    if (hist) memcpy(hist, ctx->mx.hist.data(), ctx->mx.hist.size() * sizeof(int64_t));
+    return KOMB_OK;
+}
+
+int komb_maximal_cliques_list(komb_ctx *ctx, int64_t cap_cliques, int64_t cap_verts, int64_t *n_cliques, int64_t *n_verts, int64_t *offset, int32_t *verts)
+{
+    KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_list");
+    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_list: no maximal cliques of the current k-truss result");
+    const komb_ctx::MaximalCliques &r = ctx->mx;
+    if (!(r.flags & KOMB_MAXIMAL_LISTED))
+        KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_maximal_cliques_list: the list was not kept (flags %d, %lld cliques; option MAXIMAL_LIST, the node budget)",
+                  r.flags, (long long)r.n_cliques);
+    const int64_t nc = r.n_cliques, nw = (int64_t)r.verts.size();
+    if ((offset && cap_cliques < nc) || (verts && cap_verts < nw))
+        KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_maximal_cliques_list: room for %lld cliques and %lld vertices of %lld and %lld", (long long)cap_cliques,
+                  (long long)cap_verts, (long long)nc, (long long)nw);
+    if (n_cliques) *n_cliques = nc;
+    if (n_verts) *n_verts = nw;
+    if (offset) memcpy(offset, r.offset.data(), r.offset.size() * sizeof(int64_t));
+    if (verts && nw) memcpy(verts, r.verts.data(), (size_t)nw * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_maximal_cliques_info(komb_ctx *ctx, int32_t *k_min, int32_t *k_hi, int32_t *t_max, int32_t *omega, int32_t *flags, int64_t *n_cliques,
+                              int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_info");
+    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_info: no maximal cliques of the current k-truss result");
+    const komb_ctx::MaximalCliques &r = ctx->mx;
+    if (k_min) *k_min = r.k_min;
+    if (k_hi) *k_hi = r.k_hi;
+    if (t_max) *t_max = r.t_max;
+    if (omega) *omega = r.omega;
+    if (flags) *flags = r.flags;
+    if (n_cliques) *n_cliques = r.n_cliques;
+    if (max_candidates) *max_candidates = r.max_q;
+    if (n_roots) *n_roots = r.n_roots;
+    if (nodes) *nodes = r.nodes;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_nucleus_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_run");

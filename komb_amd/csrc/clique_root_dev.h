@@ -1,9 +1,10 @@
 // clique_root_dev.h -- the root of a clique subproblem over the oriented canonical edge list, shared by max_clique.hip (the
-// maximum-clique search) and clique_census.hip (the k-clique counts): row a = the positions [rs[a], re[a]) with eu == a, their ev
-// ascending.  A clique is handled at its ROOT, the canonical edge (a, b) of its two smallest ids; its other vertices are in
-// P = {c > b : (a, c) and (b, c) in H, both of trussness >= need}.  One wavefront (a workgroup of its own) owns a root: clq_cut
-// cuts P, clq_matrix makes P's adjacency a bit matrix, rows of W = ceil(|P| / 64) 64-bit words, lane w owning word w of every
-// row.  DESIGN.md sections 4.6j and 4.6k.
+// maximum-clique search), clique_census.hip (the k-clique counts) and maximal_cliques.hip (the maximal cliques): row a = the
+// positions [rs[a], re[a]) with eu == a, their ev ascending.  A clique is handled at its ROOT, the canonical edge (a, b) of its
+// two smallest ids; its other vertices are in P = {c > b : (a, c) and (b, c) in H, both of trussness >= need}.  One wavefront (a
+// workgroup of its own) owns a root: clq_cut cuts P, clq_matrix makes P's adjacency a bit matrix, rows of W = ceil(|P| / 64)
+// 64-bit words, lane w owning word w of every row.  The maximal cliques also need the common neighbours below b: clq_cut_x cuts
+// them from the lower rows, and clq_matrix takes X ++ P as it takes P.  DESIGN.md sections 4.6j, 4.6k and 4.6l.
 #pragma once
 
 #include "common.h"
@@ -77,6 +78,61 @@ __device__ __forceinline__ uint32_t clq_cut(const ClqGraph &G, uint32_t rj, uint
             }
             n += (uint32_t)__popcll(hits);
         }
+    return n;
+}
+
+// The LOWER ROWS (maximal_cliques.hip makes them, once per run): lower row b = the entries [ls[b], le[b]) of lu / lpos, one per
+// canonical edge with ev == b, lu = its eu (ascending), lpos = its position in the canonical list.
+struct ClqLower {
+    const int32_t *lu;
+    const uint32_t *lpos, *ls, *le;
+};
+
+// a part [lo, hi) of a row, ids ascending; entry i is the canonical edge pos[i], or i itself without pos (a row of the list)
+struct ClqSpan {
+    const int32_t *id;
+    const uint32_t *pos;
+    uint32_t lo, hi;
+};
+
+// The vertices of both spans whose two edges have trussness >= need, ascending, appended at X[n]: the shorter span is walked 64
+// entries at a time, the other bisected.  With fill what lies below cap is written.  Returns the new n.
+__device__ __forceinline__ uint32_t clq_meet(const int32_t *__restrict__ tr, ClqSpan r, ClqSpan s, uint32_t need, int32_t *X, uint32_t n, uint32_t cap,
+                                             bool fill, int lane)
+{
+    const uint32_t nr = r.hi > r.lo ? r.hi - r.lo : 0u, ns = s.hi > s.lo ? s.hi - s.lo : 0u;
+    if (nr == 0 || ns == 0) return n;
+    if (nr > ns) { const ClqSpan t = r; r = s; s = t; }
+    for (uint32_t x0 = r.lo; x0 < r.hi; x0 += kWave) {
+        const uint32_t x = x0 + (uint32_t)lane;
+        bool ok = false;
+        int32_t c = 0;
+        if (x < r.hi && (uint32_t)tr[r.pos ? r.pos[x] : x] >= need) {
+            c = r.id[x];
+            const uint32_t hit = nuc_find(s.id, c, s.lo, s.hi);
+            ok = hit != kNucNone && (uint32_t)tr[s.pos ? s.pos[hit] : hit] >= need;
+        }
+        const unsigned long long hits = __ballot(ok);
+        if (ok && fill) {
+            const uint32_t pos = n + (uint32_t)__popcll(hits & nuc_below(lane));
+            if (pos < cap) X[pos] = c;
+        }
+        n += (uint32_t)__popcll(hits);
+    }
+    return n;
+}
+
+// |X| of the root rj = (a, b), X = {x < b, x != a : (x, a) and (x, b) in H, both of trussness >= need}: x < a from the lower rows
+// of a and b, a < x < b from row a before rj and the lower row of b behind a.  Both parts are ascending and the first lies below
+// the second, so X is ascending.  With fill the first cap_x go to X.  Every branch is uniform over the wave.
+__device__ __forceinline__ uint32_t clq_cut_x(const ClqGraph &G, const ClqLower &L, uint32_t rj, uint32_t need, int32_t *X, uint32_t cap_x, bool fill, int lane)
+{
+    const int32_t a = G.eu[rj], b = G.ev[rj];
+    const uint32_t lb = L.ls[b], le = L.le[b];
+    const uint32_t ia = clq_lower(L.lu, a, lb, le);      // (a itself is in the lower row of b: the edge rj)
+    const uint32_t behind = ia < le ? ia + 1 : le;
+    uint32_t n = clq_meet(G.tr, ClqSpan{L.lu, L.lpos, L.ls[a], L.le[a]}, ClqSpan{L.lu, L.lpos, lb, ia}, need, X, 0u, cap_x, fill, lane);
+    n = clq_meet(G.tr, ClqSpan{G.ev, nullptr, G.rs[a], rj}, ClqSpan{L.lu, L.lpos, behind, le}, need, X, n, cap_x, fill, lane);
     return n;
 }
 

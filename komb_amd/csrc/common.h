@@ -399,6 +399,19 @@ struct komb_ctx {
     } cc;
     bool cc_done = false;
 
+    // ---- maximal cliques (maximal_cliques.hip): the per-vertex counts in a pool block of their own, the histogram and the sorted
+    // list on the host; they describe the k-truss result they were computed from and are dropped with it (truss_free)
+    int32_t *d_mx_count = nullptr;           // [2 * nv] reported cliques through the vertex | the size of the largest one
+    struct MaximalCliques {
+        int32_t k_min = 0, k_hi = 0, t_max = 0, omega = 0, flags = 0, max_q = 0;
+        int64_t n_cliques = 0, n_roots = 0, nodes = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        std::vector<int64_t> hist;           // [k_hi - k_min + 1] maximal cliques of k_min + i vertices
+        std::vector<int64_t> offset;         // [n_cliques + 1] with KOMB_MAXIMAL_LISTED: clique i is verts[offset[i], offset[i + 1])
+        std::vector<int32_t> verts;          // ascending tuples in lexicographic order
+    } mx;
+    bool mx_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                      // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -611,6 +624,8 @@ void max_clique_drop(komb_ctx *ctx);                          // max_clique.hip:
 // clique_census.hip: the k-truss result it needs, the budget's sign and 2 <= k_lo checked by the caller, the rest of the window here (it needs t_max)
 int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local, int64_t budget);
 void clique_census_drop(komb_ctx *ctx);                       // clique_census.hip: the result goes with the k-truss result it describes
+int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget);   // maximal_cliques.hip: the k-truss result it needs, the budget's sign and 2 <= k_min checked by the caller
+void maximal_cliques_drop(komb_ctx *ctx);                     // maximal_cliques.hip: the result goes with the k-truss result it describes
 int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);

@@ -283,6 +283,7 @@ void truss_free(komb_ctx *ctx)
     nucleus_drop(ctx);                       // (and the nucleus decomposition's triangles and edge_theta[])
     max_clique_drop(ctx);                    // (and the maximum cliques: they are this result's)
     clique_census_drop(ctx);                 // (and the clique census)
+    maximal_cliques_drop(ctx);               // (and the maximal cliques)
     if (ctx->t_own_edges) { ctx->pool.put(ctx->d_t_eu); ctx->pool.put(ctx->d_t_ev); }
     ctx->pool.put(ctx->d_t_truss);
     ctx->pool.put(ctx->d_t_sup);

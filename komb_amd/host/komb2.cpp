@@ -96,6 +96,16 @@
 //                       line k<TAB>count per k.  With a <k_local> also clique_census_unitigs.tsv: #Name, Count -- every unitig
 //                       in VID order with the number of k_local-cliques it lies in.  Counts saturate at 2^64 - 1 (flags 2).
 //                       0 or empty is off; anything else that is not of that form is a usage error.  Nothing else changes.
+//   KOMB_MAXIMAL_CLIQUES=<k_min>[:<budget>]  with KOMB_TRUSS=1: also write, after the truss stage, the maximal cliques of at least
+//                       <k_min> >= 2 unitigs of its result (komb_maximal_cliques_run; without <budget> the default node budget).
+//                       maximal_cliques.tsv: a header comment "# k_min <n> flags <n> omega <n> cliques <n> nodes <n> roots <n>",
+//                       then one line per clique in list order: its size and the Names of its unitigs in ascending VID order,
+//                       tab separated -- the header alone when the list is not held (flags without 2).
+//                       maximal_clique_sizes.tsv: one line size<TAB>count per size from k_min to max(k_min, the largest
+//                       trussness).  maximal_clique_unitigs.tsv: #Name, Count, Largest -- the unitigs in VID order that lie in
+//                       at least one reported clique, with their number and the size of the largest.  0 or empty is off;
+//                       anything else that is not of that form is a usage error.  VIDs depend on -t, so only the cliques as
+//                       sets of Names compare between runs.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -902,6 +912,63 @@ void write_clique_census(komb_ctx *ctx, const int32_t window[3], const std::stri
     fclose(fp);
 }
 
+// KOMB_MAXIMAL_CLIQUES: komb_maximal_cliques_run on the truss stage's result as three tables (the cliques in list order, the sizes
+// ascending, the unitigs in VID order)
+void write_maximal_cliques(komb_ctx *ctx, int32_t k_min_arg, int64_t budget, const std::string &outdir, const Names &names, int64_t nv, int threads)
+{
+    int rc = komb_maximal_cliques_run(ctx, k_min_arg, budget);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_maximal_cliques_run", rc);
+    int32_t k_min = 0, k_hi = 0, omega = 0, flags = 0;
+    int64_t n_cliques = 0, roots = 0, nodes = 0;
+    rc = komb_maximal_cliques_info(ctx, &k_min, &k_hi, nullptr, &omega, &flags, &n_cliques, nullptr, &roots, &nodes, nullptr);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_maximal_cliques_info", rc);
+    std::vector<int64_t> hist((size_t)(k_hi - k_min + 1)), offset(1, 0);
+    std::vector<int32_t> count((size_t)nv), largest((size_t)nv), verts;
+    rc = komb_maximal_cliques_fetch(ctx, hist.data(), count.data(), largest.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_maximal_cliques_fetch", rc);
+    int64_t rows = 0;
+    if (flags & KOMB_MAXIMAL_LISTED) {
+        int64_t n_verts = 0;
+        rc = komb_maximal_cliques_list(ctx, 0, 0, &rows, &n_verts, nullptr, nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_maximal_cliques_list", rc);
+        offset.resize((size_t)rows + 1);
+        verts.resize((size_t)n_verts);
+        rc = komb_maximal_cliques_list(ctx, rows, n_verts, nullptr, nullptr, offset.data(), verts.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_maximal_cliques_list", rc);
+    }
+    std::string path = outdir + "/maximal_cliques.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "# k_min %d flags %d omega %d cliques %lld nodes %lld roots %lld\n", (int)k_min, (int)flags, (int)omega, (long long)n_cliques,
+            (long long)nodes, (long long)roots);
+    write_rows(fp, rows, threads, [&](int64_t i, std::string &buf) {
+        buf.append(std::to_string(offset[(size_t)i + 1] - offset[(size_t)i]));
+        for (int64_t k = offset[(size_t)i]; k < offset[(size_t)i + 1]; ++k) {
+            buf.push_back('\t');
+            buf.append(names.name[(size_t)verts[(size_t)k]]);
+        }
+        buf.push_back('\n');
+    });
+    fclose(fp);
+    path = outdir + "/maximal_clique_sizes.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    for (size_t i = 0; i < hist.size(); ++i) fprintf(fp, "%d\t%lld\n", (int)k_min + (int)i, (long long)hist[i]);
+    fclose(fp);
+    path = outdir + "/maximal_clique_unitigs.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Name\tCount\tLargest\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (count[(size_t)i] <= 0) return;
+        buf.append(names.name[(size_t)i]);
+        char tmp[48];
+        const int len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)count[(size_t)i], (int)largest[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_NUCLEUS_HIERARCHY: komb_nucleus_hierarchy_run on the nucleus decomposition of the truss stage's result as two tables (nodes in
 // node order, member triangles in triangle order)
 void write_nucleus_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads, bool have_nucleus)
@@ -1381,6 +1448,29 @@ int main(int argc, const char **argv)
         cc_window[0] = (int32_t)lo; cc_window[1] = (int32_t)hi; cc_window[2] = (int32_t)loc;
     }
 
+    // the maximal cliques of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1):
+    // KOMB_MAXIMAL_CLIQUES=<k_min>[:<budget>]
+    const char *mx_env = getenv("KOMB_MAXIMAL_CLIQUES");
+    const bool mx_on = mx_env && *mx_env && strcmp(mx_env, "0") != 0;
+    long long mx_k_min = 0, mx_budget = 0;
+    if (mx_on) {
+        auto number = [](const char *&q, long long lo, long long hi) -> long long {   // a decimal number of [lo, hi] at q, -1 if there is none
+            if (*q < '0' || *q > '9') return -1;
+            char *end = nullptr;
+            errno = 0;
+            const long long v = strtoll(q, &end, 10);
+            q = end;
+            return errno || v < lo || v > hi ? -1 : v;
+        };
+        const char *q = mx_env;
+        mx_k_min = number(q, 2, 0x7FFFFFFF);
+        if (*q == ':') { ++q; mx_budget = number(q, 1, 0x7FFFFFFFFFFFFFFFll); }
+        if (*q || mx_k_min < 0 || mx_budget < 0) {
+            fprintf(stderr, "komb2: KOMB_MAXIMAL_CLIQUES=%s: expected 0 or <k_min>[:<budget>] with k_min >= 2 and a node budget >= 1\n", mx_env);
+            leave(EXIT_FAILURE);
+        }
+    }
+
     // structural clustering of the whole graph (no counterpart in the reference; opt-in): KOMB_STRUCTURAL=<num>/<den>,<mu>.  It
     // makes a whole-graph k-truss run of its own, before the truss stage below replaces that result with the max core's.
     const char *sc_env = getenv("KOMB_STRUCTURAL");
@@ -1445,6 +1535,7 @@ int main(int argc, const char **argv)
         if (nh_on) write_nucleus_hierarchy(ctx, args.outdir, names, args.threads, nuc_on);
         if (mc_on) write_max_clique(ctx, (int64_t)mc_budget, args.outdir, names, nv, args.threads);
         if (cc_on) write_clique_census(ctx, cc_window, args.outdir, names, nv, args.threads);
+        if (mx_on) write_maximal_cliques(ctx, (int32_t)mx_k_min, (int64_t)mx_budget, args.outdir, names, nv, args.threads);
         if (hier_on) {                                     // the forest of the truss stage's result
             std::vector<int32_t> lvl((size_t)nv, 0);
             for (int64_t e = 0; e < ne_sub; ++e) {
