@@ -1,5 +1,7 @@
 /*
- * komb_accel.h -- C ABI of the MI355X-native k-core / k-truss / CoreA path.
+ * komb_accel.h -- C ABI of the MI355X-native k-core / k-truss / CoreA path, and of the analyses of a k-truss result built on
+ * it: components, communities, hierarchies, densest subgraph, structural clusters, nuclei, maximum and maximal cliques, the
+ * clique census and the k-clique communities (clique percolation).
  *
  * This is the drop-in boundary for KOMB's decomposition hot path: each entry
  * point replaces the igraph / CoreA call group named beside it (paths are
@@ -117,7 +119,8 @@ int         komb_abi_version(void);
  * two_pass), REC_CAP, OWN_DENSE_CAP, NO_OWN_DENSE, NO_REC_SCRATCH, NO_FIRST_QUEUE, RETIRE_EVERY, SHARD_ENGINE, and the
  * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
  * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), MAXIMAL_LDS,
- * MAXIMAL_PIVOT, MAXIMAL_LIST, MAXIMAL_DEBUG (komb_maximal_cliques_run, below), and the
+ * MAXIMAL_PIVOT, MAXIMAL_LIST, MAXIMAL_DEBUG (komb_maximal_cliques_run, below), PERC_GROUP, PERC_DEBUG
+ * (komb_clique_communities_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -657,6 +660,59 @@ int komb_maximal_cliques_list(komb_ctx *ctx, int64_t cap_cliques, int64_t cap_ve
                               int64_t *offset /*[cap_cliques + 1]*/, int32_t *verts /*[cap_verts]*/);
 int komb_maximal_cliques_info(komb_ctx *ctx, int32_t *k_min, int32_t *k_hi, int32_t *t_max, int32_t *omega, int32_t *flags,
                               int64_t *n_cliques, int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms);   /* any may be NULL */
+
+/* ---- k-clique communities: clique percolation -------------------------------- */
+/* What networkx.algorithms.community.k_clique_communities gives (Palla, Derenyi, Farkas, Vicsek, Nature 2005): the overlapping
+ * communities of H, the last COMPLETE k-truss result.  For the unitig graph a maximal clique is one repeat family; a k-clique
+ * community is a chain of families that overlap almost completely, and a unitig may lie in several of them -- which k-truss
+ * communities, SCAN clusters and nuclei, each a partition of edges or triangles, cannot express.
+ * Fix k >= 2.  The MEMBER cliques are the maximal cliques of H with at least k vertices.  Two member cliques are ADJACENT when
+ * they share at least k - 1 vertices.  A k-CLIQUE COMMUNITY is the union of the vertex sets of one connected class of member
+ * cliques.  This equals the original definition (the k-cliques of H joined through shared (k - 1)-cliques): every k-clique lies
+ * in a member clique, the k-cliques inside one clique are connected, and two cliques that share k - 1 vertices hold two
+ * k-cliques that do.  A vertex may lie in several communities; the communities of k + 1 lie inside those of k; at k = 2 they are
+ * the connected components of H without its isolated vertices; at k = 3 their vertex sets are those of the k-truss communities
+ * at k = 3, at k = 4 those of the 1-nuclei of the nucleus hierarchy.
+ * komb_clique_communities_run(ctx, k, budget) works on the list that komb_maximal_cliques_run holds (KOMB_MAXIMAL_LISTED, with a
+ * k_min <= k); all clique indices are positions in that sorted list, as komb_maximal_cliques_list gives it.  The REP of a
+ * community is the smallest index of its cliques; communities are numbered 0 .. n - 1 in ascending rep order.
+ * Adjacent pairs are found through the cliques' incidence, not by testing all pairs: a clique of s vertices has s - k + 2
+ * PIVOTS, its vertices of smallest (load, id), load = the member cliques through the vertex, and every clique adjacent to it
+ * contains one of them.  pair_tests = the sum over member cliques i and their pivots v of the member
+ * cliques j > i through v: the candidates the run looks at, a deterministic number computed before anything is linked.
+ * budget caps it: 0 means the default, 2^32; a negative value is KOMB_ERR_ARG; when pair_tests exceeds the budget the run is
+ * refused with KOMB_ERR_LIMIT before anything is linked (the message names both numbers).  There are no partial results.
+ * komb_clique_communities_count: the number n of communities and n_member_verts = offset[n], the sum of their vertex counts.
+ * komb_clique_communities_fetch: label[i] = the rep of clique i's community, -1 for a clique of fewer than k vertices;
+ * size[i] = the number of cliques of that community, 0 for such a clique; both [n_cliques of the list].
+ * komb_clique_communities_fetch_communities: rep[n], n_cliques[n] = the cliques of the community, offset[n + 1] and
+ * verts[n_member_verts]: community c is verts[offset[c], offset[c + 1]), ascending and distinct.
+ * komb_clique_communities_fetch_vertices: n_comm[nv] = how many communities contain the vertex; first[nv] = the smallest
+ * community number that contains it, -1 if none.
+ * komb_clique_communities_info: k; k_min = that of the list used; n_member_cliques; n_communities; largest = the most vertices
+ * in one community; n_covered = the vertices with n_comm >= 1; n_overlap = those with n_comm >= 2; pair_tests; ms = the device
+ * time of the run on the context's HIP-event timer.  Any output pointer may be NULL.
+ * A list without a member clique (H without an edge, k above t_max): n = 0, every label -1, every size and n_comm 0, every
+ * first -1, offset = {0}; not an error.
+ * No context or no graph loaded: KOMB_ERR_ARG, nothing is written.  k < 2 or a negative budget: KOMB_ERR_ARG.  No
+ * maximal-cliques result of the current k-truss result, or one whose k_min is above k (the list lacks member cliques; the
+ * message names both numbers): KOMB_ERR_STATE, as is a count / fetch / info before a run.  A maximal-cliques result without
+ * KOMB_MAXIMAL_LISTED: KOMB_ERR_LIMIT, as komb_maximal_cliques_list answers.  A pool failure: KOMB_ERR_NOMEM.
+ * The result is built on the side and installed when a run has succeeded, as komb_maximal_cliques_run does: a refused or failed
+ * run leaves the previous result readable.  It describes one maximal-cliques result and goes with it: a komb_maximal_cliques_run
+ * that succeeds, a new k-truss run of any kind, komb_truss_unprepare and a graph load drop it.  No other call changes or drops
+ * it; a run changes no other result, no komb_stats field and not the resident k-truss preparation.  Every output is unique:
+ * nothing depends on the run, on an option or on scheduling.  Options: PERC_GROUP=4|16|64: the lanes that intersect one candidate
+ * with the clique at hand (default: chosen per clique from its size: up to 8 vertices 4, up to 32 vertices 16, else 64);
+ * PERC_DEBUG=1 prints one stderr line with the counts, pair_tests and the device time. */
+int komb_clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget);
+int komb_clique_communities_count(komb_ctx *ctx, int64_t *n_communities, int64_t *n_member_verts);   /* any may be NULL */
+int komb_clique_communities_fetch(komb_ctx *ctx, int32_t *label /*[n_cliques of the list]*/, int32_t *size /*[n_cliques of the list]*/);   /* any may be NULL */
+int komb_clique_communities_fetch_communities(komb_ctx *ctx, int32_t *rep /*[n]*/, int32_t *n_cliques /*[n]*/, int64_t *offset /*[n + 1]*/,
+                                              int32_t *verts /*[n_member_verts]*/);   /* any may be NULL */
+int komb_clique_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm /*[nv]*/, int32_t *first /*[nv]*/);   /* any may be NULL */
+int komb_clique_communities_info(komb_ctx *ctx, int32_t *k, int32_t *k_min, int64_t *n_member_cliques, int64_t *n_communities, int64_t *largest,
+                                 int64_t *n_covered, int64_t *n_overlap, int64_t *pair_tests, double *ms);   /* any may be NULL */
 
 /* ---- k-truss ----------------------------------------------------------- */
 /* Replaces igraph_induced_subgraph_map + igraph_trussness

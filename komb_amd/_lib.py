@@ -148,6 +148,13 @@ SIGNATURES = {
     "komb_maximal_cliques_list": (_i32, [_vp, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _vp]),
     "komb_maximal_cliques_info": (_i32, [_vp] + [ctypes.POINTER(ctypes.c_int32)] * 5 + [ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_clique_communities_run": (_i32, [_vp, ctypes.c_int32, _i64]),
+    "komb_clique_communities_count": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "komb_clique_communities_fetch": (_i32, [_vp, _vp, _vp]),
+    "komb_clique_communities_fetch_communities": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "komb_clique_communities_fetch_vertices": (_i32, [_vp, _vp, _vp]),
+    "komb_clique_communities_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)] + [ctypes.POINTER(_i64)] * 6
+                                            + [ctypes.POINTER(ctypes.c_double)]),
     "komb_truss_run": (_i32, [_vp, _vp]),
     "komb_truss_run_sharded": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "komb_truss_run_slice": (_i32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32]),

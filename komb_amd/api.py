@@ -43,7 +43,8 @@ OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
                 "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "CENSUS_LDS", "CENSUS_PIVOT",
-                "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "POISON")
+                "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "PERC_GROUP", "PERC_DEBUG",
+                "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
@@ -699,6 +700,63 @@ class KombAccel:
         """(hist, count, largest, info) of the maximal cliques of the last k-truss result."""
         self.maximal_cliques_run(k_min, budget)
         return self.maximal_cliques_fetch() + (self.maximal_cliques_info(),)
+
+    # ---- k-clique communities of the held maximal cliques: clique percolation (include/komb_accel.h)
+    CLIQUE_COMMUNITIES_INFO_FIELDS = ("k", "k_min", "n_member_cliques", "n_communities", "largest", "n_covered", "n_overlap", "pair_tests", "ms")
+
+    def clique_communities_run(self, k=3, budget=0):
+        """Needs the list of a komb_maximal_cliques_run with k_min <= k on the current k-truss result.  budget: the cap on
+        pair_tests, 0 for the default."""
+        self._sync_env_options()
+        self._check(self._lib.komb_clique_communities_run(self._ctx, k, budget))
+
+    def clique_communities_info(self):
+        """{"k", "k_min", "n_member_cliques", "n_communities", "largest", "n_covered", "n_overlap", "pair_tests", "ms"} of the
+        last komb_clique_communities_run."""
+        i32 = [ctypes.c_int32() for _ in range(2)]
+        i64 = [ctypes.c_int64() for _ in range(6)]
+        ms = ctypes.c_double()
+        self._check(self._lib.komb_clique_communities_info(self._ctx, *(ctypes.byref(x) for x in i32 + i64), ctypes.byref(ms)))
+        return dict(zip(self.CLIQUE_COMMUNITIES_INFO_FIELDS, [x.value for x in i32 + i64] + [ms.value]))
+
+    def clique_communities_count(self):
+        """(n_communities, n_member_verts)."""
+        n, nw = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.komb_clique_communities_count(self._ctx, ctypes.byref(n), ctypes.byref(nw)))
+        return n.value, nw.value
+
+    def clique_communities_fetch(self):
+        """(label int32[n_cliques of the list], size int32[same]): the rep of every clique's community (-1 for a clique of
+        fewer than k vertices) and the number of cliques of that community (0)."""
+        self.clique_communities_count()                    # (the state check, before the list is asked for its length)
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_maximal_cliques_list(self._ctx, 0, 0, ctypes.byref(n), None, None, None))
+        label, size = _out_i32(n.value), _out_i32(n.value)
+        self._check(self._lib.komb_clique_communities_fetch(self._ctx, ptr(label), ptr(size)))
+        return label, size
+
+    def clique_communities_fetch_communities(self):
+        """(rep int32[n], n_cliques int32[n], offset int64[n + 1], verts int32[n_member_verts]): community c is
+        verts[offset[c]:offset[c + 1]], ascending and distinct."""
+        n, nw = self.clique_communities_count()
+        rep, ncl = _out_i32(n), _out_i32(n)
+        offset = np.full(n + 1, SENTINEL_I32, dtype=np.int64)
+        verts = _out_i32(nw)
+        self._check(self._lib.komb_clique_communities_fetch_communities(self._ctx, ptr(rep), ptr(ncl), ptr(offset), ptr(verts)))
+        return rep, ncl, offset, verts
+
+    def clique_communities_fetch_vertices(self):
+        """(n_comm int32[nv], first int32[nv]): how many communities contain the vertex and the smallest of them (-1)."""
+        n_comm, first = _out_i32(max(self.nv, 0)), _out_i32(max(self.nv, 0))
+        self._check(self._lib.komb_clique_communities_fetch_vertices(self._ctx, ptr(n_comm), ptr(first)))
+        return n_comm, first
+
+    def run_clique_communities(self, k=3, budget=0):
+        """(label, size, rep, n_cliques, offset, verts, n_comm, first, info) of the k-clique communities of the held maximal
+        cliques."""
+        self.clique_communities_run(k, budget)
+        return (self.clique_communities_fetch() + self.clique_communities_fetch_communities() + self.clique_communities_fetch_vertices()
+                + (self.clique_communities_info(),))
 
     # ---- CoreA (a9 + a10)
     def get_anomaly_score(self, degree, coreness):

@@ -676,6 +676,81 @@ int komb_maximal_cliques_info(komb_ctx *ctx, int32_t *k_min, int32_t *k_hi, int3
     return KOMB_OK;
 }
 
+int komb_clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_communities_run");
+    if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_communities_run: bad pair-test budget %lld", (long long)budget);
+    if (k < 2) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_communities_run: bad k %d", (int)k);
+    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_run: no maximal cliques of the current k-truss result");
+    const komb_ctx::MaximalCliques &r = ctx->mx;
+    if (r.k_min > k)
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_run: the held maximal cliques have k_min %d, above k %d: the list lacks member cliques",
+                  (int)r.k_min, (int)k);
+    if (!(r.flags & KOMB_MAXIMAL_LISTED))
+        KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_clique_communities_run: the list was not kept (flags %d, %lld cliques; option MAXIMAL_LIST, the node budget)",
+                  r.flags, (long long)r.n_cliques);
+    return clique_communities_run(ctx, k, budget);
+}
+
+int komb_clique_communities_count(komb_ctx *ctx, int64_t *n_communities, int64_t *n_member_verts)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_communities_count");
+    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_count: no k-clique communities of the current maximal cliques");
+    if (n_communities) *n_communities = ctx->pc.n_comm;
+    if (n_member_verts) *n_member_verts = (int64_t)ctx->pc.verts.size();
+    return KOMB_OK;
+}
+
+int komb_clique_communities_fetch(komb_ctx *ctx, int32_t *label, int32_t *size)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_communities_fetch");
+    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_fetch: no k-clique communities of the current maximal cliques");
+    const komb_ctx::CliqueCommunities &r = ctx->pc;
+    if (label && !r.label.empty()) memcpy(label, r.label.data(), r.label.size() * sizeof(int32_t));
+    if (size && !r.size.empty()) memcpy(size, r.size.data(), r.size.size() * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_clique_communities_fetch_communities(komb_ctx *ctx, int32_t *rep, int32_t *n_cliques, int64_t *offset, int32_t *verts)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_communities_fetch_communities");
+    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_fetch_communities: no k-clique communities of the current maximal cliques");
+    const komb_ctx::CliqueCommunities &r = ctx->pc;
+    if (rep && !r.rep.empty()) memcpy(rep, r.rep.data(), r.rep.size() * sizeof(int32_t));
+    if (n_cliques && !r.n_cliques.empty()) memcpy(n_cliques, r.n_cliques.data(), r.n_cliques.size() * sizeof(int32_t));
+    if (offset) memcpy(offset, r.offset.data(), r.offset.size() * sizeof(int64_t));
+    if (verts && !r.verts.empty()) memcpy(verts, r.verts.data(), r.verts.size() * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_clique_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm, int32_t *first)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_communities_fetch_vertices");
+    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_fetch_vertices: no k-clique communities of the current maximal cliques");
+    const komb_ctx::CliqueCommunities &r = ctx->pc;
+    if (n_comm && !r.v_comm.empty()) memcpy(n_comm, r.v_comm.data(), r.v_comm.size() * sizeof(int32_t));
+    if (first && !r.v_first.empty()) memcpy(first, r.v_first.data(), r.v_first.size() * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_clique_communities_info(komb_ctx *ctx, int32_t *k, int32_t *k_min, int64_t *n_member_cliques, int64_t *n_communities, int64_t *largest,
+                                 int64_t *n_covered, int64_t *n_overlap, int64_t *pair_tests, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_clique_communities_info");
+    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_info: no k-clique communities of the current maximal cliques");
+    const komb_ctx::CliqueCommunities &r = ctx->pc;
+    if (k) *k = r.k;
+    if (k_min) *k_min = r.k_min;
+    if (n_member_cliques) *n_member_cliques = r.n_member;
+    if (n_communities) *n_communities = r.n_comm;
+    if (largest) *largest = r.largest;
+    if (n_covered) *n_covered = r.n_covered;
+    if (n_overlap) *n_overlap = r.n_overlap;
+    if (pair_tests) *pair_tests = r.pair_tests;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_nucleus_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_run");

@@ -412,6 +412,20 @@ struct komb_ctx {
     } mx;
     bool mx_done = false;
 
+    // ---- k-clique communities (clique_communities.hip): computed on the device, kept on the host; they describe the held list
+    // of maximal cliques and are dropped with it (maximal_cliques_drop)
+    struct CliqueCommunities {
+        int32_t k = 0, k_min = 0;
+        int64_t n_member = 0, n_comm = 0, largest = 0, n_covered = 0, n_overlap = 0, pair_tests = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        std::vector<int32_t> label, size;    // [n_cliques of the list] the rep of the clique's community (-1) | its cliques (0)
+        std::vector<int32_t> rep, n_cliques; // [n_comm] ascending reps | the cliques of the community
+        std::vector<int64_t> offset;         // [n_comm + 1] community c is verts[offset[c], offset[c + 1]), ascending and distinct
+        std::vector<int32_t> verts;
+        std::vector<int32_t> v_comm, v_first;   // [nv] the communities through the vertex | the smallest of them (-1)
+    } pc;
+    bool pc_done = false;
+
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                      // edges of the (sub)graph last run
     int32_t *d_t_eu = nullptr, *d_t_ev = nullptr, *d_t_truss = nullptr, *d_t_sup = nullptr;
@@ -626,6 +640,9 @@ int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local
 void clique_census_drop(komb_ctx *ctx);                       // clique_census.hip: the result goes with the k-truss result it describes
 int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget);   // maximal_cliques.hip: the k-truss result it needs, the budget's sign and 2 <= k_min checked by the caller
 void maximal_cliques_drop(komb_ctx *ctx);                     // maximal_cliques.hip: the result goes with the k-truss result it describes
+// clique_communities.hip: the held list of maximal cliques (listed, k_min <= k), 2 <= k and the budget's sign checked by the caller
+int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget);
+void clique_communities_drop(komb_ctx *ctx);                  // clique_communities.hip: the result goes with the maximal cliques it describes
 int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);

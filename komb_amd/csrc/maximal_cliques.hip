@@ -356,6 +356,7 @@ bool mx_sort_list(const std::vector<int32_t> &raw, size_t n, std::vector<int64_t
 
 void maximal_cliques_drop(komb_ctx *ctx)
 {
+    clique_communities_drop(ctx);                        // (and the k-clique communities: they are this list's)
     ctx->pool.put(ctx->d_mx_count);
     ctx->d_mx_count = nullptr;
     ctx->mx = komb_ctx::MaximalCliques{};

@@ -106,6 +106,16 @@
 //                       at least one reported clique, with their number and the size of the largest.  0 or empty is off;
 //                       anything else that is not of that form is a usage error.  VIDs depend on -t, so only the cliques as
 //                       sets of Names compare between runs.  Nothing else changes.
+//   KOMB_CLIQUE_COMMUNITIES=<k>[:<budget>]  with KOMB_TRUSS=1: also write, after the truss stage, the k-clique communities of its
+//                       result, k >= 2 (komb_clique_communities_run: clique percolation over the maximal cliques of at least
+//                       <k> unitigs; without <budget> the default cap on pair tests).  The maximal cliques are those of
+//                       KOMB_MAXIMAL_CLIQUES when that ran with a k_min <= k, else of a komb_maximal_cliques_run(k, default
+//                       budget) made for this.  clique_communities.tsv: a header comment "# k <n> communities <n>
+//                       member_cliques <n> covered <n> overlap <n> pair_tests <n>", then one line per community: its number,
+//                       its cliques, its unitigs and the Names of its unitigs in ascending VID order, tab separated.
+//                       clique_community_unitigs.tsv: #Name, Communities, First -- the unitigs in VID order that lie in at
+//                       least one community, with their number of communities and the smallest community number.  0 or empty
+//                       is off; anything else that is not of that form is a usage error.  Nothing else changes.
 //   KOMB_STRICT_SAM=1   parse every SAM line (the reference drops the line that
 //                       straddles each OpenMP byte-chunk boundary, see readSAM)
 //   KOMB_DEVICE=<n>     HIP device ordinal (default 0)
@@ -969,6 +979,61 @@ void write_maximal_cliques(komb_ctx *ctx, int32_t k_min_arg, int64_t budget, con
     fclose(fp);
 }
 
+// KOMB_CLIQUE_COMMUNITIES: komb_clique_communities_run on the maximal cliques of the truss stage's result as two tables (the
+// communities in community order, the unitigs in VID order).  have_list: KOMB_MAXIMAL_CLIQUES left a list with a k_min <= k.
+void write_clique_communities(komb_ctx *ctx, int32_t k_arg, int64_t budget, bool have_list, const std::string &outdir, const Names &names, int64_t nv,
+                              int threads)
+{
+    int rc = KOMB_OK;
+    if (!have_list) {
+        rc = komb_maximal_cliques_run(ctx, k_arg, 0);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_maximal_cliques_run", rc);
+    }
+    rc = komb_clique_communities_run(ctx, k_arg, budget);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_communities_run", rc);
+    int32_t k = 0;
+    int64_t n_member = 0, n_comm = 0, covered = 0, overlap = 0, pair_tests = 0, n_verts = 0;
+    rc = komb_clique_communities_info(ctx, &k, nullptr, &n_member, &n_comm, nullptr, &covered, &overlap, &pair_tests, nullptr);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_communities_info", rc);
+    rc = komb_clique_communities_count(ctx, nullptr, &n_verts);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_communities_count", rc);
+    std::vector<int32_t> n_cliques((size_t)n_comm), verts((size_t)n_verts), v_comm((size_t)nv), v_first((size_t)nv);
+    std::vector<int64_t> offset((size_t)n_comm + 1, 0);
+    rc = komb_clique_communities_fetch_communities(ctx, nullptr, n_cliques.data(), offset.data(), verts.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_communities_fetch_communities", rc);
+    rc = komb_clique_communities_fetch_vertices(ctx, v_comm.data(), v_first.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_clique_communities_fetch_vertices", rc);
+    std::string path = outdir + "/clique_communities.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "# k %d communities %lld member_cliques %lld covered %lld overlap %lld pair_tests %lld\n", (int)k, (long long)n_comm, (long long)n_member,
+            (long long)covered, (long long)overlap, (long long)pair_tests);
+    write_rows(fp, n_comm, threads, [&](int64_t c, std::string &buf) {
+        char tmp[64];
+        const int len = snprintf(tmp, sizeof(tmp), "%lld\t%d\t%lld", (long long)c, (int)n_cliques[(size_t)c],
+                                 (long long)(offset[(size_t)c + 1] - offset[(size_t)c]));
+        buf.append(tmp, (size_t)len);
+        for (int64_t i = offset[(size_t)c]; i < offset[(size_t)c + 1]; ++i) {
+            buf.push_back('\t');
+            buf.append(names.name[(size_t)verts[(size_t)i]]);
+        }
+        buf.push_back('\n');
+    });
+    fclose(fp);
+    path = outdir + "/clique_community_unitigs.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Name\tCommunities\tFirst\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (v_comm[(size_t)i] <= 0) return;
+        buf.append(names.name[(size_t)i]);
+        char tmp[48];
+        const int len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)v_comm[(size_t)i], (int)v_first[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_NUCLEUS_HIERARCHY: komb_nucleus_hierarchy_run on the nucleus decomposition of the truss stage's result as two tables (nodes in
 // node order, member triangles in triangle order)
 void write_nucleus_hierarchy(komb_ctx *ctx, const std::string &outdir, const Names &names, int threads, bool have_nucleus)
@@ -1471,6 +1536,29 @@ int main(int argc, const char **argv)
         }
     }
 
+    // the k-clique communities of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1):
+    // KOMB_CLIQUE_COMMUNITIES=<k>[:<budget>]
+    const char *pc_env = getenv("KOMB_CLIQUE_COMMUNITIES");
+    const bool pc_on = pc_env && *pc_env && strcmp(pc_env, "0") != 0;
+    long long pc_k = 0, pc_budget = 0;
+    if (pc_on) {
+        auto number = [](const char *&q, long long lo, long long hi) -> long long {   // a decimal number of [lo, hi] at q, -1 if there is none
+            if (*q < '0' || *q > '9') return -1;
+            char *end = nullptr;
+            errno = 0;
+            const long long v = strtoll(q, &end, 10);
+            q = end;
+            return errno || v < lo || v > hi ? -1 : v;
+        };
+        const char *q = pc_env;
+        pc_k = number(q, 2, 0x7FFFFFFF);
+        if (*q == ':') { ++q; pc_budget = number(q, 1, 0x7FFFFFFFFFFFFFFFll); }
+        if (*q || pc_k < 0 || pc_budget < 0) {
+            fprintf(stderr, "komb2: KOMB_CLIQUE_COMMUNITIES=%s: expected 0 or <k>[:<budget>] with k >= 2 and a pair-test budget >= 1\n", pc_env);
+            leave(EXIT_FAILURE);
+        }
+    }
+
     // structural clustering of the whole graph (no counterpart in the reference; opt-in): KOMB_STRUCTURAL=<num>/<den>,<mu>.  It
     // makes a whole-graph k-truss run of its own, before the truss stage below replaces that result with the max core's.
     const char *sc_env = getenv("KOMB_STRUCTURAL");
@@ -1536,6 +1624,7 @@ int main(int argc, const char **argv)
         if (mc_on) write_max_clique(ctx, (int64_t)mc_budget, args.outdir, names, nv, args.threads);
         if (cc_on) write_clique_census(ctx, cc_window, args.outdir, names, nv, args.threads);
         if (mx_on) write_maximal_cliques(ctx, (int32_t)mx_k_min, (int64_t)mx_budget, args.outdir, names, nv, args.threads);
+        if (pc_on) write_clique_communities(ctx, (int32_t)pc_k, (int64_t)pc_budget, mx_on && mx_k_min <= pc_k, args.outdir, names, nv, args.threads);
         if (hier_on) {                                     // the forest of the truss stage's result
             std::vector<int32_t> lvl((size_t)nv, 0);
             for (int64_t e = 0; e < ne_sub; ++e) {
