@@ -74,30 +74,81 @@ __global__ __launch_bounds__(kBlock) void k_count_mismatch(const uint32_t *__res
 
 // supports of a bin's edges: dense own-role entries + records of the bin with that key (LDS histogram); per-bin totals
 // (their scan gives every bin its window of the index) and the 64-bit grand total on the side.
-__global__ __launch_bounds__(kBlock) void k_bin_count(const uint32_t *__restrict__ key, const uint32_t *__restrict__ boff, BinGeom g,
+constexpr int kCntU = 4;                                   // keys per thread per trip
+constexpr int kCntE = (int)(kBinEdges / kBlock);           // edges per thread
+static_assert(kBlock % (1 << kChunkBits) == 0, "a thread's edges sit at one place in different chunks of the bin");
+// (8 wavefronts per SIMD: the grid is 8 workgroups per CU, all resident at once -- the registers of the loads ahead must not cost that)
+__global__ __launch_bounds__(kBlock, 8) void k_bin_count(const uint32_t *__restrict__ key, const uint32_t *__restrict__ boff, BinGeom g,
                                                       const uint32_t *__restrict__ own, int64_t m, uint32_t *__restrict__ sum,
                                                       uint32_t *__restrict__ bin_total, unsigned long long *__restrict__ total,
                                                       int32_t *__restrict__ min_pos)
 {
     // min_pos: the smallest positive support = the peel's first level (k_bin_finish queues its frontier)
+    // A workgroup walks its bins one after the other, and a bin is a chain boff -> keys -> own with barriers in between: what
+    // keeps the stream going is how much of that chain is requested ahead.  The next bin's boff pair is loaded while the
+    // current bin's records are counted, the first trip of its keys while the current bin is reduced; a bin's own-role
+    // counts are requested before its records are counted; a trip is kCntU keys per thread, all loaded before the first
+    // LDS atomic.
     __shared__ uint32_t sh_cnt[kBinEdges];
     __shared__ uint32_t sh_part[kBlock / kWave];
     unsigned long long t = 0;
     int32_t lmin = 0x7FFFFFFF;
+    uint32_t n0 = 0, n1 = 0;                                       // the records of the workgroup's next bin
+    uint32_t kq[kCntU];                                            // ... and the first trip of their keys
+    auto first_keys = [&](uint32_t r0, uint32_t r1) {
+#pragma unroll
+        for (int u = 0; u < kCntU; ++u) {
+            const uint64_t r = (uint64_t)r0 + threadIdx.x + (uint64_t)u * kBlock;
+            kq[u] = r < r1 ? key[r] : 0xFFFFFFFFu;
+        }
+    };
+    if (blockIdx.x < g.nb) { n0 = boff[blockIdx.x]; n1 = boff[blockIdx.x + 1]; first_keys(n0, n1); }
     for (uint32_t b = blockIdx.x; b < g.nb; b += gridDim.x) {
+        const uint32_t r0 = n0, r1 = n1;
+        const uint32_t bn = b + gridDim.x;
+        const bool more = bn > b && bn < g.nb;
+        if (more) { n0 = boff[bn]; n1 = boff[bn + 1]; }
+        // the thread's kCntE edges: local indices threadIdx.x + u * kBlock, i.e. the same place in every (kBlock >> kChunkBits)-th chunk
+        const uint64_t e_first = g.edge_of(b, threadIdx.x), e_step = (uint64_t)(kBlock >> kChunkBits) << (kChunkBits + g.nb_bits);
+        uint32_t ow[kCntE];
+#pragma unroll
+        for (int u = 0; u < kCntE; ++u) {
+            const uint64_t e = e_first + (uint64_t)u * e_step;
+            ow[u] = e < (uint64_t)m ? own[e] : 0u;
+        }
         for (uint32_t i = threadIdx.x; i < kBinEdges; i += kBlock) sh_cnt[i] = 0u;
         __syncthreads();
-        const uint32_t r0 = boff[b], r1 = boff[b + 1];
-        for (uint32_t r = r0 + threadIdx.x; r < r1; r += kBlock) {
-            const uint32_t k = key[r];
-            if ((int64_t)k < m) atomicAdd(&sh_cnt[g.local_of(k)], 1u);      // (the rest: keys of unused record positions)
+        for (uint64_t r = (uint64_t)r0 + threadIdx.x; r < r1; r += (uint64_t)kBlock * kCntU) {
+            uint32_t k[kCntU];
+            if (r < (uint64_t)r0 + kBlock) {                        // (workgroup-uniform) the first trip: loaded ahead
+#pragma unroll
+                for (int u = 0; u < kCntU; ++u) k[u] = kq[u];
+            } else {
+#pragma unroll
+                for (int u = 0; u < kCntU; ++u) {
+                    const uint64_t rr = r + (uint64_t)u * kBlock;
+                    k[u] = rr < r1 ? key[rr] : 0xFFFFFFFFu;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kCntU; ++u) {
+                const uint64_t rr = r + (uint64_t)u * kBlock;
+                if (rr < r1 && (int64_t)k[u] < m) atomicAdd(&sh_cnt[g.local_of(k[u])], 1u);      // (the rest: keys of unused record positions)
+            }
         }
         __syncthreads();
+        // (the own-role counts are taken delivery of before the next bin's keys are requested: the sums below then wait for
+        // nothing that is still in flight)
+#pragma unroll
+        for (int u = 0; u < kCntE; ++u) asm volatile("" : "+v"(ow[u]));
+        if (more) first_keys(n0, n1);
         uint32_t tb = 0;
-        for (uint32_t i = threadIdx.x; i < kBinEdges; i += kBlock) {
-            const uint64_t e = g.edge_of(b, i);
+#pragma unroll
+        for (int u = 0; u < kCntE; ++u) {
+            const uint32_t i = threadIdx.x + (uint32_t)u * kBlock;
+            const uint64_t e = e_first + (uint64_t)u * e_step;
             if (e >= (uint64_t)m) continue;
-            const uint32_t c = own[e] + sh_cnt[i];
+            const uint32_t c = ow[u] + sh_cnt[i];
             sum[e] = c;
             tb += c;
             if (c) lmin = min(lmin, (int32_t)c);

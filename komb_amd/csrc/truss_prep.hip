@@ -35,10 +35,20 @@ namespace komb {
 namespace {
 
 constexpr uint32_t kPrepHeavy = 2048;           // symmetric rows longer than this are walked in chunks by the whole grid (k_prep_kept_heavy)
-constexpr uint32_t kRowCap = 1024;              // oriented entries a wavefront sorts in LDS at a time; longer rows: k_prep_rows_heavy
+// A/B switches of k_prep_rows (compile time).  KOMB_ROW_CAP: 512 entries of LDS per wavefront are 35 KB
+// per workgroup -- 4 workgroups per CU, and the grid's 2048 are two full rounds; 1024 (until now) are 51 KB, 3 per CU
+#ifndef KOMB_ROW_CAP
+#define KOMB_ROW_CAP 512
+#endif
+#ifndef KOMB_ROWS_U
+#define KOMB_ROWS_U 4
+#endif
+constexpr uint32_t kRowCap = KOMB_ROW_CAP;      // oriented entries a wavefront sorts in LDS at a time; longer rows: k_prep_rows_heavy
 constexpr uint32_t kRowStage = 8192;            // ... which stages up to this many in LDS
 constexpr int kPW = kBlock / kWave;
 constexpr int kPrepU = 4;                       // trips of a wavefront whose loads are in flight together (k_prep_kept)
+constexpr int kRowsU = KOMB_ROWS_U;             // ... and of k_prep_rows' fill phase
+static_assert(kRowCap >= 1 && kRowCap <= kRowStage && kRowsU >= 1, "rows beyond kRowCap entries go to k_prep_rows_heavy, which stages up to kRowStage");
 
 // ---- 1. degrees as sort keys; first upper slot (column above row) of every row and how many there are
 __global__ __launch_bounds__(kBlock) void k_prep_vertex(const uint32_t *__restrict__ rowptr, const int32_t *__restrict__ col, int64_t nv,
@@ -250,6 +260,41 @@ __global__ __launch_bounds__(kBlock) void k_prep_dplus(int64_t nv, const int32_t
 // ---- 4. the oriented rows.  A wavefront takes 64 consecutive INTERNAL vertices; their lists (step 2: nlocal entries at the
 // front of the vertex' region, the rest behind its back cursor) are read into LDS in batches of <= kRowCap entries (whole
 // rows), every entry is ranked among its row's by counting, and leaves as the row's rank-th slot.
+// The kernel moves exactly its algorithmic bytes and lives on how many of them are in flight: 16 wavefronts per CU (LDS), so
+// the fill phase issues kRowsU loads of tmp per lane before it uses one (rows_fill_group), and a task's (orow, where_i) are
+// requested one task ahead.
+
+// one group of the fill phase, kRowsU trips of the wavefront over the batch's flattened entries k0 .. E - 1: the owner searches
+// (LDS) of all trips first, then all their loads of tmp, then the LDS stores.  No branch in it: a position at or beyond E (the
+// batch's last group) reads the batch's last entry once more -- an entry of the lists, on a line the wavefront reads anyway --
+// and stores nothing
+__device__ __forceinline__ void rows_fill_group(const uint2 *__restrict__ tmp, uint32_t k0, uint32_t E, int lane,
+                                                const uint32_t *s_end, const uint32_t *s_rp, const uint32_t *s_nl, const uint32_t *s_bk,
+                                                int32_t *s_b, uint32_t *s_kk)
+{
+    size_t src[kRowsU];
+    uint2 ent[kRowsU];
+#pragma unroll
+    for (int u = 0; u < kRowsU; ++u) {
+        const uint32_t k = min(k0 + (uint32_t)(u * kWave + lane), E - 1u);
+        const int t = owner_of(s_end, k);
+        const uint32_t first = t ? s_end[t - 1] : 0u;
+        const uint32_t idx = k - first, nl = s_nl[t];
+        src[u] = idx < nl ? (size_t)s_rp[t] + idx : (size_t)s_bk[t] + (idx - nl);
+    }
+#pragma unroll
+    for (int u = 0; u < kRowsU; ++u) ent[u] = tmp[src[u]];
+    // every lane takes delivery of all its loads here, whether it stores them or not: the compiler then sinks no load into a
+    // guarded store's branch, and carries no "maybe pending" load to a later wait that would also cover the rank phase's stores
+#pragma unroll
+    for (int u = 0; u < kRowsU; ++u) asm volatile("" : "+v"(ent[u].x), "+v"(ent[u].y));
+#pragma unroll
+    for (int u = 0; u < kRowsU; ++u) {
+        const uint32_t k = k0 + (uint32_t)(u * kWave + lane);
+        if (k < E) { s_b[k] = (int32_t)ent[u].x; s_kk[k] = ent[u].y; }
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_prep_rows(const uint32_t *__restrict__ orow, int64_t nv, const uint4 *__restrict__ where_i,
                                                       const uint2 *__restrict__ tmp, int32_t *__restrict__ ocol,
                                                       uint32_t *__restrict__ e2k, uint4 *__restrict__ line)
@@ -266,13 +311,27 @@ __global__ __launch_bounds__(kBlock) void k_prep_rows(const uint32_t *__restrict
     int32_t (*s_piv)[kPivots] = sh_piv[w];
     const int64_t gw = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * kBlock) >> 6;
     const int64_t ntasks = (nv + kWave - 1) / kWave;
+    // (orow[a], orow[a + 1], where_i[a]) of the wavefront's NEXT task: loaded while the current one is filled and ranked
+    uint32_t n_ob = 0u, n_oe = 0u;
+    uint4 n_wh = make_uint4(0u, 0u, 0u, 0u);
+    if (gw < ntasks && gw * kWave + lane < nv) { const int64_t a = gw * kWave + lane; n_ob = orow[a]; n_oe = orow[a + 1]; n_wh = where_i[a]; }
+    // (the first task's have arrived before the loop is entered: inside it, only the loads for the task ahead are pending
+    // when a task's own values are first used, and nothing waits for them)
+    asm volatile("" : "+v"(n_ob), "+v"(n_oe), "+v"(n_wh.x), "+v"(n_wh.y), "+v"(n_wh.z));
     for (int64_t task = gw; task < ntasks; task += nw) {
         const int64_t a0 = task * kWave, a = a0 + lane;
         const bool has = a < nv;
-        const uint32_t ob = has ? orow[a] : 0u, d = has ? orow[a + 1] - ob : 0u;
+        const uint32_t ob = n_ob, d = n_oe - n_ob;                 // (0, 0 beyond the last vertex)
         const bool big = d > kRowCap;
-        const uint4 wh = has ? where_i[a] : make_uint4(0u, 0u, 0u, 0u);
+        const uint4 wh = n_wh;
         const uint32_t len = big ? 0u : d;
+        {
+            const int64_t an = a + nw * kWave;
+            const bool hn = task + nw < ntasks && an < nv;
+            n_ob = hn ? orow[an] : 0u;
+            n_oe = hn ? orow[an + 1] : 0u;
+            n_wh = hn ? where_i[an] : make_uint4(0u, 0u, 0u, 0u);
+        }
         __builtin_amdgcn_wave_barrier();
         s_rp[lane] = wh.x;                                         // the vertex' own edges: tmp[wh.x .. + wh.y)
         s_nl[lane] = wh.y;
@@ -290,13 +349,8 @@ __global__ __launch_bounds__(kBlock) void k_prep_rows(const uint32_t *__restrict
             __builtin_amdgcn_wave_barrier();
             s_end[lane] = lane < done ? 0u : (lane < r1 ? incl : 0xFFFFFFFFu);
             __builtin_amdgcn_wave_barrier();
-            for (uint32_t k = (uint32_t)lane; k < E; k += kWave) {
-                const int t = owner_of(s_end, k);
-                const uint32_t first = t ? s_end[t - 1] : 0u;
-                const uint32_t idx = k - first, nl = s_nl[t];
-                const uint2 ent = tmp[idx < nl ? (size_t)s_rp[t] + idx : (size_t)s_bk[t] + (idx - nl)];
-                s_b[k] = (int32_t)ent.x; s_kk[k] = ent.y;
-            }
+            for (uint32_t k0 = 0; k0 < E; k0 += (uint32_t)(kWave * kRowsU))          // (E = 0: a batch of empty rows)
+                rows_fill_group(tmp, k0, E, lane, s_end, s_rp, s_nl, s_bk, s_b, s_kk);
             __builtin_amdgcn_wave_barrier();
             for (uint32_t k = (uint32_t)lane; k < E; k += kWave) {
                 const int t = owner_of(s_end, k);
