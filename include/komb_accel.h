@@ -120,7 +120,7 @@ int         komb_abi_version(void);
  * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
  * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), MAXIMAL_LDS,
  * MAXIMAL_PIVOT, MAXIMAL_LIST, MAXIMAL_DEBUG (komb_maximal_cliques_run, below), PERC_GROUP, PERC_DEBUG
- * (komb_clique_communities_run, below), and the
+ * (komb_clique_communities_run, below), BICONN_HEAVY (komb_biconnected_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -276,6 +276,48 @@ int komb_truss_communities_fetch(komb_ctx *ctx, int32_t *label /*[ne_sub]*/, int
 int komb_truss_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm /*[nv]*/);
 int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edges, int64_t *n_communities,
                                 int64_t *largest, int64_t *n_multi_vertices, double *ms);                 /* any may be NULL */
+
+/* ---- biconnected components, articulation points, bridges ------------------ */
+/* Which single vertices and which single edges hold the k-truss together: the blocks of Tarjan & Vishkin ("An efficient
+ * parallel biconnectivity algorithm", SIAM J. Comput. 1985), on a breadth-first spanning forest.  Input: the last
+ * completed k-truss result, whole graph or vmask run alike -- ne_sub canonical edges (eu[i], ev[i]) with trussness
+ * truss[i] -- and a threshold k.  Member edges: truss[i] >= k; 0 <= k <= 2 is run as 2 (every edge of the result) and
+ * k_used reports 2; member vertices: the endpoints of member edges.
+ * A BLOCK (biconnected component) is a maximal set of member edges any two of which lie on a common simple cycle; an edge
+ * on no cycle is a block of its own, a BRIDGE.  block[i] is the SMALLEST canonical edge index of i's block, -1 for a
+ * non-member; size[i] is the number of edges of that block, 0 for a non-member; a member edge is a bridge exactly when
+ * size[i] == 1.  n_blocks[v], per original vertex, is the number of blocks that contain v (0 for a non-member): v is an
+ * ARTICULATION POINT -- its removal separates its component -- exactly when n_blocks[v] >= 2.  ecc_label[v] is the smallest
+ * vertex id of v's 2-edge-connected component (the connected component of v once all bridges are removed), -1 for a
+ * non-member; ecc_size[v] is that component's number of vertices, 0 for a non-member.  The block list, in ascending rep
+ * order: rep (= block[] of its edges), n_edges, n_verts; komb_biconnected_count gives its length.  Everything is fully
+ * determined by the graph: it does not depend on the run, on the spanning forest, on an option or on scheduling.
+ * komb_biconnected_info: the threshold applied, the member edges and vertices, the blocks, the bridges, the articulation
+ * points, the edges of the largest block, the 2-edge-connected components and the vertices of the largest one, depth --
+ * the number of levels of the spanning forest (0 without members) -- and ms, the device time of komb_biconnected_run on
+ * the context's HIP-event timer.  A run is four launches and one small read per level of the forest plus a constant
+ * number: its cost grows with depth.  Assembly-derived power-law graphs have depths in the tens; a long path has its
+ * length, and depth is reported so that a caller can see it.
+ * k < -1: KOMB_ERR_ARG.  No graph loaded: KOMB_ERR_ARG.  Without a completed k-truss result on this graph, or after
+ * komb_truss_run_slice / a sharded run that materialised only part of the canonical edges: KOMB_ERR_STATE; count / fetch /
+ * info before a run on the current result: KOMB_ERR_STATE.  A failing call writes nothing to its outputs.  k above the
+ * largest trussness: no members, every count 0, not an error.  A result with no edges has no members, and k_used is 2
+ * under KOMB_BICONN_K_MAX.  Canonical endpoints of a whole-graph result that no fetch has asked for yet are made here as
+ * that fetch makes them.  More than 2^31 - 1 member edges do not fit the 32-bit row offsets: KOMB_ERR_LIMIT.
+ * The result lives in arrays of its own, and its reps index the canonical edge list of the k-truss result it was computed
+ * from: whatever replaces or drops that result -- a new k-truss run of any kind, komb_truss_unprepare, a graph load --
+ * drops it too.  k-core, onion, components, communities and CoreA calls neither change nor drop it; a run changes none
+ * of their results, no komb_stats field and not the resident k-truss preparation.  Option BICONN_HEAVY (tests) moves the
+ * row length above which a frontier vertex' row is walked by its wave; it changes no result. */
+#define KOMB_BICONN_K_MAX (-1)   /* k = the largest trussness of the result (2 when it has no edges) */
+int komb_biconnected_run(komb_ctx *ctx, int32_t k);
+int komb_biconnected_count(komb_ctx *ctx, int64_t *n_blocks);
+int komb_biconnected_fetch_edges(komb_ctx *ctx, int32_t *block /*[ne_sub]*/, int32_t *size /*[ne_sub]*/);       /* either may be NULL */
+int komb_biconnected_fetch_vertices(komb_ctx *ctx, int32_t *n_blocks, int32_t *ecc_label, int32_t *ecc_size);     /* [nv] each, any may be NULL */
+int komb_biconnected_fetch_blocks(komb_ctx *ctx, int32_t *rep, int32_t *n_edges, int32_t *n_verts);               /* [n_blocks] each, any may be NULL */
+int komb_biconnected_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edges, int64_t *n_member_vertices,
+                          int64_t *n_blocks, int64_t *n_bridges, int64_t *n_articulation, int64_t *largest_block,
+                          int64_t *n_ecc, int64_t *largest_ecc, int32_t *depth, double *ms);                     /* any may be NULL */
 
 /* ---- k-truss community hierarchy: the nesting forest of the communities over all k ---- */
 /* All thresholds at once: which k-truss community lies inside which community of a smaller k (the index of Huang et al.

@@ -52,6 +52,7 @@ class KombStats(ctypes.Structure):
 KOMB_CREATE_NULL_STREAM, KOMB_CREATE_NO_WARMUP, KOMB_CREATE_WARM_UPLOAD = 1, 2, 4
 KOMB_COMP_CORE, KOMB_COMP_TRUSS, KOMB_COMP_K_MAX = 0, 1, -1
 KOMB_COMM_K_MAX = -1
+KOMB_BICONN_K_MAX = -1
 KOMB_DENSEST_CORE, KOMB_DENSEST_PREFIX = 0, 1
 KOMB_SC_OUTLIER, KOMB_SC_HUB, KOMB_SC_BORDER, KOMB_SC_CORE = 0, 1, 2, 3
 KOMB_MAXCLQ_EXACT, KOMB_MAXCLQ_ENUMERATED, KOMB_MAXCLQ_LISTED = 1, 2, 4
@@ -98,6 +99,14 @@ SIGNATURES = {
     "komb_truss_communities_fetch_vertices": (_i32, [_vp, _vp]),
     "komb_truss_communities_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                            ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_biconnected_run": (_i32, [_vp, ctypes.c_int32]),
+    "komb_biconnected_count": (_i32, [_vp, ctypes.POINTER(_i64)]),
+    "komb_biconnected_fetch_edges": (_i32, [_vp, _vp, _vp]),
+    "komb_biconnected_fetch_vertices": (_i32, [_vp, _vp, _vp, _vp]),
+    "komb_biconnected_fetch_blocks": (_i32, [_vp, _vp, _vp, _vp]),
+    "komb_biconnected_info": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                     ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                     ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]),
     "komb_community_hierarchy_run": (_i32, [_vp]),
     "komb_community_hierarchy_count": (_i32, [_vp, ctypes.POINTER(_i64)]),
     "komb_community_hierarchy_fetch_nodes": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),

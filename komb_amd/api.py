@@ -43,7 +43,7 @@ OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_
                 "REC_CAP", "OWN_DENSE_CAP", "NO_OWN_DENSE", "NO_REC_SCRATCH", "NO_FIRST_QUEUE", "FULL_CAPS", "PREP_ROW_STAGE", "RETIRE_EVERY", "SHARD_ENGINE",
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
                 "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "CENSUS_LDS", "CENSUS_PIVOT",
-                "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "PERC_GROUP", "PERC_DEBUG",
+                "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "PERC_GROUP", "PERC_DEBUG", "BICONN_HEAVY",
                 "POISON")
 
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
@@ -382,6 +382,59 @@ class KombAccel:
         """label, size of the k-truss communities of the last k-truss result."""
         self.truss_communities_run(k)
         return self.truss_communities_fetch()
+
+    # ---- biconnected components, articulation points, bridges of the k-truss (include/komb_accel.h)
+    BICONN_INFO = (("k_used", ctypes.c_int32), ("n_member_edges", ctypes.c_int64), ("n_member_vertices", ctypes.c_int64),
+                   ("n_blocks", ctypes.c_int64), ("n_bridges", ctypes.c_int64), ("n_articulation", ctypes.c_int64),
+                   ("largest_block", ctypes.c_int64), ("n_ecc", ctypes.c_int64), ("largest_ecc", ctypes.c_int64),
+                   ("depth", ctypes.c_int32), ("ms", ctypes.c_double))
+
+    def biconnected_run(self, k=2):
+        """k: the trussness threshold (0..2 run as 2), -1 (KOMB_BICONN_K_MAX) for the largest trussness of the result."""
+        self._sync_env_options()
+        self._check(self._lib.komb_biconnected_run(self._ctx, k))
+
+    def biconnected_count(self):
+        """The number of blocks of the last komb_biconnected_run."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_biconnected_count(self._ctx, ctypes.byref(n)))
+        return n.value
+
+    def biconnected_fetch_edges(self):
+        """(block, size) int32[ne_sub] in the canonical edge order of the k-truss result: the smallest canonical edge index
+        of the edge's block (-1: not a member) and its number of edges (1: a bridge)."""
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_biconnected_count(self._ctx, None))     # (the blocks' own errors first: no graph, no run)
+        self._check(self._lib.komb_truss_count(self._ctx, ctypes.byref(n)))
+        block = _out_i32(max(n.value, 0))
+        size = _out_i32(max(n.value, 0))
+        self._check(self._lib.komb_biconnected_fetch_edges(self._ctx, ptr(block), ptr(size)))
+        return block, size
+
+    def biconnected_fetch_vertices(self):
+        """(n_blocks, ecc_label, ecc_size) int32[nv]: the blocks that contain the vertex (>= 2: an articulation point), the
+        smallest id of its 2-edge-connected component (-1: not a member) and that component's vertices."""
+        out = [_out_i32(max(self.nv, 0)) for _ in range(3)]
+        self._check(self._lib.komb_biconnected_fetch_vertices(self._ctx, *(ptr(x) for x in out)))
+        return tuple(out)
+
+    def biconnected_fetch_blocks(self):
+        """{"rep", "n_edges", "n_verts"}: int32[n_blocks] each, blocks in ascending rep order."""
+        n = self.biconnected_count()
+        out = {name: _out_i32(max(n, 0)) for name in ("rep", "n_edges", "n_verts")}
+        self._check(self._lib.komb_biconnected_fetch_blocks(self._ctx, *(ptr(x) for x in out.values())))
+        return out
+
+    def biconnected_info(self):
+        """A dict keyed by the C names of komb_biconnected_info's outputs."""
+        vals = [t() for _, t in self.BICONN_INFO]
+        self._check(self._lib.komb_biconnected_info(self._ctx, *(ctypes.byref(x) for x in vals)))
+        return {name: x.value for (name, _), x in zip(self.BICONN_INFO, vals)}
+
+    def run_biconnected(self, k=2):
+        """block, size of the biconnected components of the last k-truss result."""
+        self.biconnected_run(k)
+        return self.biconnected_fetch_edges()
 
     # ---- k-truss community hierarchy: the nesting forest of the communities over all k (include/komb_accel.h)
     def community_hierarchy_run(self):

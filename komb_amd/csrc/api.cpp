@@ -359,6 +359,83 @@ int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_membe
     return KOMB_OK;
 }
 
+int komb_biconnected_run(komb_ctx *ctx, int32_t k)
+{
+    KOMB_HIER_ENTER(ctx, "komb_biconnected_run");
+    if (k < KOMB_BICONN_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_biconnected_run: bad threshold %d", k);
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_run: no completed k-truss result on this graph");
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    if (k == KOMB_BICONN_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
+    if (k < 2) k = 2;
+    return biconnected_run(ctx, k);
+}
+
+int komb_biconnected_count(komb_ctx *ctx, int64_t *n_blocks)
+{
+    KOMB_HIER_ENTER(ctx, "komb_biconnected_count");
+    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_count: no blocks of the current k-truss result");
+    if (n_blocks) *n_blocks = ctx->bc.n_blocks;
+    return KOMB_OK;
+}
+
+int komb_biconnected_fetch_edges(komb_ctx *ctx, int32_t *block, int32_t *size)
+{
+    KOMB_HIER_ENTER(ctx, "komb_biconnected_fetch_edges");
+    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_fetch_edges: no blocks of the current k-truss result");
+    const size_t bytes = (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0) * sizeof(int32_t);
+    if (bytes == 0) return KOMB_OK;
+    if (block) KOMB_HIP(ctx, staged_copy(ctx, block, ctx->d_bc_block, bytes, false));
+    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_bc_size, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_biconnected_fetch_vertices(komb_ctx *ctx, int32_t *n_blocks, int32_t *ecc_label, int32_t *ecc_size)
+{
+    KOMB_HIER_ENTER(ctx, "komb_biconnected_fetch_vertices");
+    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_fetch_vertices: no blocks of the current k-truss result");
+    if (ctx->nv == 0) return KOMB_OK;
+    const size_t bytes = (size_t)ctx->nv * sizeof(int32_t);
+    if (n_blocks) KOMB_HIP(ctx, staged_copy(ctx, n_blocks, ctx->d_bc_nblocks, bytes, false));
+    if (ecc_label) KOMB_HIP(ctx, staged_copy(ctx, ecc_label, ctx->d_bc_ecc_label, bytes, false));
+    if (ecc_size) KOMB_HIP(ctx, staged_copy(ctx, ecc_size, ctx->d_bc_ecc_size, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_biconnected_fetch_blocks(komb_ctx *ctx, int32_t *rep, int32_t *n_edges, int32_t *n_verts)
+{
+    KOMB_HIER_ENTER(ctx, "komb_biconnected_fetch_blocks");
+    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_fetch_blocks: no blocks of the current k-truss result");
+    if (ctx->bc.n_blocks == 0) return KOMB_OK;
+    const size_t n = (size_t)ctx->bc.n_blocks, bytes = n * sizeof(int32_t);
+    int32_t *const out[3] = {rep, n_edges, n_verts};
+    for (int i = 0; i < 3; ++i)
+        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_bc_list + i * n, bytes, false));
+    return KOMB_OK;
+}
+
+int komb_biconnected_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edges, int64_t *n_member_vertices, int64_t *n_blocks,
+                          int64_t *n_bridges, int64_t *n_articulation, int64_t *largest_block, int64_t *n_ecc, int64_t *largest_ecc,
+                          int32_t *depth, double *ms)
+{
+    KOMB_HIER_ENTER(ctx, "komb_biconnected_info");
+    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_info: no blocks of the current k-truss result");
+    const komb_ctx::Biconnected &r = ctx->bc;
+    if (k_used) *k_used = r.k;
+    if (n_member_edges) *n_member_edges = r.n_member_edges;
+    if (n_member_vertices) *n_member_vertices = r.n_member_vertices;
+    if (n_blocks) *n_blocks = r.n_blocks;
+    if (n_bridges) *n_bridges = r.n_bridges;
+    if (n_articulation) *n_articulation = r.n_articulation;
+    if (largest_block) *largest_block = r.largest_block;
+    if (n_ecc) *n_ecc = r.n_ecc;
+    if (largest_ecc) *largest_ecc = r.largest_ecc;
+    if (depth) *depth = r.depth;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
 int komb_densest_subgraph_run(komb_ctx *ctx, int32_t iters)
 {
     KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_run");

@@ -328,6 +328,22 @@ struct komb_ctx {
     double comm_ms = 0.0, comm_ms_vertices = 0.0;   // device time of the run | of the vertex pass (HIP events)
     bool comm_done = false, comm_v_ready = false;
 
+    // ---- biconnected components (biconnected.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
+    // computed from and dropped with it (truss_free)
+    int32_t *d_bc_block = nullptr;           // [t_ne] smallest canonical edge index of the edge's block, -1 for a non-member
+    int32_t *d_bc_size = nullptr;            // [t_ne] edges of that block, 0 for a non-member (1: a bridge)
+    int32_t *d_bc_nblocks = nullptr;         // [nv] blocks that contain the vertex (>= 2: an articulation point)
+    int32_t *d_bc_ecc_label = nullptr;       // [nv] smallest ORIGINAL id of the vertex' 2-edge-connected component, -1 for a non-member
+    int32_t *d_bc_ecc_size = nullptr;        // [nv] vertices of that component, 0 for a non-member
+    int32_t *d_bc_list = nullptr;            // [3 * n_blocks] rep | n_edges | n_verts of the blocks in ascending rep order
+    struct Biconnected {
+        int32_t k = 0, depth = 0;            // the threshold of the last run (resolved) | the levels of its spanning forest
+        int64_t n_member_edges = 0, n_member_vertices = 0, n_blocks = 0, n_bridges = 0, n_articulation = 0, largest_block = 0,
+                n_ecc = 0, largest_ecc = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+    } bc;
+    bool bc_done = false;
+
     // ---- k-truss community hierarchy (community_hierarchy.hip): the nesting forest of the communities over all k, in pool blocks
     // of its own, indexed like the k-truss result it was computed from and dropped with it (truss_free)
     int32_t *d_ch_nodes = nullptr;           // [5 * ch_cap] k | rep | parent | size | shell, each a block of ch_cap words with ch_nodes in use
@@ -620,6 +636,8 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind);               // hierarchy.hip: 
 int communities_run(komb_ctx *ctx, int32_t k);                // communities.hip: k checked and resolved by the caller
 int communities_vertices(komb_ctx *ctx);                      // communities.hip: n_comm[] and the multi-community count, made on first request
 void communities_drop(komb_ctx *ctx);                         // communities.hip: the result goes with the k-truss result it indexes
+int biconnected_run(komb_ctx *ctx, int32_t k);                // biconnected.hip: k checked and resolved by the caller
+void biconnected_drop(komb_ctx *ctx);                         // biconnected.hip: the result goes with the k-truss result it indexes
 int community_hierarchy_run(komb_ctx *ctx);                   // community_hierarchy.hip: the k-truss result it needs checked by the caller
 int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
 void community_hierarchy_drop(komb_ctx *ctx);                 // community_hierarchy.hip: the result goes with the k-truss result it indexes

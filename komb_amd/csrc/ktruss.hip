@@ -279,6 +279,7 @@ void truss_free(komb_ctx *ctx)
 {
     communities_drop(ctx);                   // (its labels index this result's canonical edges)
     community_hierarchy_drop(ctx);           // (so do the community hierarchy's reps and node[])
+    biconnected_drop(ctx);                   // (and the blocks' reps and block[])
     structural_drop(ctx);                    // (and the structural clustering's similar[]; its d and sim_deg are this result's)
     nucleus_drop(ctx);                       // (and the nucleus decomposition's triangles and edge_theta[])
     max_clique_drop(ctx);                    // (and the maximum cliques: they are this result's)

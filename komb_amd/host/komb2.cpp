@@ -33,6 +33,20 @@
 //                       community's number of edges.  truss_community_vertices.tsv: #VID, Name, Communities -- the
 //                       unitigs with a member edge and the number of communities they belong to (more than one: a
 //                       unitig shared between dense regions).  Nothing else changes.
+//   KOMB_BICONNECTED=<k>|max  with KOMB_TRUSS=1: also write, after the truss stage, the biconnected components of the WHOLE
+//                       graph's k-truss (a k-truss run of its own, made once the stage and its tables are done, and
+//                       komb_biconnected_run on its edges of trussness >= k, max: the largest trussness; the stage's own
+//                       subject is the max core, one dense piece; what holds the assembly graph together shows on the
+//                       whole graph).
+//                       truss_blocks.tsv: #VID_U, Name_U, VID_V, Name_V, Trussness, Block, Size, Bridge -- one row per
+//                       member edge in canonical order, Block numbering the blocks from 0 in the order of their first
+//                       edge, Size the block's number of edges, Bridge 1 for an adjacency whose loss separates its two
+//                       unitigs (a block of one edge), else 0.  truss_articulation.tsv: #VID, Name, Blocks, Articulation,
+//                       Component2E, Size2E -- one row per unitig with a member edge in VID order: the blocks it lies in,
+//                       1 when its loss separates the graph (more than one block), the Name of the smallest-VID unitig of
+//                       its 2-edge-connected component (what stays connected once the bridges are removed) and that
+//                       component's number of unitigs.  VIDs depend on -t, so only the tables by Name compare between
+//                       runs.  Nothing else changes.
 //   KOMB_DENSEST=<rounds>   also write, after kcore.tsv, the densest subgraph komb_densest_subgraph_run(rounds) finds on
 //                       the coreness: densest_subgraph.tsv -- #VID, Name, Coreness, Load, members only, in VID order -- and
 //                       core_density.tsv -- #K, Vertices, Edges, the vertices of coreness >= K and the edges between two
@@ -792,6 +806,64 @@ void write_communities(komb_ctx *ctx, const std::string &outdir, const Names &na
     fclose(fp);
 }
 
+// KOMB_BICONNECTED: a whole-graph k-truss run of its own (the max core, the truss stage's subject, is one dense piece) and
+// komb_biconnected_run on it as two tables (edges in canonical order, vertices in VID order)
+void write_biconnected(komb_ctx *ctx, int32_t k, const std::string &outdir, const Names &names, int64_t nv, int threads)
+{
+    int rc = komb_truss_run(ctx, nullptr);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_truss_run", rc);
+    int64_t ne = 0;
+    komb_truss_count(ctx, &ne);
+    std::vector<int32_t> eu((size_t)ne), ev((size_t)ne), tr((size_t)ne);
+    rc = komb_truss_fetch(ctx, eu.data(), ev.data(), tr.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_truss_fetch", rc);
+    rc = komb_biconnected_run(ctx, k);
+    if (rc != KOMB_OK) die_accel(ctx, "komb_biconnected_run", rc);
+    std::vector<int32_t> block((size_t)ne), size((size_t)ne), rank((size_t)ne, -1), n_blocks((size_t)nv), ecc((size_t)nv), ecc_size((size_t)nv);
+    rc = komb_biconnected_fetch_edges(ctx, block.data(), size.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_biconnected_fetch_edges", rc);
+    rc = komb_biconnected_fetch_vertices(ctx, n_blocks.data(), ecc.data(), ecc_size.data());
+    if (rc != KOMB_OK) die_accel(ctx, "komb_biconnected_fetch_vertices", rc);
+    int32_t next = 0;
+    for (int64_t i = 0; i < ne; ++i)                       // a label is the block's first edge: ranks in ascending label order
+        if (block[(size_t)i] == (int32_t)i) rank[(size_t)i] = next++;
+    std::string path = outdir + "/truss_blocks.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID_U\tName_U\tVID_V\tName_V\tTrussness\tBlock\tSize\tBridge\n");
+    write_rows(fp, ne, threads, [&](int64_t i, std::string &buf) {
+        if (block[(size_t)i] < 0) return;
+        char tmp[80];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)eu[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)eu[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t", (int)ev[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)ev[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\t%d\t%d\n", (int)tr[(size_t)i], (int)rank[(size_t)block[(size_t)i]], (int)size[(size_t)i],
+                       size[(size_t)i] == 1 ? 1 : 0);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    path = outdir + "/truss_articulation.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tBlocks\tArticulation\tComponent2E\tSize2E\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        if (ecc[(size_t)i] < 0) return;
+        char tmp[64];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\t", (int)n_blocks[(size_t)i], n_blocks[(size_t)i] >= 2 ? 1 : 0);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)ecc[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%d\n", (int)ecc_size[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
 // KOMB_NUCLEUS: komb_nucleus_run on the truss stage's result as two tables (triangles in triangle order, the result's unitigs in VID order)
 void write_nucleus(komb_ctx *ctx, const std::string &outdir, const Names &names, int64_t nv, int threads,
                    const std::vector<int32_t> &eu, const std::vector<int32_t> &ev)
@@ -1452,6 +1524,19 @@ int main(int argc, const char **argv)
         }
     }
 
+    // biconnected components of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
+    const char *bc_env = getenv("KOMB_BICONNECTED");
+    const bool bc_on = bc_env && *bc_env;
+    long bc_k = (long)KOMB_BICONN_K_MAX;
+    if (bc_on && strcmp(bc_env, "max") != 0) {
+        char *end = nullptr;
+        bc_k = strtol(bc_env, &end, 10);
+        if (*end || bc_k < 0 || bc_k > 2147483647L) {
+            fprintf(stderr, "komb2: KOMB_BICONNECTED=%s: expected a trussness threshold >= 0 or max\n", bc_env);
+            leave(EXIT_FAILURE);
+        }
+    }
+
     // (3,4)-nucleus decomposition of the truss stage's result (no counterpart in the reference; opt-in, needs KOMB_TRUSS=1)
     const char *nuc_env = getenv("KOMB_NUCLEUS");
     const bool nuc_on = nuc_env && !strcmp(nuc_env, "1");
@@ -1634,6 +1719,7 @@ int main(int argc, const char **argv)
             write_hierarchy(ctx, KOMB_COMP_TRUSS, args.outdir, "truss", "Trussness", names, nv, args.threads,
                             [&](int64_t i) { return (int)lvl[(size_t)i]; });
         }
+        if (bc_on) write_biconnected(ctx, (int32_t)bc_k, args.outdir, names, nv, args.threads);   // (last: it replaces the stage's k-truss result)
     }
     fprintf(stdout, "\nTime elapsed doing K-core decomposition: %.3f s\n", since(t0));
     fprintf(stdout, "Created Kcore\n");
