@@ -294,13 +294,6 @@ __global__ void k_pc_vfix(const int32_t *__restrict__ v_comm, int32_t *__restric
 
 inline int pc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
-inline int pc_bits(int64_t n)                            // bits that hold every value below n
-{
-    int b = 1;
-    while (b < 31 && (1ll << b) < n) ++b;
-    return b;
-}
-
 } // namespace
 
 void clique_communities_drop(komb_ctx *ctx)
@@ -377,7 +370,7 @@ int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_msize, d_mpos, nc));
         k_pc_keys<<<pc_grid(words), kBlock, 0, s>>>(d_off, d_verts, d_msize, d_mpos, unc, uw, unv, d_keys, A.ctl);
         KOMB_HIP(ctx, hipGetLastError());
-        KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, entries, 32 + pc_bits(nv), &d_sorted));
+        KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, entries, 32 + key_bits(nv), &d_sorted));
         k_pc_rows<<<pc_grid(entries), kBlock, 0, s>>>(d_sorted, ue, unv, unc, d_row, d_rs, d_re, A.ctl);
         KOMB_HIP(ctx, hipGetLastError());
         // ---- the pivots and pair_tests, before anything is linked
@@ -426,7 +419,7 @@ int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
         // ---- the communities' vertices: keys (community, vertex) of every member clique's vertices, sorted, distinct
         k_pc_ckeys<<<pc_grid(words), kBlock, 0, s>>>(d_off, d_verts, d_msize, d_mpos, d_label, d_cnum, unc, uw, d_keys);
         KOMB_HIP(ctx, hipGetLastError());
-        KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, entries, 32 + pc_bits(n_comm), &d_sorted));
+        KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, entries, 32 + key_bits(n_comm), &d_sorted));
         uint64_t *d_uniq = d_sorted == d_keys ? d_keys_alt : d_keys;
         int64_t n_uniq = 0;
         KOMB_TRY(prim_unique_u64(ctx, d_sorted, d_uniq, entries, &n_uniq));

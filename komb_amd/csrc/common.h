@@ -583,6 +583,12 @@ inline hipError_t d2h(komb_ctx *ctx, void *dst, const void *src, size_t bytes)
 // ---- primitives implemented in prims.hip (rocPRIM/hipCUB behind plain signatures)
 namespace komb {
 int prim_sort_u64(komb_ctx *ctx, uint64_t *keys, uint64_t *tmp_keys, int64_t n, int end_bit, uint64_t **sorted);
+inline int key_bits(int64_t n)                            // bits that hold every value below n: the end_bit of a sort by such a field
+{
+    int b = 1;
+    while (b < 31 && (1ll << b) < n) ++b;
+    return b;
+}
 int prim_unique_u64(komb_ctx *ctx, const uint64_t *in, uint64_t *out, int64_t n, int64_t *n_out);
 int prim_exclusive_sum_u32(komb_ctx *ctx, const uint32_t *in, uint32_t *out, int64_t n);   // out[n-1] valid; in/out may alias
 int prim_exclusive_sum_u32_u64(komb_ctx *ctx, const uint32_t *in, unsigned long long *out, int64_t n);

@@ -28,7 +28,7 @@
 //     host after the launch.  A stale best only costs nodes.
 //   * nodes: every wave adds its nodes to one counter in batches of at most 256 and reads the counter at every node; once it has
 //     reached the budget the wave stops.  The overshoot is at most 256 per wave (KOMB_MAXCLQ_OVERSHOOT in all).
-// The launches of a run: k_clq_rows, k_mc_tmax; then per phase (seed, search, enumeration) k_mc_search in count mode (the
+// The launches of a run: k_clq_rows, k_clq_tmax; then per phase (seed, search, enumeration) k_mc_search in count mode (the
 // largest |P|, which sizes the scratch slots and the LDS) and in the phase's mode; k_mc_verify on the witness; k_mc_mark when
 // the counts are the witness' own.  No workgroup waits for another; every loop runs over a row part, a candidate set or a
 // stack that is bounded before it starts, and the node counter bounds the search as a whole.
@@ -40,45 +40,19 @@ namespace komb {
 
 namespace {
 
-constexpr int kMcGrid = 1024;                         // wavefronts (workgroups of one) of a launch
-constexpr uint32_t kMcBatch = 256;                    // nodes a wave adds to the counter at once, at most
-static_assert((long long)kMcGrid * kMcBatch == KOMB_MAXCLQ_OVERSHOOT, "the documented overshoot");
-constexpr uint32_t kMcLdsCand = 512;                  // default and largest MAXCLQ_LDS: 512 x 8 words = 32 KiB
-constexpr size_t kMcLdsBytes = 56u << 10;             // LDS of a workgroup (below the 64 KiB a launch gets without asking)
-constexpr size_t kMcScratchBytes = 512ull << 20;      // all scratch slots of a launch together
 constexpr int kMcSeedWaves = 64;                      // greedy dives of the seed
-constexpr long long kMcDefaultBudget = 1ll << 30;
-constexpr long long kMcMaxBudget = 0x7FFFFFFFll - KOMB_MAXCLQ_OVERSHOOT;   // nodes (and so every count[v]) fit int32
 constexpr long long kMcListDefault = 65536;
 
 enum McMode : int { MC_COUNT = 0, MC_SEED = 1, MC_SEARCH = 2, MC_ENUM = 3 };
 
-struct McCtl {                                        // 64 bytes, zeroed before every run
-    unsigned long long nodes;                         // nodes spent, all phases
-    unsigned long long n_cliques;                     // enumeration: leaves of size omega
-    unsigned long long n_roots;                       // roots opened
-    uint32_t cursor;                                  // next chunk of 64 canonical edges (zeroed before every launch)
-    uint32_t best;                                    // the largest clique found
-    uint32_t t_max;
-    uint32_t max_p;                                   // count mode: the largest |P|
-    uint32_t bad;                                     // an inconsistency (cannot happen; checked)
-    uint32_t stopped;                                 // a wave found the budget spent
-    uint32_t pad[4];
-};
-static_assert(sizeof(McCtl) == 64, "McCtl layout");
-
 struct McArgs {
-    const int32_t *eu, *ev, *tr;
-    const uint32_t *rs, *re;
+    ClqGraph g;
     uint32_t m, n_chunks;
-    McCtl *ctl;
+    ClqCtl *ctl;
     int mode;
     uint32_t need;                                    // count / seed / enumeration: the threshold of roots and edges (the search reads best)
     unsigned long long budget;
-    unsigned char *scratch;                           // slot b: P[cap_p] | mat[cap_p * w_max] | stk[levels * w_max]
-    size_t slot_bytes, off_mat, off_stk;
-    uint32_t cap_p, levels;
-    uint32_t lds_cand, lds_levels, lds_off_mat, lds_off_stk;   // LDS: cur[levels] | mat | stk (offsets in 64-bit words); lds_levels == 0: the stack is global
+    ClqLayout lay;                                    // the candidates are P; LDS head: cur[levels]; one set per stack level
     int32_t *wit;                                     // witness table: row s = a clique of s vertices
     uint32_t *wit_owner, wit_stride;
     int32_t *count, *list;                            // enumeration
@@ -86,63 +60,34 @@ struct McArgs {
     uint32_t omega;
 };
 
-__global__ void k_mc_tmax(const int32_t *__restrict__ tr, uint32_t m, McCtl *ctl, uint32_t best0)
-{
-    int32_t hi = 0;
-    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock) { const int32_t t = tr[j]; hi = t > hi ? t : hi; }
-    for (int off = kWave / 2; off > 0; off >>= 1) { const int32_t other = __shfl_xor(hi, off); hi = other > hi ? other : hi; }
-    if ((threadIdx.x & (kWave - 1)) == 0 && hi > 0) atomicMax(&ctl->t_max, (uint32_t)hi);
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&ctl->best, best0);
-}
-
-__device__ __forceinline__ uint32_t mc_best(McCtl *ctl) { return __hip_atomic_load(&ctl->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long mc_nodes(McCtl *ctl) { return __hip_atomic_load(&ctl->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-struct McWave { uint32_t nodes, roots, max_p; bool stop; };
-
-__device__ __forceinline__ void mc_flush(McCtl *ctl, McWave &w, int lane)
-{
-    if (lane == 0 && w.nodes) atomicAdd(&ctl->nodes, (unsigned long long)w.nodes);
-    w.nodes = 0;
-}
+__device__ __forceinline__ uint32_t mc_best(ClqCtl *ctl) { return __hip_atomic_load(&ctl->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // One root: canonical edge rj = (a, b).  Every branch below is uniform over the wave.
-__device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned long long *smem, McWave &w, int lane)
+__device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned long long *smem, ClqWave &w, int lane)
 {
-    McCtl *ctl = A.ctl;
-    const ClqGraph G{A.eu, A.ev, A.tr, A.rs, A.re};
-    const int32_t a = A.eu[rj], b = A.ev[rj];
-    unsigned char *slot = A.scratch + (size_t)blockIdx.x * A.slot_bytes;
-    int32_t *P = (int32_t *)slot;
+    ClqCtl *ctl = A.ctl;
+    const int32_t a = A.g.eu[rj], b = A.g.ev[rj];
+    int32_t *P = (int32_t *)clq_slot(A.lay);
     const bool fill = A.mode != MC_COUNT;
-    const uint32_t n = clq_cut(G, rj, need, P, A.cap_p, fill, lane);
-    if (!fill) { w.max_p = n > w.max_p ? n : w.max_p; return; }
+    const uint32_t n = clq_cut(A.g, rj, need, P, A.lay.cap, fill, lane);
+    if (!fill) { w.max_cand = n > w.max_cand ? n : w.max_cand; return; }
     ++w.roots;
-    if (n > A.cap_p || n > kClqMaxCand) { if (lane == 0) ctl->bad = 1u; return; }   // (the count launch saw every root with a need not above this one)
+    if (n > A.lay.cap || n > kClqMaxCand) { if (lane == 0) ctl->bad = 1u; return; }   // (the count launch saw every root with a need not above this one)
     if (n + 2u < (A.mode == MC_ENUM ? A.omega : mc_best(ctl) + 1u)) {            // too few candidates: closed at once, one node, no matrix
-        if (w.nodes >= kMcBatch) mc_flush(ctl, w, lane);
-        ++w.nodes;
+        clq_count(ctl, w, lane);
         return;
     }
     const uint32_t W = (n + 63u) >> 6;
-    const bool in_lds = n <= A.lds_cand;
     int32_t *cur = (int32_t *)smem;
-    unsigned long long *mat = in_lds ? smem + A.lds_off_mat : (unsigned long long *)(slot + A.off_mat);
-    const bool stk_lds = in_lds && A.lds_levels > 0;
-    unsigned long long *stk = stk_lds ? smem + A.lds_off_stk : (unsigned long long *)(slot + A.off_stk);
-    const uint32_t levels = stk_lds ? A.lds_levels : A.levels;
-    clq_matrix(G, need, P, n, W, mat, lane);
+    const ClqPlace at = clq_place(A.lay, smem, n);
+    unsigned long long *mat = at.mat, *stk = at.stk;
+    clq_matrix(A.g, need, P, n, W, mat, lane);
     // ---- the search
     const bool mine = (uint32_t)lane < W;
-    if (mine) {
-        const uint32_t base = (uint32_t)lane * 64u;
-        stk[lane] = n - base >= 64u ? ~0ull : (1ull << (n - base)) - 1ull;
-    }
+    if (mine) stk[lane] = clq_prefix(n, (uint32_t)lane * 64u);
     uint32_t d = 0;
     for (;;) {
-        if (w.nodes >= kMcBatch) mc_flush(ctl, w, lane);
-        if (mc_nodes(ctl) + w.nodes >= A.budget) { w.stop = true; break; }
-        ++w.nodes;
+        if (!clq_node(ctl, w, A.budget, lane)) break;
         unsigned long long R = mine ? stk[(size_t)d * W + lane] : 0ull;
         const int cnt = clq_sum(__popcll(R));
         const int s = (int)d + 2;
@@ -176,29 +121,19 @@ __device__ void mc_root(const McArgs &A, uint32_t rj, uint32_t need, unsigned lo
             if (cnt < k_need) pop = true;
             for (int k = 1; k < k_need && !pop; ++k) {               // one independent set off U per round
                 unsigned long long Q = U;
-                for (;;) {
-                    const unsigned long long nz = __ballot(Q != 0ull);
-                    if (!nz) break;
-                    const int src = __ffsll((long long)nz) - 1;
-                    const unsigned long long word = clq_shfl64(Q, src);
-                    const int bit = __ffsll((long long)word) - 1;
-                    const uint32_t v = (uint32_t)src * 64u + (uint32_t)bit;
+                for (uint32_t v = clq_first(Q); v != kClqNone; v = clq_first(Q)) {
                     if (mine) Q &= ~mat[(size_t)v * W + lane];
-                    if (lane == src) { Q &= ~(1ull << bit); U &= ~(1ull << bit); }
+                    if ((uint32_t)lane == (v >> 6)) { Q &= ~(1ull << (v & 63u)); U &= ~(1ull << (v & 63u)); }
                 }
                 if (!__ballot(U != 0ull)) pop = true;
             }
         }
         if (!pop) {
-            const unsigned long long nz = __ballot(U != 0ull);       // (not empty: cnt > 0, or the colouring left something)
-            const int src = __ffsll((long long)nz) - 1;
-            const unsigned long long word = clq_shfl64(U, src);
-            const int bit = __ffsll((long long)word) - 1;
-            const uint32_t v = (uint32_t)src * 64u + (uint32_t)bit;
-            if (d + 1 >= levels) { if (lane == 0) ctl->bad = 1u; break; }   // (a clique of more than t_max vertices)
+            const uint32_t v = clq_first(U);                         // (not empty: cnt > 0, or the colouring left something)
+            if (d + 1 >= at.levels) { if (lane == 0) ctl->bad = 1u; break; }   // (a clique of more than t_max vertices)
             if (mine) {
                 const unsigned long long child = R & mat[(size_t)v * W + lane];
-                if (lane == src) R &= ~(1ull << bit);
+                if ((uint32_t)lane == (v >> 6)) R &= ~(1ull << (v & 63u));
                 stk[(size_t)d * W + lane] = R;
                 stk[(size_t)(d + 1) * W + lane] = child;
             }
@@ -216,16 +151,11 @@ __global__ __launch_bounds__(kWave) void k_mc_search(McArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
     const int lane = threadIdx.x;
-    McCtl *ctl = A.ctl;
-    McWave w{0u, 0u, 0u, false};
+    ClqCtl *ctl = A.ctl;
+    ClqWave w{0u, 0u, 0u, false};
     bool done = false;                                   // the seed: one root per wave
-    while (!w.stop && !done) {
-        uint32_t chunk = 0;
-        if (lane == 0) chunk = atomicAdd(&ctl->cursor, 1u);
-        chunk = (uint32_t)__shfl((int32_t)chunk, 0);
-        if (chunk >= A.n_chunks) break;
-        const uint32_t j = chunk * kWave + (uint32_t)lane;
-        const uint32_t tj = j < A.m ? (uint32_t)A.tr[j] : 0u;
+    uint32_t chunk, tj;
+    while (!w.stop && !done && clq_next_chunk(ctl, A.g.tr, A.m, A.n_chunks, chunk, tj, lane)) {
         unsigned long long todo = __ballot(tj >= (A.mode == MC_SEARCH ? mc_best(ctl) + 1u : A.need));
         while (todo && !w.stop && !done) {
             const int src = __ffsll((long long)todo) - 1;
@@ -235,22 +165,17 @@ __global__ __launch_bounds__(kWave) void k_mc_search(McArgs A)
                 need = mc_best(ctl) + 1u;
                 if ((uint32_t)__shfl((int32_t)tj, src) < need) continue;
             }
-            if (A.mode != MC_COUNT && mc_nodes(ctl) >= A.budget) { w.stop = true; break; }
+            if (A.mode != MC_COUNT && clq_nodes(ctl) >= A.budget) { w.stop = true; break; }
             mc_root(A, chunk * kWave + (uint32_t)src, need, smem, w, lane);
             done = A.mode == MC_SEED;
         }
     }
-    mc_flush(ctl, w, lane);
-    if (lane == 0) {
-        if (w.roots) atomicAdd(&ctl->n_roots, (unsigned long long)w.roots);
-        if (w.max_p) atomicMax(&ctl->max_p, w.max_p);
-        if (w.stop) ctl->stopped = 1u;
-    }
+    clq_finish(ctl, w, lane);
 }
 
 // every pair of the witness is an edge of H (and its vertices are distinct)
 __global__ void k_mc_verify(const int32_t *__restrict__ wit, uint32_t omega, const int32_t *__restrict__ ev, const uint32_t *__restrict__ rs,
-                            const uint32_t *__restrict__ re, McCtl *ctl)
+                            const uint32_t *__restrict__ re, ClqCtl *ctl)
 {
     const uint32_t id = blockIdx.x * kBlock + threadIdx.x;
     if (id >= omega * omega) return;
@@ -266,12 +191,10 @@ __global__ void k_mc_mark(const int32_t *__restrict__ wit, uint32_t omega, int32
     if (i < omega) count[wit[i]] = 1;
 }
 
-inline size_t mc_align16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
 struct McRun {                                          // what the phases of one run share
     komb_ctx *ctx;
     McArgs A;
-    McCtl h;
+    ClqCtl h;
     uint32_t t_max, lds_opt;
     int launch(int mode, uint32_t need, int grid_cap);
 };
@@ -282,56 +205,28 @@ int McRun::launch(int mode, uint32_t need, int grid_cap)
     hipStream_t s = ctx->stream;
     A.need = need;
     A.mode = MC_COUNT;
-    A.scratch = nullptr; A.slot_bytes = 0; A.cap_p = 0;
-    const int count_grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kMcGrid);
+    A.lay = ClqLayout{};
+    const int count_grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kClqGrid);
     KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->cursor, 0, sizeof(uint32_t), s));
-    KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->max_p, 0, sizeof(uint32_t), s));
+    KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->max_cand, 0, sizeof(uint32_t), s));
     k_mc_search<<<count_grid, kWave, 0, s>>>(A);
     KOMB_HIP(ctx, hipGetLastError());
-    KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(McCtl)));
-    const uint32_t max_p = h.max_p;
+    KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(ClqCtl)));
+    const uint32_t max_p = h.max_cand;
     if (max_p > kClqMaxCand)
         KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_max_clique_run: a root edge has %u candidates of trussness >= %u; the limit is %u (one 64-bit word per lane)",
                   max_p, need, kClqMaxCand);
-    const uint32_t depth = t_max >= 2 ? t_max - 2 : 0;
-    const uint32_t w_max = std::max<uint32_t>(1u, (max_p + 63u) >> 6);
-    A.cap_p = max_p;
-    A.levels = std::min(max_p, depth) + 2;
-    A.off_mat = mc_align16((size_t)max_p * sizeof(int32_t));
-    A.off_stk = A.off_mat + (size_t)max_p * w_max * 8;
-    A.slot_bytes = mc_align16(A.off_stk + (size_t)A.levels * w_max * 8);
-    // LDS: cur | the matrix of a root of up to lds_cand candidates | its stack, when that still fits
-    const size_t cur_words = mc_align16((size_t)A.levels * sizeof(int32_t)) / 8;
-    uint32_t n_l = std::min(max_p, lds_opt);
-    while (n_l > 0 && (cur_words + (size_t)n_l * ((n_l + 63u) >> 6)) * 8 > kMcLdsBytes) n_l -= 1;
-    const uint32_t w_l = (n_l + 63u) >> 6;
-    A.lds_cand = n_l;
-    A.lds_off_mat = (uint32_t)cur_words;
-    A.lds_off_stk = A.lds_off_mat + n_l * w_l;
-    A.lds_levels = std::min(n_l, depth) + 2;
-    size_t lds_words = A.lds_off_stk;
-    if (n_l > 0 && (lds_words + (size_t)A.lds_levels * w_l) * 8 <= kMcLdsBytes) lds_words += (size_t)A.lds_levels * w_l;
-    else A.lds_levels = 0;
-    int grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)grid_cap);
-    const size_t fit = kMcScratchBytes / A.slot_bytes;
-    if ((size_t)grid > fit) grid = fit < 1 ? 1 : (int)fit;
+    const ClqLaunch L = clq_layout(A.lay, max_p, t_max, 1, 0, 1, lds_opt, A.n_chunks, grid_cap);
+    if (!L.fits) KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_max_clique_run: t_max %u does not fit the LDS of a wavefront", t_max);
     DevBufs bufs(ctx);
-    KOMB_HIP(ctx, bufs.alloc(&A.scratch, (size_t)grid * A.slot_bytes));
+    KOMB_HIP(ctx, bufs.alloc(&A.lay.scratch, (size_t)L.grid * A.lay.slot_bytes));
     A.mode = mode;
     KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->cursor, 0, sizeof(uint32_t), s));
-    k_mc_search<<<grid, kWave, lds_words * 8, s>>>(A);
+    k_mc_search<<<L.grid, kWave, L.lds_bytes, s>>>(A);
     KOMB_HIP(ctx, hipGetLastError());
-    KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(McCtl)));
+    KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(ClqCtl)));
     if (h.bad) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: the search is inconsistent (mode %d, need %u, largest candidate set %u)", mode, need, max_p);
     return KOMB_OK;
-}
-
-long long mc_opt(const komb_ctx *ctx, const char *name, long long dflt, long long lo, long long hi)
-{
-    const char *e = ctx_opt(ctx, name);
-    if (!e) return dflt;
-    const long long v = strtoll(e, nullptr, 10);
-    return v < lo ? lo : (v > hi ? hi : v);
 }
 
 } // namespace
@@ -354,9 +249,9 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
     Range r_all("komb_max_clique_run");
     struct Fresh { komb_ctx *c; int32_t *count; ~Fresh() { c->pool.put(count); } } fresh{ctx, nullptr};
     komb_ctx::MaxClique res;
-    const long long limit = budget == 0 ? kMcDefaultBudget : std::min<long long>(budget, kMcMaxBudget);
+    const long long limit = budget == 0 ? kClqDefaultBudget : std::min<long long>(budget, kClqMaxBudget);
     const bool seed = !ctx_opt(ctx, "MAXCLQ_SEED") || ctx_flag(ctx, "MAXCLQ_SEED");
-    const long long list_cap = mc_opt(ctx, "MAXCLQ_LIST", kMcListDefault, 0, 1ll << 24);
+    const long long list_cap = clq_opt(ctx, "MAXCLQ_LIST", kMcListDefault, 0, 1ll << 24);
     KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.count, (size_t)nv * sizeof(int32_t)));
     DevBufs bufs(ctx);
     EventSet evs;
@@ -374,24 +269,12 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
         McRun run{};
         run.ctx = ctx;
         McArgs &A = run.A;
-        uint32_t *d_rs = nullptr, *d_re = nullptr;
         KOMB_HIP(ctx, bufs.alloc(&A.ctl, 1));
-        KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
-        KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
-        KOMB_HIP(ctx, hipMemsetAsync(A.ctl, 0, sizeof(McCtl), s));
-        KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
-        KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
-        const uint32_t um = (uint32_t)m;
-        const int g = (int)((m + kBlock - 1) / kBlock);
-        k_clq_rows<<<g, kBlock, 0, s>>>(ctx->d_t_eu, um, d_rs, d_re);
-        k_mc_tmax<<<g < 1024 ? g : 1024, kBlock, 0, s>>>(ctx->d_t_truss, um, A.ctl, 1u);
-        KOMB_HIP(ctx, hipGetLastError());
-        KOMB_HIP(ctx, d2h(ctx, &run.h, A.ctl, sizeof(McCtl)));
-        const uint32_t t_max = run.h.t_max;
-        if (t_max < 2) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: %lld edges and a largest trussness of %u", (long long)m, t_max);
-        run.t_max = t_max;
-        run.lds_opt = (uint32_t)mc_opt(ctx, "MAXCLQ_LDS", kMcLdsCand, 0, kMcLdsCand);
-        A.eu = ctx->d_t_eu; A.ev = ctx->d_t_ev; A.tr = ctx->d_t_truss; A.rs = d_rs; A.re = d_re;
+        KOMB_HIP(ctx, hipMemsetAsync(A.ctl, 0, sizeof(ClqCtl), s));
+        KOMB_TRY(clq_rows(ctx, bufs, &A.g));
+        KOMB_TRY(clq_tmax(ctx, "komb_max_clique_run", A.ctl, 1u, &run.h));
+        const uint32_t t_max = run.t_max = run.h.t_max, um = (uint32_t)m;
+        run.lds_opt = (uint32_t)clq_opt(ctx, "MAXCLQ_LDS", kClqLdsCand, 0, kClqLdsCand);
         A.m = um; A.n_chunks = (um + kWave - 1) / kWave;
         A.budget = (unsigned long long)limit;
         A.wit_stride = t_max;
@@ -406,7 +289,7 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
         nodes_seed = run.h.nodes;
         (void)hipEventRecord(e1, s);
         // ---- search: omega
-        if (!run.h.stopped && run.h.best < t_max) KOMB_TRY(run.launch(MC_SEARCH, run.h.best + 1, kMcGrid));
+        if (!run.h.stopped && run.h.best < t_max) KOMB_TRY(run.launch(MC_SEARCH, run.h.best + 1, kClqGrid));
         nodes_search = run.h.nodes - nodes_seed;
         (void)hipEventRecord(e2, s);
         uint32_t omega = run.h.best;
@@ -422,11 +305,11 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
             KOMB_HIP(ctx, hipStreamSynchronize(s));
             d_wit = A.wit;
         } else {
-            k_mc_verify<<<(int)(((size_t)omega * omega + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_wit, omega, ctx->d_t_ev, d_rs, d_re, A.ctl);
+            k_mc_verify<<<(int)(((size_t)omega * omega + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_wit, omega, A.g.ev, A.g.rs, A.g.re, A.ctl);
             KOMB_HIP(ctx, hipGetLastError());
             wit.resize(omega);
             KOMB_HIP(ctx, staged_copy(ctx, wit.data(), d_wit, (size_t)omega * sizeof(int32_t), false));
-            KOMB_HIP(ctx, d2h(ctx, &run.h, A.ctl, sizeof(McCtl)));
+            KOMB_HIP(ctx, d2h(ctx, &run.h, A.ctl, sizeof(ClqCtl)));
             if (run.h.bad) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: the clique of %u vertices the search holds is not one", omega);
             std::sort(wit.begin(), wit.end());
         }
@@ -440,7 +323,7 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
             A.count = fresh.count;
             A.list_cap = (unsigned long long)list_cap;
             KOMB_HIP(ctx, bufs.alloc(&A.list, (size_t)list_cap * omega));
-            KOMB_TRY(run.launch(MC_ENUM, omega, kMcGrid));
+            KOMB_TRY(run.launch(MC_ENUM, omega, kClqGrid));
             enumerated = !run.h.stopped;
             if (enumerated && run.h.n_cliques < 1)
                 KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_max_clique_run: the enumeration found no clique of %u vertices", omega);

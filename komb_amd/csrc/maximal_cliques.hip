@@ -25,7 +25,7 @@
 //     written there -- or, past the stream's end, nothing but the overflow word.  All are read by the host after the launch.
 //   * nodes: as in the search, batches of at most 256 per wave to one counter that every node reads; a wave that finds the budget
 //     spent stops.  What was reported by then is a lower bound: every reported clique is maximal, none is reported twice.
-// The launches of a run: k_clq_rows, k_mx_tmax; k_mx_keys, the sort, k_mx_lower; k_mx_walk in count mode (the largest |Q| at need
+// The launches of a run: k_clq_tmax; k_clq_rows, k_mx_keys, the sort, k_mx_lower; k_mx_walk in count mode (the largest |Q| at need
 // k_min, which sizes the scratch slots and the LDS; above 4096 the run is refused) and in run mode.  No workgroup waits for another.
 #include "clique_root_dev.h"
 
@@ -36,56 +36,22 @@ namespace komb {
 
 namespace {
 
-constexpr int kMxGrid = 1024;                         // wavefronts (workgroups of one) of a launch
-constexpr uint32_t kMxBatch = 256;                    // nodes a wave adds to the counter at once, at most
-static_assert((long long)kMxGrid * kMxBatch == KOMB_MAXCLQ_OVERSHOOT, "the documented overshoot");
-constexpr uint32_t kMxLdsCand = 512;                  // default and largest MAXIMAL_LDS: 512 x 8 words = 32 KiB
-constexpr size_t kMxLdsBytes = 56u << 10;             // LDS of a workgroup (below the 64 KiB a launch gets without asking)
-constexpr size_t kMxScratchBytes = 512ull << 20;      // all scratch slots of a launch together
-constexpr long long kMxDefaultBudget = 1ll << 30;
-constexpr long long kMxMaxBudget = 0x7FFFFFFFll - KOMB_MAXCLQ_OVERSHOOT;   // the search's limit: every count fits int32
 constexpr long long kMxListDefault = 65536;           // MAXIMAL_LIST
 constexpr long long kMxListMax = 1ll << 24;           // its largest value, and the words of the stream at most
-
-struct MxCtl {                                        // 64 bytes, zeroed before every run
-    unsigned long long nodes;
-    unsigned long long n_roots;                       // roots opened
-    unsigned long long list_words;                    // the stream's cursor: every report adds its size + 1
-    uint32_t cursor;                                  // next chunk of 64 canonical edges (zeroed before every launch)
-    uint32_t t_max;
-    uint32_t max_q;                                   // count mode: the largest |X| + |P|
-    uint32_t bad;                                     // an inconsistency (cannot happen; checked)
-    uint32_t stopped;                                 // a wave found the budget spent
-    uint32_t overflow;                                // a report found no room in the stream
-    uint32_t pad[4];
-};
-static_assert(sizeof(MxCtl) == 64, "MxCtl layout");
 
 struct MxArgs {
     ClqGraph g;
     ClqLower low;
     uint32_t m, n_chunks;
-    MxCtl *ctl;
+    ClqCtl *ctl;
     bool count_only, pivot_max;
     uint32_t k_min, k_hi;
     unsigned long long budget;
-    unsigned char *scratch;                           // slot b: Q[cap_q] | mat[cap_q * w_max] | stk[levels * 2 * w_max]
-    size_t slot_bytes, off_mat, off_stk;
-    uint32_t cap_q, levels;
-    // LDS in 64-bit words: cur[levels] and piv[levels] (int32) | hist[k_hi - k_min + 1] | mat | stk; lds_levels == 0: the stack is global
-    uint32_t lds_cand, lds_levels, lds_off_hist, lds_off_mat, lds_off_stk;
+    ClqLayout lay;                                    // the candidates are Q; LDS head: cur[levels], piv[levels] | hist[k_hi - k_min + 1]; two sets per stack level
     unsigned long long *hist;
     int32_t *count, *largest, *list;
     unsigned long long list_cap;                      // words of the stream
 };
-
-__global__ void k_mx_tmax(const int32_t *__restrict__ tr, uint32_t m, MxCtl *ctl)
-{
-    int32_t hi = 0;
-    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock) { const int32_t t = tr[j]; hi = t > hi ? t : hi; }
-    for (int off = kWave / 2; off > 0; off >>= 1) { const int32_t other = __shfl_xor(hi, off); hi = other > hi ? other : hi; }
-    if ((threadIdx.x & (kWave - 1)) == 0 && hi > 0) atomicMax(&ctl->t_max, (uint32_t)hi);
-}
 
 // ---- the lower rows: keys (ev, position) sorted, then one entry per key and the row bounds
 __global__ void k_mx_keys(const int32_t *__restrict__ ev, uint32_t m, uint64_t *__restrict__ keys)
@@ -95,7 +61,7 @@ __global__ void k_mx_keys(const int32_t *__restrict__ ev, uint32_t m, uint64_t *
 }
 
 __global__ void k_mx_lower(const uint64_t *__restrict__ keys, const int32_t *__restrict__ eu, uint32_t m, uint32_t nv, int32_t *__restrict__ lu,
-                           uint32_t *__restrict__ lpos, uint32_t *__restrict__ ls, uint32_t *__restrict__ le, MxCtl *ctl)
+                           uint32_t *__restrict__ lpos, uint32_t *__restrict__ ls, uint32_t *__restrict__ le, ClqCtl *ctl)
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= m) return;
@@ -105,23 +71,6 @@ __global__ void k_mx_lower(const uint64_t *__restrict__ keys, const int32_t *__r
     lpos[i] = p;
     if (i == 0 || (uint32_t)(keys[i - 1] >> 32) != b) ls[b] = i;
     if (i + 1 == m || (uint32_t)(keys[i + 1] >> 32) != b) le[b] = i + 1;
-}
-
-__device__ __forceinline__ unsigned long long mx_nodes(MxCtl *ctl) { return __hip_atomic_load(&ctl->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-struct MxWave { uint32_t nodes, roots, max_q; bool stop; };
-
-__device__ __forceinline__ void mx_flush(MxCtl *ctl, MxWave &w, int lane)
-{
-    if (lane == 0 && w.nodes) atomicAdd(&ctl->nodes, (unsigned long long)w.nodes);
-    w.nodes = 0;
-}
-
-// bits [0, n) of the word that starts at bit base
-__device__ __forceinline__ unsigned long long mx_prefix(uint32_t n, uint32_t base)
-{
-    if (n <= base) return 0ull;
-    return n - base >= 64u ? ~0ull : (1ull << (n - base)) - 1ull;
 }
 
 // A maximal clique of d + 2 vertices: a, b and the d vertices of cur[].
@@ -149,87 +98,50 @@ __device__ __forceinline__ void mx_report(const MxArgs &A, unsigned long long *h
     }
 }
 
-// The pivot of the node (P, X) (lane w holds word w of each; P is not empty): the vertex of P | X with the most neighbours in P,
-// the smallest such; or the first of P.
-__device__ __forceinline__ uint32_t mx_pivot(const MxArgs &A, unsigned long long P, unsigned long long X, const unsigned long long *mat, uint32_t W, int lane)
-{
-    const unsigned long long nzp = __ballot(P != 0ull);
-    if (!A.pivot_max) {
-        const int src = __ffsll((long long)nzp) - 1;
-        return (uint32_t)src * 64u + (uint32_t)(__ffsll((long long)clq_shfl64(P, src)) - 1);
-    }
-    const unsigned long long U = P | X;
-    unsigned long long key = 0ull;                       // (neighbours + 1) << 32 | ~vertex: the largest wins
-    for (unsigned long long wi = __ballot(U != 0ull); wi; wi &= wi - 1) {
-        const int i = __ffsll((long long)wi) - 1;
-        const bool in = (clq_shfl64(U, i) >> lane) & 1ull;
-        const uint32_t u = (uint32_t)i * 64u + (uint32_t)lane;
-        uint32_t c = 0;
-        for (unsigned long long wj = nzp; wj; wj &= wj - 1) {
-            const int j = __ffsll((long long)wj) - 1;
-            const unsigned long long Pj = clq_shfl64(P, j);
-            if (in) c += (uint32_t)__popcll(Pj & mat[(size_t)u * W + (uint32_t)j]);
-        }
-        const unsigned long long mine = ((unsigned long long)(c + 1u) << 32) | (0xFFFFFFFFu - u);
-        if (in && mine > key) key = mine;
-    }
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        const unsigned long long other = clq_shfl64(key, lane ^ off);
-        key = other > key ? other : key;
-    }
-    return 0xFFFFFFFFu - (uint32_t)key;
-}
-
 // One root: canonical edge rj = (a, b).  Every branch below is uniform over the wave.
-__device__ void mx_root(const MxArgs &A, uint32_t rj, unsigned long long *smem, MxWave &w, int lane)
+__device__ void mx_root(const MxArgs &A, uint32_t rj, unsigned long long *smem, ClqWave &w, int lane)
 {
-    MxCtl *ctl = A.ctl;
+    ClqCtl *ctl = A.ctl;
     const int32_t a = A.g.eu[rj], b = A.g.ev[rj];
-    unsigned char *slot = A.scratch + (size_t)blockIdx.x * A.slot_bytes;
-    int32_t *Q = (int32_t *)slot;
+    int32_t *Q = (int32_t *)clq_slot(A.lay);
     const bool fill = !A.count_only;
-    const uint32_t nx = clq_cut_x(A.g, A.low, rj, A.k_min, Q, A.cap_q, fill, lane);
-    const uint32_t room = nx < A.cap_q ? A.cap_q - nx : 0u;
-    const uint32_t np = clq_cut(A.g, rj, A.k_min, Q + (A.cap_q - room), room, fill, lane);
+    const uint32_t cap_q = A.lay.cap;
+    const uint32_t nx = clq_cut_x(A.g, A.low, rj, A.k_min, Q, cap_q, fill, lane);
+    const uint32_t room = nx < cap_q ? cap_q - nx : 0u;
+    const uint32_t np = clq_cut(A.g, rj, A.k_min, Q + (cap_q - room), room, fill, lane);
     const uint32_t n = nx + np;
-    if (A.count_only) { w.max_q = n > w.max_q ? n : w.max_q; return; }
+    if (A.count_only) { w.max_cand = n > w.max_cand ? n : w.max_cand; return; }
     ++w.roots;
-    if (n > A.cap_q || n > kClqMaxCand) { if (lane == 0) ctl->bad = 1u; return; }   // (the count launch saw every root at this need)
-    volatile int32_t *cur = (int32_t *)smem, *piv = cur + A.levels;   // (written by lane 0, read by every lane)
-    unsigned long long *hist = smem + A.lds_off_hist;
+    if (n > cap_q || n > kClqMaxCand) { if (lane == 0) ctl->bad = 1u; return; }   // (the count launch saw every root at this need)
+    volatile int32_t *cur = (int32_t *)smem, *piv = cur + A.lay.levels;   // (written by lane 0, read by every lane)
+    unsigned long long *hist = smem + A.lay.lds_off_extra;
     if (np == 0 || np + 2u < A.k_min) {                  // the edge alone, or no clique of k_min vertices: one node, no matrix
-        if (w.nodes >= kMxBatch) mx_flush(ctl, w, lane);
-        ++w.nodes;
+        clq_count(ctl, w, lane);
         if (np == 0 && nx == 0 && A.k_min <= 2u) mx_report(A, hist, a, b, Q, cur, 0u, lane);
         return;
     }
     const uint32_t W = (n + 63u) >> 6;
-    const bool in_lds = n <= A.lds_cand;
-    unsigned long long *mat = in_lds ? smem + A.lds_off_mat : (unsigned long long *)(slot + A.off_mat);
-    const bool stk_lds = in_lds && A.lds_levels > 0;
-    unsigned long long *stk = stk_lds ? smem + A.lds_off_stk : (unsigned long long *)(slot + A.off_stk);
-    const uint32_t levels = stk_lds ? A.lds_levels : A.levels;
+    const ClqPlace at = clq_place(A.lay, smem, n);
+    unsigned long long *mat = at.mat, *stk = at.stk;
     clq_matrix(A.g, A.k_min, Q, n, W, mat, lane);
     // ---- the walk: (P, X) is the node at level d, which holds d + 2 vertices
     const bool mine = (uint32_t)lane < W;
     const uint32_t base = (uint32_t)lane * 64u;
-    unsigned long long X = mine ? mx_prefix(nx, base) : 0ull;
-    unsigned long long P = mine ? mx_prefix(n, base) & ~X : 0ull;
+    unsigned long long X = mine ? clq_prefix(nx, base) : 0ull;
+    unsigned long long P = mine ? clq_prefix(n, base) & ~X : 0ull;
     uint32_t d = 0;
     bool enter = true;
     for (;;) {
         uint32_t u = 0;
         if (enter) {                                     // a node
-            if (w.nodes >= kMxBatch) mx_flush(ctl, w, lane);
-            if (mx_nodes(ctl) + w.nodes >= A.budget) { w.stop = true; break; }
-            ++w.nodes;
+            if (!clq_node(ctl, w, A.budget, lane)) break;
             const uint32_t cnt = (uint32_t)clq_sum(__popcll(P));
             bool open = false;
             if (cnt == 0) {
                 if (d + 2u >= A.k_min && !__ballot(X != 0ull)) mx_report(A, hist, a, b, Q, cur, d, lane);
             } else if (d + 2u + cnt >= A.k_min) {
-                u = mx_pivot(A, P, X, mat, W, lane);
-                if (d + 1 >= levels || u >= n) { if (lane == 0) ctl->bad = 1u; break; }   // (a clique of more than t_max vertices)
+                u = A.pivot_max ? clq_pivot(P, P | X, mat, W, lane) : clq_first(P);   // (of P | X; or the first of P)
+                if (d + 1 >= at.levels || u >= n) { if (lane == 0) ctl->bad = 1u; break; }   // (a clique of more than t_max vertices)
                 if (mine) {
                     stk[(size_t)(2 * d) * W + lane] = P;
                     stk[(size_t)(2 * d + 1) * W + lane] = X;
@@ -250,17 +162,14 @@ __device__ void mx_root(const MxArgs &A, uint32_t rj, unsigned long long *smem, 
             X = mine ? stk[(size_t)(2 * d + 1) * W + lane] : 0ull;
         }
         const unsigned long long T = mine ? P & ~mat[(size_t)u * W + lane] : 0ull;
-        const unsigned long long nz = __ballot(T != 0ull);
-        if (!nz) {
+        const uint32_t v = clq_first(T);
+        if (v == kClqNone) {
             if (d == 0) break;
             --d;
             enter = false;
             continue;
         }
-        const int src = __ffsll((long long)nz) - 1;
-        const int bit = __ffsll((long long)clq_shfl64(T, src)) - 1;
-        const uint32_t v = (uint32_t)src * 64u + (uint32_t)bit;
-        if (lane == src) { P &= ~(1ull << bit); X |= 1ull << bit; }   // (v moves from P to X; row(v) holds no v, so the child loses it)
+        if ((uint32_t)lane == (v >> 6)) { P &= ~(1ull << (v & 63u)); X |= 1ull << (v & 63u); }   // (v moves from P to X; row(v) holds no v, so the child loses it)
         if (mine) {
             stk[(size_t)(2 * d) * W + lane] = P;
             stk[(size_t)(2 * d + 1) * W + lane] = X;
@@ -279,50 +188,30 @@ __global__ __launch_bounds__(kWave) void k_mx_walk(MxArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
     const int lane = threadIdx.x;
-    MxCtl *ctl = A.ctl;
-    MxWave w{0u, 0u, 0u, false};
-    unsigned long long *hist = smem + A.lds_off_hist;
+    ClqCtl *ctl = A.ctl;
+    ClqWave w{0u, 0u, 0u, false};
+    unsigned long long *hist = smem + A.lay.lds_off_extra;
     const uint32_t n_k = A.k_hi - A.k_min + 1u;
     if (!A.count_only) {                                 // (a count launch has no LDS)
         for (uint32_t i = (uint32_t)lane; i < n_k; i += kWave) hist[i] = 0ull;
         __syncthreads();
     }
-    while (!w.stop) {
-        uint32_t chunk = 0;
-        if (lane == 0) chunk = atomicAdd(&ctl->cursor, 1u);
-        chunk = (uint32_t)__shfl((int32_t)chunk, 0);
-        if (chunk >= A.n_chunks) break;
-        const uint32_t j = chunk * kWave + (uint32_t)lane;
-        const uint32_t tj = j < A.m ? (uint32_t)A.g.tr[j] : 0u;
+    uint32_t chunk, tj;
+    while (!w.stop && clq_next_chunk(ctl, A.g.tr, A.m, A.n_chunks, chunk, tj, lane)) {
         unsigned long long todo = __ballot(tj >= A.k_min);
         while (todo && !w.stop) {
             const int src = __ffsll((long long)todo) - 1;
             todo &= todo - 1;
-            if (!A.count_only && mx_nodes(ctl) >= A.budget) { w.stop = true; break; }
+            if (!A.count_only && clq_nodes(ctl) >= A.budget) { w.stop = true; break; }
             mx_root(A, chunk * kWave + (uint32_t)src, smem, w, lane);
         }
     }
-    mx_flush(ctl, w, lane);
     if (!A.count_only) {
         __syncthreads();
         for (uint32_t i = (uint32_t)lane; i < n_k; i += kWave)
             if (hist[i]) atomicAdd(A.hist + i, hist[i]);
     }
-    if (lane == 0) {
-        if (w.roots) atomicAdd(&ctl->n_roots, (unsigned long long)w.roots);
-        if (w.max_q) atomicMax(&ctl->max_q, w.max_q);
-        if (w.stop) ctl->stopped = 1u;
-    }
-}
-
-inline size_t mx_align16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
-long long mx_opt(const komb_ctx *ctx, const char *name, long long dflt, long long lo, long long hi)
-{
-    const char *e = ctx_opt(ctx, name);
-    if (!e) return dflt;
-    const long long v = strtoll(e, nullptr, 10);
-    return v < lo ? lo : (v > hi ? hi : v);
+    clq_finish(ctl, w, lane);
 }
 
 // The stream (size, vertices ...)* of n cliques as the sorted list: ascending tuples in lexicographic order, CSR style.
@@ -373,24 +262,19 @@ int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
     Range r_all("komb_maximal_cliques_run");
     struct Fresh { komb_ctx *c; int32_t *count; ~Fresh() { c->pool.put(count); } } fresh{ctx, nullptr};
     komb_ctx::MaximalCliques res;
-    const long long limit = budget == 0 ? kMxDefaultBudget : std::min<long long>(budget, kMxMaxBudget);
-    const long long list_cap = mx_opt(ctx, "MAXIMAL_LIST", kMxListDefault, 0, kMxListMax);
+    const long long limit = budget == 0 ? kClqDefaultBudget : std::min<long long>(budget, kClqMaxBudget);
+    const long long list_cap = clq_opt(ctx, "MAXIMAL_LIST", kMxListDefault, 0, kMxListMax);
     DevBufs bufs(ctx);
-    MxCtl h{};
+    ClqCtl h{};
     MxArgs A{};
     KOMB_HIP(ctx, bufs.alloc(&A.ctl, 1));
     KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.count, (size_t)std::max<int64_t>(2 * nv, 1) * sizeof(int32_t)));   // count[nv] | largest[nv]
 
     ctx->timer.start(s);
-    KOMB_HIP(ctx, hipMemsetAsync(A.ctl, 0, sizeof(MxCtl), s));
+    KOMB_HIP(ctx, hipMemsetAsync(A.ctl, 0, sizeof(ClqCtl), s));
     if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.count, 0, (size_t)(2 * nv) * sizeof(int32_t), s));
     const uint32_t um = (uint32_t)m;
-    if (m > 0) {
-        k_mx_tmax<<<(int)std::min<int64_t>((m + kBlock - 1) / kBlock, 1024), kBlock, 0, s>>>(ctx->d_t_truss, um, A.ctl);
-        KOMB_HIP(ctx, hipGetLastError());
-        KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(MxCtl)));
-        if (h.t_max < 2) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_maximal_cliques_run: %lld edges and a largest trussness of %u", (long long)m, h.t_max);
-    }
+    if (m > 0) KOMB_TRY(clq_tmax(ctx, "komb_maximal_cliques_run", A.ctl, 0u, &h));
     const int32_t t_max = (int32_t)h.t_max;
     const int32_t k_hi = std::max(t_max, k_min);         // no clique has more than t_max vertices (and the fetch has at least one entry)
     const uint32_t n_k = (uint32_t)(k_hi - k_min + 1);
@@ -400,11 +284,10 @@ int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
     res.flags = KOMB_MAXIMAL_COMPLETE | KOMB_MAXIMAL_LISTED;
     if (m > 0 && k_min <= t_max) {                       // (above t_max there is nothing to report)
         const int g = (int)((m + kBlock - 1) / kBlock);
-        uint32_t *d_rs = nullptr, *d_re = nullptr, *d_ls = nullptr, *d_le = nullptr, *d_lpos = nullptr;
+        uint32_t *d_ls = nullptr, *d_le = nullptr, *d_lpos = nullptr;
         int32_t *d_lu = nullptr;
         uint64_t *d_keys = nullptr, *d_keys_alt = nullptr, *d_sorted = nullptr;
-        KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
-        KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
+        KOMB_TRY(clq_rows(ctx, bufs, &A.g));
         KOMB_HIP(ctx, bufs.alloc(&d_ls, (size_t)nv));
         KOMB_HIP(ctx, bufs.alloc(&d_le, (size_t)nv));
         KOMB_HIP(ctx, bufs.alloc(&d_lu, (size_t)m));
@@ -412,20 +295,15 @@ int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
         KOMB_HIP(ctx, bufs.alloc(&d_keys, (size_t)m));
         KOMB_HIP(ctx, bufs.alloc(&d_keys_alt, (size_t)m));
         KOMB_HIP(ctx, bufs.alloc(&A.hist, (size_t)n_k));
-        for (uint32_t *p : {d_rs, d_re, d_ls, d_le}) KOMB_HIP(ctx, hipMemsetAsync(p, 0, (size_t)nv * sizeof(uint32_t), s));
+        for (uint32_t *p : {d_ls, d_le}) KOMB_HIP(ctx, hipMemsetAsync(p, 0, (size_t)nv * sizeof(uint32_t), s));
         KOMB_HIP(ctx, hipMemsetAsync(A.hist, 0, (size_t)n_k * sizeof(unsigned long long), s));
-        k_clq_rows<<<g, kBlock, 0, s>>>(ctx->d_t_eu, um, d_rs, d_re);
-        KOMB_HIP(ctx, hipGetLastError());
         // ---- the lower rows: the canonical edges by (ev, eu); positions ascend with eu inside one ev, so (ev, position) sorts them
         k_mx_keys<<<g, kBlock, 0, s>>>(ctx->d_t_ev, um, d_keys);
         KOMB_HIP(ctx, hipGetLastError());
-        int id_bits = 1;
-        while (id_bits < 31 && (1ll << id_bits) < nv) ++id_bits;
-        KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, m, 32 + id_bits, &d_sorted));
+        KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, m, 32 + key_bits(nv), &d_sorted));
         k_mx_lower<<<g, kBlock, 0, s>>>(d_sorted, ctx->d_t_eu, um, (uint32_t)nv, d_lu, d_lpos, d_ls, d_le, A.ctl);
         KOMB_HIP(ctx, hipGetLastError());
         bufs.release(d_sorted == d_keys ? d_keys_alt : d_keys);
-        A.g = ClqGraph{ctx->d_t_eu, ctx->d_t_ev, ctx->d_t_truss, d_rs, d_re};
         A.low = ClqLower{d_lu, d_lpos, d_ls, d_le};
         A.m = um; A.n_chunks = (um + kWave - 1) / kWave;
         A.k_min = (uint32_t)k_min; A.k_hi = (uint32_t)k_hi;
@@ -435,49 +313,28 @@ int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
         A.count = fresh.count; A.largest = fresh.count + nv;
         // ---- the largest |X| + |P| at need k_min
         A.count_only = true;
-        const int count_grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kMxGrid);
+        const int count_grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kClqGrid);
         k_mx_walk<<<count_grid, kWave, 0, s>>>(A);
         KOMB_HIP(ctx, hipGetLastError());
-        KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(MxCtl)));
+        KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(ClqCtl)));
         if (h.bad) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_maximal_cliques_run: the lower rows are inconsistent (%lld edges)", (long long)m);
-        const uint32_t max_q = h.max_q;
+        const uint32_t max_q = h.max_cand;
         if (max_q > kClqMaxCand)
             KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_maximal_cliques_run: a root edge has %u candidates and excluded vertices of trussness >= %d; the limit is %u "
                       "(one 64-bit word per lane)", max_q, (int)k_min, kClqMaxCand);
         // ---- the slots and the LDS, sized from it
-        const uint32_t depth = (uint32_t)t_max - 2u;
-        const uint32_t w_max = std::max<uint32_t>(1u, (max_q + 63u) >> 6);
-        A.cap_q = max_q;
-        A.levels = std::min(max_q, depth) + 2;
-        A.off_mat = mx_align16((size_t)max_q * sizeof(int32_t));
-        A.off_stk = A.off_mat + (size_t)max_q * w_max * 8;
-        A.slot_bytes = mx_align16(A.off_stk + (size_t)A.levels * 2 * w_max * 8);
-        const size_t head_words = mx_align16((size_t)A.levels * 2 * sizeof(int32_t)) / 8 + n_k;
-        uint32_t n_l = std::min(max_q, (uint32_t)mx_opt(ctx, "MAXIMAL_LDS", kMxLdsCand, 0, kMxLdsCand));
-        while (n_l > 0 && (head_words + (size_t)n_l * ((n_l + 63u) >> 6)) * 8 > kMxLdsBytes) n_l -= 1;
-        const uint32_t w_l = (n_l + 63u) >> 6;
-        A.lds_cand = n_l;
-        A.lds_off_hist = (uint32_t)(head_words - n_k);
-        A.lds_off_mat = (uint32_t)head_words;
-        A.lds_off_stk = A.lds_off_mat + n_l * w_l;
-        A.lds_levels = std::min(n_l, depth) + 2;
-        size_t lds_words = A.lds_off_stk;
-        if (n_l > 0 && (lds_words + (size_t)A.lds_levels * 2 * w_l) * 8 <= kMxLdsBytes) lds_words += (size_t)A.lds_levels * 2 * w_l;
-        else A.lds_levels = 0;
-        if (lds_words * 8 > kMxLdsBytes)
-            KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_maximal_cliques_run: %u sizes at t_max %d do not fit the LDS of a wavefront", n_k, (int)t_max);
-        int grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kMxGrid);
-        const size_t fit = kMxScratchBytes / A.slot_bytes;
-        if ((size_t)grid > fit) grid = fit < 1 ? 1 : (int)fit;
-        KOMB_HIP(ctx, bufs.alloc(&A.scratch, (size_t)grid * A.slot_bytes));
+        const ClqLaunch L = clq_layout(A.lay, max_q, (uint32_t)t_max, 2, n_k, 2, (uint32_t)clq_opt(ctx, "MAXIMAL_LDS", kClqLdsCand, 0, kClqLdsCand),
+                                       A.n_chunks, kClqGrid);
+        if (!L.fits) KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_maximal_cliques_run: %u sizes at t_max %d do not fit the LDS of a wavefront", n_k, (int)t_max);
+        KOMB_HIP(ctx, bufs.alloc(&A.lay.scratch, (size_t)L.grid * A.lay.slot_bytes));
         // the stream: a clique of s vertices takes s + 1 words, MAXIMAL_LIST cliques of t_max vertices fit unless that is more than 2^24 words
         A.list_cap = (unsigned long long)std::min<long long>(list_cap * ((long long)t_max + 1), kMxListMax);
         KOMB_HIP(ctx, bufs.alloc(&A.list, (size_t)A.list_cap));
         A.count_only = false;
         KOMB_HIP(ctx, hipMemsetAsync(&A.ctl->cursor, 0, sizeof(uint32_t), s));
-        k_mx_walk<<<grid, kWave, lds_words * 8, s>>>(A);
+        k_mx_walk<<<L.grid, kWave, L.lds_bytes, s>>>(A);
         KOMB_HIP(ctx, hipGetLastError());
-        KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(MxCtl)));
+        KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(ClqCtl)));
         if (h.bad)
             KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_maximal_cliques_run: the walk is inconsistent (k_min %d, t_max %d, largest candidate list %u)", (int)k_min,
                       (int)t_max, max_q);
