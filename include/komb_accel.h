@@ -125,8 +125,25 @@ int         komb_abi_version(void);
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
  * allocation the context hands out is filled with that 32-bit word first -- tests of reads of memory nothing wrote)
- * (DESIGN.md section 8).  value NULL unsets. */
+ * (DESIGN.md section 8).  value NULL unsets.
+ * Two more are tests' means of reaching what a call does when a device allocation fails.  Every device allocation request
+ * of the context is counted.  ALLOC_FAIL_AT ("<n>", decimal): zeroes the counter; request number n from now (1-based) fails
+ * with out-of-memory -- before anything is allocated, given back or touched on the device -- once, and the trigger is
+ * gone; "0" only counts; NULL disarms.  ALLOC_TRIM_AT ("<n>"): zeroes the same counter; request number n, if it is one of
+ * the caching pool's, first gives every cached block back to the driver, as a request the driver refuses does before it
+ * tries again, and is then served normally.  A value that is not a non-negative decimal number: KOMB_ERR_ARG, nothing
+ * changed.  Neither changes a result; with neither set a request pays one branch.
+ * komb_alloc_info (no device needed; any output may be NULL): requests counted since either option was last set; whether
+ * the ALLOC_FAIL_AT trigger has fired since it was last set (0 | 1); blocks and bytes of the pool that are handed out;
+ * blocks the pool holds that nobody uses; how often the pool gave its cached blocks back (a refused request or
+ * ALLOC_TRIM_AT).
+ * What EVERY entry point below keeps to when a device allocation fails (KOMB_ERR_NOMEM, komb_last_error names the request):
+ * no host output has been written; the pool has nothing handed out that no entry point can reach; the results of the
+ * other analyses on the context read as before; the same call repeated succeeds.  Whether the entry's own previous result
+ * survives is stated with the entry. */
 int         komb_set_option(komb_ctx *ctx, const char *name, const char *value);
+int         komb_alloc_info(komb_ctx *ctx, int64_t *requests, int32_t *fired, int64_t *pool_blocks_in_use, int64_t *pool_bytes_in_use,
+                            int64_t *pool_blocks_cached, int64_t *trims);
 
 /* ---- graph construction ------------------------------------------------ */
 /* Replaces igraph_create + igraph_simplify(multiple=true, loops=true)
@@ -135,7 +152,10 @@ int         komb_set_option(komb_ctx *ctx, const char *name, const char *value);
  * [0,nv).  Removes loops and parallel edges on the device and keeps the graph
  * resident in HBM as a symmetric CSR (rows ascending, the caller's ids).  What
  * only the k-truss path needs is made by the first k-truss call (below).
- * Every result is reported in the caller's vertex ids. */
+ * Every result is reported in the caller's vertex ids.
+ * A load drops the previous graph and every result on the context before it does anything else, so a load that fails -- an
+ * argument, a limit, KOMB_ERR_NOMEM -- leaves NO graph: komb_graph_info and every fetch answer KOMB_ERR_STATE until a load
+ * succeeds (komb_graph_from_csr alike). */
 int komb_graph_from_edges(komb_ctx *ctx, int64_t nv, int64_t n_raw,
                           const int64_t *uv_pairs);
 
@@ -153,7 +173,10 @@ int komb_graph_get_csr(komb_ctx *ctx, int64_t *rowptr, int32_t *col);
 /* Replaces igraph_degree(ALL,NO_LOOPS) + igraph_coreness(ALL)
  * (src/graph.cpp:462-463).  komb_core_run computes on the device and leaves
  * degree/coreness in HBM (this is the timed region of bench.py);
- * komb_core_fetch copies them out; komb_degree_coreness = run + fetch. */
+ * komb_core_fetch copies them out; komb_degree_coreness = run + fetch.
+ * A run writes into the result's own arrays from its first kernel on: a run that fails (KOMB_ERR_NOMEM, KOMB_ERR_DEVICE)
+ * drops the previous k-core result -- komb_core_fetch, and what needs the coreness, answer KOMB_ERR_STATE until a run
+ * completes -- and changes nothing else on the context. */
 int komb_core_run(komb_ctx *ctx);
 /* One process per GPU, every rank holding the same graph: rank r owns the vertices
  * [nv*r/world, nv*(r+1)/world) -- their live degrees and the decrements on them; every sub-round the ranks exchange
@@ -179,7 +202,8 @@ int komb_degree_coreness(komb_ctx *ctx, int32_t *degree, int32_t *coreness);
  * coreness[nv] out (either may be NULL); komb_onion_info reports the last run: the number of layers (the largest layer
  * number, 0 for an empty graph), the largest coreness and the run's device time in ms.  The onion uses arrays of its
  * own: it changes no k-core, k-truss or CoreA result and no komb_stats field.  No graph loaded: KOMB_ERR_ARG; fetch /
- * info before a run on the current graph: KOMB_ERR_STATE. */
+ * info before a run on the current graph: KOMB_ERR_STATE.  A run that fails (KOMB_ERR_NOMEM, KOMB_ERR_DEVICE) drops the
+ * previous onion result: fetch / info answer KOMB_ERR_STATE until a run completes. */
 int komb_onion_run(komb_ctx *ctx);
 int komb_onion_fetch(komb_ctx *ctx, int32_t *layer /*[nv]*/, int32_t *coreness /*[nv]*/);
 int komb_onion_info(komb_ctx *ctx, int64_t *n_layers, int32_t *max_coreness, double *ms);
@@ -202,7 +226,8 @@ int komb_onion_info(komb_ctx *ctx, int64_t *n_layers, int32_t *max_coreness, dou
  * komb_components_info: the kind, the threshold actually applied (KOMB_COMP_K_MAX resolved), members, components, the
  * size of the largest component and the device time of the run in ms (the context's HIP-event timer).
  * The result is a snapshot in arrays of its own: loading a graph drops it; later k-core / k-truss calls neither change
- * nor invalidate it; a call changes no k-core, k-truss, onion or CoreA result and no komb_stats field.  Option
+ * nor invalidate it; a call changes no k-core, k-truss, onion or CoreA result and no komb_stats field.  A run that fails
+ * (KOMB_ERR_NOMEM, KOMB_ERR_DEVICE) drops the previous snapshot: fetch / info answer KOMB_ERR_STATE until a run completes.  Option
  * COMP_SAMPLE (0 | 1) selects between the one-pass and the giant-component-skipping link of the core kind. */
 #define KOMB_COMP_CORE   0    /* members: vertices with coreness >= k; edges: resident edges between two members     */
 #define KOMB_COMP_TRUSS  1    /* edges: those of the last k-truss result with trussness >= k; members: their endpoints */
@@ -266,7 +291,8 @@ int komb_hierarchy_info(komb_ctx *ctx, int32_t *kind, int64_t *n_nodes, int64_t 
  * The result lives in arrays of its own, and its labels index the canonical edge list of the k-truss result it was
  * computed from: whatever replaces or drops that result -- a new k-truss run of any kind, komb_truss_unprepare, a graph
  * load -- drops the communities too, and fetch / info then return KOMB_ERR_STATE until the next run.  k-core, onion,
- * components and CoreA calls neither change nor drop it.  A communities run changes no k-core, k-truss, onion,
+ * components and CoreA calls neither change nor drop it.  A communities run drops the previous communities when it
+ * starts: one that fails (KOMB_ERR_NOMEM, KOMB_ERR_DEVICE) leaves none.  A communities run changes no k-core, k-truss, onion,
  * components or CoreA result, no komb_stats field and not the resident k-truss preparation.  Options COMM_SHORT /
  * COMM_HEAVY (tests) move the lengths at which an edge's triangle search goes from its lane to its wave / to several
  * workgroups; neither changes a result. */
@@ -307,7 +333,8 @@ int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_membe
  * The result lives in arrays of its own, and its reps index the canonical edge list of the k-truss result it was computed
  * from: whatever replaces or drops that result -- a new k-truss run of any kind, komb_truss_unprepare, a graph load --
  * drops it too.  k-core, onion, components, communities and CoreA calls neither change nor drop it; a run changes none
- * of their results, no komb_stats field and not the resident k-truss preparation.  Option BICONN_HEAVY (tests) moves the
+ * of their results, no komb_stats field and not the resident k-truss preparation.  A run drops the previous blocks when it
+ * starts: one that fails (KOMB_ERR_NOMEM, KOMB_ERR_LIMIT, KOMB_ERR_DEVICE) leaves none.  Option BICONN_HEAVY (tests) moves the
  * row length above which a frontier vertex' row is walked by its wave; it changes no result. */
 #define KOMB_BICONN_K_MAX (-1)   /* k = the largest trussness of the result (2 when it has no edges) */
 int komb_biconnected_run(komb_ctx *ctx, int32_t k);
@@ -769,7 +796,13 @@ int komb_clique_communities_info(komb_ctx *ctx, int32_t *k, int32_t *k_min, int6
  * afterwards (src/graph.cpp:529-532), not part of igraph_trussness: for a
  * whole-graph run they are made by the first fetch that asks for them and kept
  * with the graph (a run under a vmask makes its subgraph's before it returns).
- * Trussness of a triangle-free edge is 2. */
+ * Trussness of a triangle-free edge is 2.
+ * A run drops the previous k-truss result, and every analysis that indexes it, once its arguments have been accepted: a
+ * run that fails after that (KOMB_ERR_NOMEM, KOMB_ERR_LIMIT, KOMB_ERR_DEVICE) leaves NO k-truss result -- komb_truss_count
+ * and the fetches answer KOMB_ERR_STATE -- holds nothing of the one it had begun, and changes no k-core, onion, components,
+ * hierarchy or densest-subgraph result.  The record stream of the default index layout is memory the run can do without:
+ * where that is refused the run builds the index by the exact two-pass layout instead and succeeds
+ * (komb_stats.index_layout says which). */
 int komb_truss_run(komb_ctx *ctx, const uint8_t *vmask);
 /* What igraph_trussness does to its argument before it lists a triangle (src/graph.cpp:508: vertices ordered by degree,
  * every edge oriented from its lower to its higher endpoint) is the k-truss PREPARATION here: (degree,id)-ranked internal
@@ -802,6 +835,8 @@ int komb_set_shard_peel(komb_ctx *ctx, int32_t on);
  * bench.py --gpus N runs by default.  With a vmask the results are complete on every rank.  world == 1 is komb_truss_run. */
 int komb_truss_run_slice(komb_ctx *ctx, const uint8_t *vmask, int32_t rank, int32_t world);
 int komb_truss_count(komb_ctx *ctx, int64_t *ne_sub);
+/* (a fetch that fails -- the first one that asks for endpoints or supports makes them: KOMB_ERR_NOMEM -- has written none of
+ * its outputs and leaves the result as it was) */
 int komb_truss_fetch(komb_ctx *ctx, int32_t *eu, int32_t *ev, int32_t *truss);
 /* per-edge triangle counts the peel started from (canonical order): an extra of this library (igraph_trussness has no
  * such output), put into canonical order by the first call after a run */

@@ -66,6 +66,8 @@ _vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 SIGNATURES = {
     "komb_abi_version": (_i32, []),
     "komb_set_option": (_i32, [_vp, ctypes.c_char_p, ctypes.c_char_p]),
+    "komb_alloc_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                               ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "komb_truss_prepare": (_i32, [_vp]),
     "komb_truss_unprepare": (_i32, [_vp]),
     "komb_graph_moments": (_i32, [_vp]),

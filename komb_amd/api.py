@@ -46,6 +46,9 @@ OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_
                 "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "PERC_GROUP", "PERC_DEBUG", "BICONN_HEAVY",
                 "POISON")
 
+# (ALLOC_FAIL_AT / ALLOC_TRIM_AT are one-shot triggers counted from the moment they are set: they are NOT forwarded -- forwarding
+# would re-arm them before every call; a test sets them with set_option)
+
 # Every output array starts as a sentinel, not as zeros: an entry the library leaves unwritten fails any comparison at once
 # instead of passing wherever 0 is the expected value.
 SENTINEL_I32 = -0x5A5A5A5B              # 0xA5A5A5A5
@@ -83,6 +86,16 @@ class KombAccel:
         """komb_set_option: a tuning / test switch of this context (None unsets).  No option changes a result."""
         v = None if value is None else str(value).encode()
         self._check(self._lib.komb_set_option(self._ctx, name.encode(), v))
+
+    def alloc_info(self):
+        """komb_alloc_info: the allocation-request counter of options ALLOC_FAIL_AT / ALLOC_TRIM_AT and the pool's state (host
+        state only; works without a device)."""
+        req, used, nbytes, cached, trims = (ctypes.c_int64() for _ in range(5))
+        fired = ctypes.c_int32()
+        self._check(self._lib.komb_alloc_info(self._ctx, ctypes.byref(req), ctypes.byref(fired), ctypes.byref(used), ctypes.byref(nbytes),
+                                              ctypes.byref(cached), ctypes.byref(trims)))
+        return {"requests": req.value, "fired": fired.value, "pool_blocks_in_use": used.value, "pool_bytes_in_use": nbytes.value,
+                "pool_blocks_cached": cached.value, "trims": trims.value}
 
     def _sync_env_options(self):
         if not FORWARD_ENV_OPTIONS:

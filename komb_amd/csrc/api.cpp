@@ -978,7 +978,39 @@ int komb_set_option(komb_ctx *ctx, const char *name, const char *value)
             p.on = true; p.word = (uint32_t)w; p.stream = ctx->stream;
         }
     }
+    const bool fail_at = !strcmp(name, "ALLOC_FAIL_AT");
+    if (fail_at || !strcmp(name, "ALLOC_TRIM_AT")) { // one-shot triggers on the count of device allocation requests (common.h: AllocHook)
+        AllocHook &h = ctx->pool.hook;
+        long long n = 0;
+        if (value) {
+            char *end = nullptr;
+            errno = 0;
+            n = strtoll(value, &end, 10);
+            if (!*value || *end || errno || n < 0 || value[0] < '0' || value[0] > '9')
+                KOMB_FAIL(ctx, KOMB_ERR_ARG, "option %s=%s: expected a request number (0: count only)", name, value);
+        }
+        if (fail_at) { h.fail_at = n; h.fired = 0; } else h.trim_at = n;
+        if (value) h.requests = 0;                   // both count from the moment either was last set
+        h.armed = ctx->options.count(fail_at ? "ALLOC_TRIM_AT" : "ALLOC_FAIL_AT") || value;
+    }
     if (value) ctx->options[name] = value; else ctx->options.erase(name);
+    return KOMB_OK;
+}
+
+int komb_alloc_info(komb_ctx *ctx, int64_t *requests, int32_t *fired, int64_t *pool_blocks_in_use, int64_t *pool_bytes_in_use,
+                    int64_t *pool_blocks_cached, int64_t *trims)
+{
+    if (!ctx) return KOMB_ERR_ARG;                   // host state only: no device needed
+    int64_t used = 0, used_bytes = 0, cached = 0;
+    for (const auto &b : ctx->pool.blocks) {
+        if (b.used) { ++used; used_bytes += (int64_t)b.bytes; } else ++cached;
+    }
+    if (requests) *requests = ctx->pool.hook.requests;
+    if (fired) *fired = ctx->pool.hook.fired;
+    if (pool_blocks_in_use) *pool_blocks_in_use = used;
+    if (pool_bytes_in_use) *pool_bytes_in_use = used_bytes;
+    if (pool_blocks_cached) *pool_blocks_cached = cached;
+    if (trims) *trims = (int64_t)ctx->pool.n_trim;
     return KOMB_OK;
 }
 

@@ -154,10 +154,31 @@ struct EventSet {
 // 32-bit word before it is returned, so a kernel or host step that reads memory it never wrote sees garbage instead of the
 // zeros of a fresh page or the previous run's values (tests only; off, it costs one branch per allocation).  The fill is
 // waited for: the graph upload writes on the staging streams, not on the context's.
+// Options ALLOC_FAIL_AT / ALLOC_TRIM_AT (komb_set_option; tests only): one counter over every device allocation request of the
+// context -- DevPool::get and Poison::malloc, the two places all of them pass through -- and two one-shot triggers on it.
+// Request number fail_at (1-based, counted from the moment the option was set) returns hipErrorOutOfMemory before anything is
+// done: no hipMalloc, no trim(), nothing on the device.  Request number trim_at, when it is a pool request, gives the cached
+// blocks back to the driver first (trim(), what a real near-out-of-memory request does before it retries) and is then served
+// normally.  Both disarm when they fire.  `armed` is the one branch a request pays with neither option set.
+struct AllocHook {
+    bool armed = false;                              // counting, or a trigger waits
+    int64_t requests = 0, fail_at = 0, trim_at = 0;  // 0: no trigger
+    int32_t fired = 0;                               // the fail trigger has fired since it was last set
+    enum Act { PASS, FAIL, TRIM };
+    Act step()                                       // one request (called only while armed)
+    {
+        ++requests;
+        if (fail_at && requests == fail_at) { fail_at = 0; fired = 1; return FAIL; }
+        if (trim_at && requests == trim_at) { trim_at = 0; return TRIM; }
+        return PASS;
+    }
+};
+
 struct Poison {
     bool on = false;
     uint32_t word = 0;
     hipStream_t stream = nullptr;                    // the context's stream
+    AllocHook *hook = nullptr;                       // the pool's (DevPool::hook): the allocations outside the pool count on it too
     hipError_t fill(void *p, size_t bytes) const
     {
         if (!on || !p || !bytes) return hipSuccess;
@@ -169,6 +190,7 @@ struct Poison {
     }
     hipError_t malloc(void **out, size_t bytes) const  // hipMalloc, then the fill (the one allocation path outside the pool)
     {
+        if (hook && hook->armed && hook->step() == AllocHook::FAIL) return hipErrorOutOfMemory;
         void *q = nullptr;
         hipError_t e = hipMalloc(&q, bytes);
         if (e != hipSuccess) return e;
@@ -187,8 +209,17 @@ struct DevPool {
     size_t n_malloc = 0, n_trim = 0;                 // statistics (KOMB_POOL_DEBUG)
     double ms_malloc = 0.0;                          // host time inside hipMalloc
     Poison poison;                                   // option POISON (above); also what the allocations outside the pool use
+    AllocHook hook;                                  // options ALLOC_FAIL_AT / ALLOC_TRIM_AT (above)
+    DevPool() { poison.hook = &hook; }
+    DevPool(const DevPool &) = delete;               // (poison.hook points into this object)
+    DevPool &operator=(const DevPool &) = delete;
     hipError_t get(void **out, size_t bytes)
     {
+        if (hook.armed) {
+            const AllocHook::Act a = hook.step();
+            if (a == AllocHook::FAIL) return hipErrorOutOfMemory;
+            if (a == AllocHook::TRIM) { ++n_trim; trim(); }
+        }
         if (bytes == 0) bytes = 16;
         int best = -1;
         for (int i = 0; i < (int)blocks.size(); ++i)
@@ -469,6 +500,18 @@ struct komb_ctx {
 // every device allocation outside the pool (the resident graph, the k-core results, the graph build's scratch): hipMalloc,
 // then the POISON fill when that option is set
 inline hipError_t dev_malloc(komb_ctx *ctx, void **out, size_t bytes) { return ctx->pool.poison.malloc(out, bytes); }
+// two arrays that only make sense together (a result's two halves, made on its first run): both or neither.  The pointers are
+// published only when both exist -- a run that finds the first one set takes the second for granted.
+template <class A, class B> inline hipError_t dev_malloc_pair(komb_ctx *ctx, A **a, size_t a_bytes, B **b, size_t b_bytes)
+{
+    void *pa = nullptr, *pb = nullptr;
+    hipError_t e = dev_malloc(ctx, &pa, a_bytes);
+    if (e != hipSuccess) return e;
+    e = dev_malloc(ctx, &pb, b_bytes);
+    if (e != hipSuccess) { (void)hipFree(pa); return e; }
+    *a = (A *)pa; *b = (B *)pb;
+    return hipSuccess;
+}
 
 // ---- options (komb_set_option): what the library used to read from KOMB_* environment variables.  The drop-in never sets
 // any; tests and measurements do, explicitly, per context.

@@ -275,8 +275,8 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k)
     hipStream_t s = ctx->stream;
     ctx->comp_done = false;
     if (!ctx->d_comp_label) {
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_comp_label, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_comp_size, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
+        const size_t bytes = (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t);
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_comp_label, bytes, &ctx->d_comp_size, bytes));
     }
     ctx->comp_kind = kind; ctx->comp_k = k;
     ctx->comp_members = ctx->comp_count = ctx->comp_largest = 0; ctx->comp_ms = 0.0;

@@ -172,15 +172,17 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
     const int64_t nv = ctx->nv;
     hipStream_t s = ctx->stream;
     const bool truss = kind == KOMB_COMP_TRUSS;
-    ctx->hier_done = false;
     const size_t cap = (size_t)(nv > 0 ? nv : 1);            // nodes <= vertices (forest.hip)
-    if (!ctx->d_hier_nodes) {
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_hier_nodes, 5 * cap * sizeof(int32_t)));
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_hier_vnode, cap * sizeof(int32_t)));
+    if (!ctx->d_hier_nodes)
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_hier_nodes, 5 * cap * sizeof(int32_t), &ctx->d_hier_vnode, cap * sizeof(int32_t)));
+    // The result arrays are written by the last kernels of the run only, behind every allocation of the run, and the figures
+    // are installed at the end: a run that fails for memory leaves the previous result readable (include/komb_accel.h).
+    if (nv == 0) {
+        ctx->hier_kind = kind; ctx->hier_nodes = ctx->hier_roots = 0; ctx->hier_depth = 0; ctx->hier_ms = 0.0;
+        ctx->hier_kmax = truss ? 2 : 0;
+        ctx->hier_done = true;
+        return KOMB_OK;
     }
-    ctx->hier_kind = kind; ctx->hier_nodes = ctx->hier_roots = 0; ctx->hier_depth = 0; ctx->hier_ms = 0.0;
-    ctx->hier_kmax = truss ? 2 : 0;
-    if (nv == 0) { ctx->hier_done = true; return KOMB_OK; }
 
     const int64_t m = truss ? ctx->t_ne : 0;
     if (truss && m > 0) KOMB_TRY(truss_edges_canonical(ctx));       // (a whole-graph result whose endpoints no fetch has asked for yet)
@@ -297,10 +299,12 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
                     (uint32_t *)ctx->d_hier_nodes + 3 * cap, (uint32_t *)ctx->d_hier_nodes + 4 * cap};
     int32_t *rank = cur;                                      // (cur[] has served; n <= nv)
     if (n > 0) KOMB_TRY(forest_tail(ctx, bufs, f, n, bits, out, rank, nullptr, vvals, vvals2));   // (the vertices' sort has served: n <= nv)
+    ctx->hier_done = false;                                   // from here on the previous result is being overwritten
     k_hier_vertices_out<<<grid, kBlock, 0, s>>>((uint32_t)nv, vnode, rank, ctx->d_hier_vnode);
     const double ms = ctx->timer.stop(s);
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(HierCtl)));
+    ctx->hier_kind = kind;
     ctx->hier_nodes = (int64_t)n; ctx->hier_roots = (int64_t)h.f.n_roots; ctx->hier_depth = h.f.depth;
     ctx->hier_kmax = n > 0 ? k_top : k_min;
     ctx->hier_ms = ms;

@@ -246,8 +246,8 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
     hipStream_t s = ctx->stream;
     ctx->core_done = false;
     if (!ctx->d_deg) {
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_deg, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_core, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
+        const size_t bytes = (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t);
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_deg, bytes, &ctx->d_core, bytes));
     }
     komb_stats &stt = ctx->stats;
     stt.core_levels = stt.core_subrounds = stt.core_launches = 0;

@@ -325,7 +325,7 @@ int truss_support_canonical(komb_ctx *ctx)
         KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_fetch_support: no k-truss result to take the supports from");
     hipStream_t s = ctx->stream;
     const int64_t m = ctx->t_ne;
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_sup, (size_t)m * sizeof(int32_t)));
+    if (!ctx->d_t_sup) KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_sup, (size_t)m * sizeof(int32_t)));   // (a call that failed behind this left it)
 #ifndef KOMB_TEST_SKIP_SLICE_ZERO                                    // (negative control of the poisoned-memory tests only: tests/manual)
     if (ctx->t_k_lo) KOMB_HIP(ctx, hipMemsetAsync(ctx->d_t_sup, 0, (size_t)ctx->t_k_lo * sizeof(int32_t), s));
     if (ctx->t_k_hi < (uint32_t)m) KOMB_HIP(ctx, hipMemsetAsync(ctx->d_t_sup + ctx->t_k_hi, 0, ((size_t)m - ctx->t_k_hi) * sizeof(int32_t), s));
@@ -336,9 +336,8 @@ int truss_support_canonical(komb_ctx *ctx)
     return KOMB_OK;
 }
 
-// rank/world/fn: support counting is sharded by source-vertex range; fn sums the
-// partial support vectors over the ranks (RCCL all-reduce on the host side).
-int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user)
+namespace {
+int truss_run_body(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user)
 {
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !fn))
         KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_run_sharded: bad rank %d / world %d / callback", rank, world);
@@ -350,8 +349,14 @@ int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, kom
     st.max_trussness = 0; st.ms_support = st.ms_peel = st.ms_orient = st.ms_tri_count = st.ms_tri_fill = st.ms_gather = st.ms_allreduce = st.ms_compact = 0.0;
     st.truss_scans = 0; st.ms_prepare = 0.0; st.truss_prepared = 0; st.ms_prep_vertex = st.ms_prep_edges = st.ms_prep_rows = 0.0;
     auto empty_result = [&]() -> int {
-        KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_eu, 4)); KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_ev, 4));
-        KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_truss, 4)); KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_sup, 4));
+        void *q[4] = {nullptr, nullptr, nullptr, nullptr};          // (published only when all four exist: nothing stays held by a failure)
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = ctx->pool.get(&q[i], 4);
+        if (e != hipSuccess) {
+            for (void *p : q) ctx->pool.put(p);
+            KOMB_HIP(ctx, e);
+        }
+        ctx->d_t_eu = (int32_t *)q[0]; ctx->d_t_ev = (int32_t *)q[1]; ctx->d_t_truss = (int32_t *)q[2]; ctx->d_t_sup = (int32_t *)q[3];
         ctx->t_own_edges = true; ctx->t_ne = 0; ctx->truss_done = true; ctx->t_sup_ready = true;
         return KOMB_OK;
     };
@@ -891,7 +896,6 @@ int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, kom
     bufs.detach(d_off2);
     ctx->t_sup_ready = false;
     if (vmask_host) {                                                // (the subgraph's preparation goes with this call: its supports are put in order now)
-        ctx->t_ne = m;
         KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_t_sup, (size_t)m * sizeof(int32_t)));
         k_scatter_len<<<grid_for(m), kBlock, 0, s>>>(ctx->d_t_slice, tp->e2k, m, 0u, (uint32_t)m, ctx->d_t_sup);
         ctx->t_sup_ready = true;
@@ -903,9 +907,21 @@ int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, kom
         fprintf(stderr, "komb pool: %zu blocks, %.2f GB held, %zu hipMalloc calls so far (%.1f ms inside them), %zu trims\n", ctx->pool.blocks.size(), held / 1e9, ctx->pool.n_malloc, ctx->pool.ms_malloc, ctx->pool.n_trim);
     }
     if (vmask_host) KOMB_HIP(ctx, hipStreamSynchronize(s));         // (the subgraph's arrays go back to the pool on return)
-    ctx->t_ne = m;
+    ctx->t_ne = m;                                                   // (published with truss_done: nothing reads one without the other)
     ctx->truss_done = true;
     return KOMB_OK;
+}
+} // namespace
+
+// rank/world/fn: support counting is sharded by source-vertex range; fn sums the
+// partial support vectors over the ranks (RCCL all-reduce on the host side).
+// A run that fails or is refused after it has dropped the previous result leaves NO k-truss result: whatever it had already
+// installed of the new one (pool blocks) goes back, so that nothing stays held that no entry point can reach.
+int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user)
+{
+    const int rc = truss_run_body(ctx, vmask_host, rank, world, fn, user);
+    if (rc != KOMB_OK && !ctx->truss_done) truss_free(ctx);
+    return rc;
 }
 
 } // namespace komb

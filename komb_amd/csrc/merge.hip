@@ -156,9 +156,11 @@ int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *s
     // 20 000 vertices, minutes for millions, on a stream nothing can cancel.  The exact tie order makes the peel sequential
     // (DESIGN.md section 9), so large graphs are refused rather than left to occupy the device.
     if (nv > kMergeMaxNodes) KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_densest_block: %lld nodes; the exact (sequential) densest-block peel is limited to %d", (long long)nv, kMergeMaxNodes);
-    if (n_block) *n_block = 0;
-    if (max_density) *max_density = 0.0;
-    if (nv == 0) return KOMB_OK;
+    if (nv == 0) {                                           // (a call that fails below writes no output at all)
+        if (n_block) *n_block = 0;
+        if (max_density) *max_density = 0.0;
+        return KOMB_OK;
+    }
     Range r_all("komb_densest_block");
     hipStream_t s = ctx->stream;
     DevBufs bufs(ctx);

@@ -90,8 +90,8 @@ int onion_run(komb_ctx *ctx)
     hipStream_t s = ctx->stream;
     ctx->onion_done = false;
     if (!ctx->d_onion_layer) {
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_onion_layer, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
-        KOMB_HIP(ctx, dev_malloc(ctx, (void **)&ctx->d_onion_core, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
+        const size_t bytes = (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t);
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_onion_layer, bytes, &ctx->d_onion_core, bytes));
     }
     if (nv == 0) {
         ctx->onion_layers = 0; ctx->onion_max_core = 0; ctx->onion_ms = 0.0;

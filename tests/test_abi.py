@@ -32,6 +32,23 @@ def test_abi_version(built):
     assert komb_amd._lib.load().komb_abi_version() == 7
 
 
+def test_alloc_info_binding(built):
+    """komb_alloc_info is bound with the types and in the order the header declares: requests, fired, and the pool's four
+    figures, every one an output pointer; the Python method names them as the header does."""
+    import komb_amd
+    text = open(os.path.join(ROOT, "include", "komb_accel.h")).read()
+    decl = re.search(r"int\s+komb_alloc_info\((.*?)\);", text, flags=re.S).group(1)
+    params = [" ".join(x.split()) for x in decl.split(",")]
+    assert params == ["komb_ctx *ctx", "int64_t *requests", "int32_t *fired", "int64_t *pool_blocks_in_use", "int64_t *pool_bytes_in_use",
+                      "int64_t *pool_blocks_cached", "int64_t *trims"]
+    res, args = komb_amd._lib.SIGNATURES["komb_alloc_info"]
+    ctype = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}
+    assert res is ctypes.c_int and args[0] is ctypes.c_void_p
+    assert args[1:] == [ctypes.POINTER(ctype[x.split()[0]]) for x in params[1:]]
+    with komb_amd.KombAccel() as a:
+        assert list(a.alloc_info()) == [x.split("*")[1] for x in params[1:]]
+
+
 def test_stats_struct_matches_header(built):
     """ctypes mirror of komb_stats has the fields of the header, in order."""
     import komb_amd
