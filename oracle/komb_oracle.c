@@ -628,3 +628,384 @@ int32_t orc_run_merge(int64_t nv, const int64_t *rowptr, const int32_t *col, con
     if (max_density) *max_density = best;
     return best_left;
 }
+
+/* ============================================================ cliques and nuclei
+ * References for the analyses that walk cliques on the GPU (the clique census, the maximal cliques and, through them, the
+ * maximum cliques) and for the (3,4)-nucleus decomposition.  They restate DEFINITIONS (include/komb_accel.h), not the
+ * library's decomposition: the walks start at a VERTEX, not at a canonical edge; every set is a sorted array and every step a
+ * sorted-array intersection over the CSR rows; there is no bit matrix, no pivot and no trussness anywhere (t_max, which only
+ * sizes the library's windows, comes from orc_trussness in oracle.py).  tests/test_oracle_cliques.py ties them to the Python
+ * restatements, to networkx and to one recorded run. */
+
+struct arena { int32_t *p; int64_t cap; };
+static void arena_need(struct arena *A, int64_t n)
+{
+    if (n <= A->cap) return;
+    int64_t cap = A->cap ? A->cap : 1024;
+    while (cap < n) cap *= 2;
+    A->p = (int32_t *)realloc(A->p, (size_t)cap * sizeof(int32_t));
+    A->cap = cap;
+}
+
+/* out = a & b, both ascending; the shorter one is walked, the longer one bisected when it is much longer, else merged */
+static int32_t isect(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int32_t *out)
+{
+    if (na > nb) { const int32_t *t = a; a = b; b = t; int64_t tn = na; na = nb; nb = tn; }
+    int32_t n = 0;
+    if (na * 4 < nb) {
+        int64_t lo = 0;
+        for (int64_t i = 0; i < na && lo < nb; ++i) {
+            int64_t l = lo, h = nb;
+            while (l < h) { int64_t mid = l + ((h - l) >> 1); if (b[mid] < a[i]) l = mid + 1; else h = mid; }
+            lo = l;
+            if (l < nb && b[l] == a[i]) { out[n++] = a[i]; lo = l + 1; }
+        }
+        return n;
+    }
+    int64_t i = 0, j = 0;
+    while (i < na && j < nb) {
+        if (a[i] < b[j]) ++i;
+        else if (a[i] > b[j]) ++j;
+        else { out[n++] = a[i]; ++i; ++j; }
+    }
+    return n;
+}
+
+static inline uint64_t sat_add(uint64_t a, uint64_t b) { const uint64_t s = a + b; return s < a ? UINT64_MAX : s; }
+
+/* row[j] = min(C(n, j), 2^64 - 1), j = 0 .. n: Pascal's rule with saturating adds (adds of non-negative numbers, so exact) */
+static void binom_row(int32_t n, uint64_t *row)
+{
+    row[0] = 1;
+    for (int32_t j = 1; j <= n; ++j) row[j] = 0;
+    for (int32_t i = 1; i <= n; ++i)
+        for (int32_t j = i; j >= 1; --j) row[j] = sat_add(row[j], row[j - 1]);
+}
+
+static int32_t max_upper_degree(int64_t nv, const int64_t *rowptr, const int64_t *ustart)
+{
+    int64_t mx = 0;
+    for (int64_t v = 0; v < nv; ++v) if (rowptr[v + 1] - ustart[v] > mx) mx = rowptr[v + 1] - ustart[v];
+    return (int32_t)mx;
+}
+
+/* ---------------------------------------------------------------- clique census
+ * Definition: total[k] = the k-cliques, local[v] = the k_local-cliques through v (include/komb_accel.h, "clique census").
+ * Plain ordered enumeration: a clique is visited once, as its ascending tuple; the node of the tuple (v_1 .. v_d) holds
+ * P = the common neighbours above v_d and has one child per member of P.  Every node at depth d is one d-clique.
+ * One exception, for inputs like K_70 whose 2^70 cliques nothing enumerates: a node whose P has ORC_CLOSED_FROM or more
+ * vertices and is itself a clique is closed by binomials (the tuples below it are the subsets of P).  The graphs the
+ * mid-size tests use have omega <= 16, so there every clique is visited, and *n_nodes (the cliques visited) says so: it
+ * equals the sum of the totals exactly when nothing was closed. */
+#define ORC_CLOSED_FROM 20
+
+struct cc {
+    const int64_t *rowptr, *ustart; const int32_t *col;
+    int32_t k_cap, k_local, omega;
+    uint64_t *total, *local, *row, *row1, nodes;
+    int32_t *held;
+    struct arena A;
+};
+
+static int cc_complete(struct cc *C, int64_t off, int32_t p)
+{
+    for (int32_t i = 0; i + 1 < p; ++i) {
+        const int32_t x = C->A.p[off + i];
+        if (isect(C->A.p + off + i + 1, p - i - 1, C->col + C->ustart[x], C->rowptr[x + 1] - C->ustart[x], C->A.p + off + p) != p - i - 1) return 0;
+    }
+    return 1;
+}
+
+static void cc_node(struct cc *C, int32_t d, int64_t off, int32_t p)
+{
+    if (d >= 2) {
+        C->nodes++;
+        if (d <= C->k_cap) C->total[d] = sat_add(C->total[d], 1);
+        if (d > C->omega) C->omega = d;
+        if (d == C->k_local) for (int32_t i = 0; i < d; ++i) C->local[C->held[i]] = sat_add(C->local[C->held[i]], 1);
+    }
+    if (p == 0) return;
+    arena_need(&C->A, off + 2 * (int64_t)p);
+    if (p >= ORC_CLOSED_FROM && cc_complete(C, off, p)) {
+        binom_row(p - 1, C->row1);
+        binom_row(p, C->row);
+        for (int32_t j = 1; j <= p; ++j) if (d + j <= C->k_cap) C->total[d + j] = sat_add(C->total[d + j], C->row[j]);
+        if (d + p > C->omega) C->omega = d + p;
+        const int32_t j = C->k_local - d;
+        if (C->k_local && j >= 1 && j <= p) {
+            for (int32_t i = 0; i < d; ++i) C->local[C->held[i]] = sat_add(C->local[C->held[i]], C->row[j]);
+            for (int32_t i = 0; i < p; ++i) C->local[C->A.p[off + i]] = sat_add(C->local[C->A.p[off + i]], C->row1[j - 1]);
+        }
+        return;
+    }
+    for (int32_t i = 0; i < p; ++i) {
+        const int32_t x = C->A.p[off + i];
+        const int32_t n = isect(C->A.p + off + i + 1, p - i - 1, C->col + C->ustart[x], C->rowptr[x + 1] - C->ustart[x], C->A.p + off + p);
+        C->held[d] = x;
+        cc_node(C, d + 1, off + p, n);
+    }
+}
+
+int32_t orc_clique_census(int64_t nv, const int64_t *rowptr, const int32_t *col, int32_t k_cap, int32_t k_local,
+                          uint64_t *total, uint64_t *local, int32_t *saturated, uint64_t *n_nodes)
+{
+    if (nv < 0 || k_cap < 2 || k_local < 0 || (k_local && !local)) return -1;
+    int64_t *ustart = (int64_t *)malloc((size_t)(nv + 1) * sizeof(int64_t));
+    int64_t *ebase = (int64_t *)malloc((size_t)(nv + 1) * sizeof(int64_t));
+    upper_index(nv, rowptr, col, ustart, ebase);
+    const int32_t mud = max_upper_degree(nv, rowptr, ustart);
+    struct cc C = { rowptr, ustart, col, k_cap, k_local, 0, total, local, NULL, NULL, 0, NULL, { NULL, 0 } };
+    C.row = (uint64_t *)malloc((size_t)(mud + 2) * sizeof(uint64_t));
+    C.row1 = (uint64_t *)malloc((size_t)(mud + 2) * sizeof(uint64_t));
+    C.held = (int32_t *)malloc((size_t)(mud + 3) * sizeof(int32_t));
+    memset(total, 0, (size_t)(k_cap + 1) * sizeof(uint64_t));
+    if (local) memset(local, 0, (size_t)(nv > 0 ? nv : 1) * sizeof(uint64_t));
+    for (int64_t v = 0; v < nv; ++v) {
+        const int32_t p = (int32_t)(rowptr[v + 1] - ustart[v]);
+        if (!p) continue;
+        arena_need(&C.A, p);
+        memcpy(C.A.p, col + ustart[v], (size_t)p * sizeof(int32_t));
+        C.held[0] = (int32_t)v;
+        cc_node(&C, 1, 0, p);
+    }
+    int sat = 0;
+    for (int32_t k = 0; k <= k_cap; ++k) sat |= total[k] == UINT64_MAX;
+    if (k_local) for (int64_t v = 0; v < nv; ++v) sat |= local[v] == UINT64_MAX;
+    if (saturated) *saturated = sat;
+    if (n_nodes) *n_nodes = C.nodes;
+    free(ustart); free(ebase); free(C.row); free(C.row1); free(C.held); free(C.A.p);
+    return C.omega;
+}
+
+/* --------------------------------------------------------------- maximal cliques
+ * Definition: a clique contained in no larger one (include/komb_accel.h, "maximal cliques"); those of >= k_min vertices are
+ * reported.  The PIVOT-FREE form: the same ordered enumeration of every clique as above, the node of (v_1 .. v_d) carrying
+ * C = the intersection of its members' FULL neighbourhoods; its children are the members of C above v_d, and the clique is
+ * maximal exactly when C is empty.  Ascending tuples in depth-first order come out in lexicographic order (no maximal clique
+ * is a prefix of another), so the list needs no sort. */
+struct mx {
+    const int64_t *rowptr; const int32_t *col;
+    int32_t k_cap, k_min, omega, want_list, bad;
+    int64_t *hist; int32_t *count, *largest, *held;
+    int64_t n_c, n_v, cap_c, cap_v, *off; int32_t *verts;
+    uint64_t nodes;
+    struct arena A;
+};
+
+static void mx_node(struct mx *M, int32_t d, int64_t off, int32_t c, int32_t last)
+{
+    M->nodes++;
+    if (c == 0) {
+        if (d < 2) return;
+        if (d <= M->k_cap) M->hist[d]++; else M->bad = 1;
+        if (d < M->k_min) return;
+        if (d > M->omega) M->omega = d;
+        for (int32_t i = 0; i < d; ++i) { const int32_t v = M->held[i]; M->count[v]++; if (M->largest[v] < d) M->largest[v] = d; }
+        if (M->want_list) {
+            if (M->n_c + 2 > M->cap_c) { M->cap_c *= 2; M->off = (int64_t *)realloc(M->off, (size_t)M->cap_c * sizeof(int64_t)); }
+            if (M->n_v + d > M->cap_v) { while (M->n_v + d > M->cap_v) M->cap_v *= 2; M->verts = (int32_t *)realloc(M->verts, (size_t)M->cap_v * sizeof(int32_t)); }
+            memcpy(M->verts + M->n_v, M->held, (size_t)d * sizeof(int32_t));
+            M->n_v += d;
+            M->off[M->n_c + 1] = M->n_v;
+        }
+        M->n_c++;
+        return;
+    }
+    arena_need(&M->A, off + 2 * (int64_t)c);
+    for (int32_t i = 0; i < c; ++i) {
+        const int32_t x = M->A.p[off + i];
+        if (x <= last) continue;
+        const int32_t n = isect(M->A.p + off, c, M->col + M->rowptr[x], M->rowptr[x + 1] - M->rowptr[x], M->A.p + off + c);
+        M->held[d] = x;
+        mx_node(M, d + 1, off + c, n, x);
+    }
+}
+
+int64_t orc_maximal_cliques(int64_t nv, const int64_t *rowptr, const int32_t *col, int32_t k_min, int32_t k_cap,
+                            int64_t *hist, int32_t *count, int32_t *largest, int32_t *omega, uint64_t *n_nodes,
+                            int64_t **offset_out, int32_t **verts_out, int64_t *n_verts)
+{
+    if (nv < 0 || k_min < 2 || k_cap < 2) return -1;
+    int64_t mdeg = 0;
+    for (int64_t v = 0; v < nv; ++v) if (rowptr[v + 1] - rowptr[v] > mdeg) mdeg = rowptr[v + 1] - rowptr[v];
+    struct mx M = { rowptr, col, k_cap, k_min, 0, offset_out && verts_out, 0, hist, count, largest, NULL, 0, 0, 0, 0, NULL, NULL, 0, { NULL, 0 } };
+    M.held = (int32_t *)malloc((size_t)(mdeg + 3) * sizeof(int32_t));
+    memset(hist, 0, (size_t)(k_cap + 1) * sizeof(int64_t));
+    memset(count, 0, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t));
+    memset(largest, 0, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t));
+    if (M.want_list) { M.cap_c = 4096; M.off = (int64_t *)malloc((size_t)M.cap_c * sizeof(int64_t)); M.off[0] = 0; M.cap_v = 16384; M.verts = (int32_t *)malloc((size_t)M.cap_v * sizeof(int32_t)); }
+    for (int64_t v = 0; v < nv; ++v) {
+        const int32_t c = (int32_t)(rowptr[v + 1] - rowptr[v]);
+        if (!c) continue;
+        arena_need(&M.A, c);
+        memcpy(M.A.p, col + rowptr[v], (size_t)c * sizeof(int32_t));
+        M.held[0] = (int32_t)v;
+        mx_node(&M, 1, 0, c, (int32_t)v);
+    }
+    free(M.held); free(M.A.p);
+    if (omega) *omega = M.omega;
+    if (n_nodes) *n_nodes = M.nodes;
+    if (n_verts) *n_verts = M.n_v;
+    if (M.want_list) { *offset_out = M.off; *verts_out = M.verts; }
+    return M.bad ? -1 : M.n_c;
+}
+
+void orc_free(void *p) { free(p); }
+
+/* ------------------------------------------------------- (3,4)-nucleus decomposition
+ * Definition: include/komb_accel.h, "(3,4)-nucleus decomposition".  Triangles a < b < c in ascending (a, b, c) order, which is
+ * the order tests/nucleus_ref.py lists them in (canonical edge (a, b), then c); the 4-cliques a < b < c < d in the order
+ * (triangle (a, b, c), d), each as the ids of its four triangles (a,b,c), (a,b,d), (a,c,d), (b,c,d); key0 = the cliques per
+ * triangle; theta by a sequential bucket peel (Batagelj-Zaversnik's bins over the triangles: the triangle with the fewest
+ * cliques left goes next, takes that number as theta and retires its cliques, each of which costs its other unprocessed
+ * triangles above the level one).  The GPU's peel is level-synchronous over frontiers; theta is unique. */
+struct nuc {
+    int64_t nv; const int64_t *rowptr; const int32_t *col; int64_t *ustart, *ebase;
+    int64_t ne, *tri_base; int32_t *tc;
+};
+
+static int64_t nuc_edge(const struct nuc *N, int32_t a, int32_t b)
+{
+    return N->ebase[a] + (find_sorted(N->col, N->ustart[a], N->rowptr[a + 1], b) - N->ustart[a]);
+}
+
+static int64_t nuc_tid(const struct nuc *N, int32_t a, int32_t b, int32_t c)
+{
+    const int64_t e = nuc_edge(N, a, b);
+    return find_sorted(N->tc, N->tri_base[e], N->tri_base[e + 1], c);
+}
+
+/* the triangles: tri_base[e] .. tri_base[e + 1] are those of canonical edge e, tc their third vertices ascending */
+static int64_t nuc_triangles(struct nuc *N)
+{
+    N->ustart = (int64_t *)malloc((size_t)(N->nv + 1) * sizeof(int64_t));
+    N->ebase = (int64_t *)malloc((size_t)(N->nv + 1) * sizeof(int64_t));
+    upper_index(N->nv, N->rowptr, N->col, N->ustart, N->ebase);
+    N->ne = N->ebase[N->nv];
+    N->tri_base = (int64_t *)calloc((size_t)N->ne + 1, sizeof(int64_t));
+    const int32_t mud = max_upper_degree(N->nv, N->rowptr, N->ustart);
+    int32_t *tmp = (int32_t *)malloc((size_t)(mud + 1) * sizeof(int32_t));
+    int64_t cap = 1024, nt = 0;
+    N->tc = (int32_t *)malloc((size_t)cap * sizeof(int32_t));
+    for (int64_t a = 0; a < N->nv; ++a)
+        for (int64_t j = N->ustart[a]; j < N->rowptr[a + 1]; ++j) {
+            const int32_t b = N->col[j];
+            const int32_t n = isect(N->col + j + 1, N->rowptr[a + 1] - j - 1, N->col + N->ustart[b], N->rowptr[b + 1] - N->ustart[b], tmp);
+            if (nt + n > cap) { while (nt + n > cap) cap *= 2; N->tc = (int32_t *)realloc(N->tc, (size_t)cap * sizeof(int32_t)); }
+            memcpy(N->tc + nt, tmp, (size_t)n * sizeof(int32_t));
+            nt += n;
+            N->tri_base[N->ebase[a] + (j - N->ustart[a]) + 1] = nt;
+        }
+    free(tmp);
+    return nt;
+}
+
+static void nuc_free(struct nuc *N) { free(N->ustart); free(N->ebase); free(N->tri_base); free(N->tc); }
+
+/* every 4-clique once, in (triangle, d) order; quads == NULL only counts */
+static int64_t nuc_cliques(const struct nuc *N, int32_t *ta, int32_t *tb, int32_t *quads)
+{
+    int64_t nq = 0;
+    for (int64_t a = 0; a < N->nv; ++a)
+        for (int64_t j = N->ustart[a]; j < N->rowptr[a + 1]; ++j) {
+            const int32_t b = N->col[j];
+            const int64_t e = N->ebase[a] + (j - N->ustart[a]);
+            for (int64_t t = N->tri_base[e]; t < N->tri_base[e + 1]; ++t) {
+                const int32_t c = N->tc[t];
+                if (ta) { ta[t] = (int32_t)a; tb[t] = b; }
+                for (int64_t t2 = t + 1; t2 < N->tri_base[e + 1]; ++t2) {          /* d > c next to a and b */
+                    const int32_t d = N->tc[t2];
+                    if (find_sorted(N->col, N->ustart[c], N->rowptr[c + 1], d) < 0) continue;
+                    if (quads) {
+                        quads[4 * nq] = (int32_t)t; quads[4 * nq + 1] = (int32_t)t2;
+                        quads[4 * nq + 2] = (int32_t)nuc_tid(N, (int32_t)a, c, d); quads[4 * nq + 3] = (int32_t)nuc_tid(N, b, c, d);
+                    }
+                    nq++;
+                }
+            }
+        }
+    return nq;
+}
+
+int64_t orc_nucleus_count(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t *n_cliques4)
+{
+    struct nuc N = { nv, rowptr, col, NULL, NULL, 0, NULL, NULL };
+    const int64_t nt = nuc_triangles(&N);
+    if (n_cliques4) *n_cliques4 = nuc_cliques(&N, NULL, NULL, NULL);
+    nuc_free(&N);
+    return nt;
+}
+
+int32_t orc_nucleus(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t n_triangles, int64_t n_cliques4,
+                    int32_t *a, int32_t *b, int32_t *c, int32_t *key0, int32_t *theta,
+                    int32_t *edge_theta, int32_t *vertex_theta, int32_t *quads)
+{
+    struct nuc N = { nv, rowptr, col, NULL, NULL, 0, NULL, NULL };
+    const int64_t nt = nuc_triangles(&N);
+    if (nt != n_triangles || nt > INT32_MAX) { nuc_free(&N); return -2; }
+    const int64_t nq = nuc_cliques(&N, a, b, NULL);
+    if (nq != n_cliques4 || nq > INT32_MAX / 4) { nuc_free(&N); return -2; }
+    nuc_cliques(&N, a, b, quads);
+    memcpy(c, N.tc, (size_t)nt * sizeof(int32_t));
+    for (int64_t v = 0; v < nv; ++v) vertex_theta[v] = -1;
+    for (int64_t e = 0; e < N.ne; ++e) edge_theta[e] = -1;
+    if (nt == 0) { nuc_free(&N); return -1; }
+
+    /* incidences: inc[ip[t] .. ip[t + 1]) = the cliques of triangle t */
+    int64_t *ip = (int64_t *)calloc((size_t)nt + 1, sizeof(int64_t));
+    for (int64_t i = 0; i < 4 * nq; ++i) ip[quads[i] + 1]++;
+    int32_t maxk = 0;
+    for (int64_t t = 0; t < nt; ++t) { key0[t] = (int32_t)ip[t + 1]; if (key0[t] > maxk) maxk = key0[t]; ip[t + 1] += ip[t]; }
+    int32_t *inc = (int32_t *)malloc((size_t)(nq > 0 ? 4 * nq : 1) * sizeof(int32_t));
+    int64_t *cur = (int64_t *)malloc((size_t)(nt + 1) * sizeof(int64_t));
+    memcpy(cur, ip, (size_t)(nt + 1) * sizeof(int64_t));
+    for (int64_t q = 0; q < nq; ++q) for (int r = 0; r < 4; ++r) inc[cur[quads[4 * q + r]]++] = (int32_t)q;
+    free(cur);
+
+    /* the peel */
+    int32_t *key = (int32_t *)malloc((size_t)nt * sizeof(int32_t));
+    memcpy(key, key0, (size_t)nt * sizeof(int32_t));
+    int64_t *bin = (int64_t *)calloc((size_t)maxk + 2, sizeof(int64_t));
+    int64_t *pos = (int64_t *)malloc((size_t)nt * sizeof(int64_t));
+    int32_t *ord = (int32_t *)malloc((size_t)nt * sizeof(int32_t));
+    uint8_t *done = (uint8_t *)calloc((size_t)nt, 1), *gone = (uint8_t *)calloc((size_t)(nq > 0 ? nq : 1), 1);
+    for (int64_t t = 0; t < nt; ++t) bin[key[t]]++;
+    int64_t start = 0;
+    for (int32_t k = 0; k <= maxk; ++k) { const int64_t n = bin[k]; bin[k] = start; start += n; }
+    for (int64_t t = 0; t < nt; ++t) { pos[t] = bin[key[t]]; ord[pos[t]] = (int32_t)t; bin[key[t]]++; }
+    for (int32_t k = maxk; k > 0; --k) bin[k] = bin[k - 1];
+    bin[0] = 0;
+    int32_t tmax = 0;
+    for (int64_t i = 0; i < nt; ++i) {
+        const int32_t t = ord[i], k = key[t];
+        theta[t] = k;
+        if (k > tmax) tmax = k;
+        done[t] = 1;
+        for (int64_t x = ip[t]; x < ip[t + 1]; ++x) {
+            const int32_t q = inc[x];
+            if (gone[q]) continue;
+            gone[q] = 1;
+            for (int r = 0; r < 4; ++r) {
+                const int32_t u = quads[4 * (int64_t)q + r];
+                if (done[u] || key[u] <= k) continue;
+                const int32_t ku = key[u];
+                const int64_t pu = pos[u], pw = bin[ku];
+                const int32_t w = ord[pw];
+                if (u != w) { pos[u] = pw; pos[w] = pu; ord[pu] = w; ord[pw] = u; }
+                bin[ku]++;
+                key[u]--;
+            }
+        }
+    }
+    for (int64_t t = 0; t < nt; ++t) {
+        const int64_t e3[3] = { nuc_edge(&N, a[t], b[t]), nuc_edge(&N, a[t], c[t]), nuc_edge(&N, b[t], c[t]) };
+        const int32_t v3[3] = { a[t], b[t], c[t] };
+        for (int r = 0; r < 3; ++r) {
+            if (edge_theta[e3[r]] < theta[t]) edge_theta[e3[r]] = theta[t];
+            if (vertex_theta[v3[r]] < theta[t]) vertex_theta[v3[r]] = theta[t];
+        }
+    }
+    free(ip); free(inc); free(key); free(bin); free(pos); free(ord); free(done); free(gone);
+    nuc_free(&N);
+    return tmax;
+}

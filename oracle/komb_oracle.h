@@ -104,6 +104,39 @@ int32_t orc_run_merge(int64_t nv, const int64_t *rowptr, const int32_t *col, con
 int32_t orc_trussness_omp(int64_t nv, const int64_t *rowptr, const int32_t *col,
                           int32_t *truss, int nthreads);
 
+/* ---- references for the clique analyses and the (3,4)-nucleus decomposition (include/komb_accel.h has the definitions).
+ * Each walks from a VERTEX over sorted-array intersections of the CSR rows: no canonical-edge roots, no bit matrices, no
+ * pivots, no trussness -- nothing of the library's decomposition.  PINNED by tests/test_oracle_cliques.py against the Python
+ * restatements under tests/, networkx and one recorded run. */
+
+/* Clique census by plain ordered enumeration (a node at depth d is one d-clique; a candidate set of >= 20 vertices that is
+ * itself a clique is closed by binomials, which is what lets K_70 through).  total[k_cap + 1]: total[k] = min(the k-cliques,
+ * 2^64 - 1) for 2 <= k <= k_cap, entries 0 and 1 are 0; k_local != 0: local[nv] = the k_local-cliques through every vertex,
+ * saturating alike.  *saturated = some entry is 2^64 - 1; *n_nodes = the cliques visited one by one.  Returns the size of the largest
+ * clique (0 without an edge), -1 for bad arguments. */
+int32_t orc_clique_census(int64_t nv, const int64_t *rowptr, const int32_t *col, int32_t k_cap, int32_t k_local,
+                          uint64_t *total, uint64_t *local, int32_t *saturated, uint64_t *n_nodes);
+
+/* Maximal cliques, pivot-free: the same enumeration carrying the intersection of the members' full neighbourhoods; a clique
+ * is maximal when that is empty.  hist[k_cap + 1]: hist[k] = the maximal cliques of k >= 2 vertices (every size, whatever
+ * k_min); count[nv], largest[nv], *omega and the list cover those of >= k_min vertices.  The list (only with both pointers
+ * given) is malloc'ed here and the caller's to orc_free: clique i is verts[offset[i] .. offset[i + 1]), ascending, the
+ * cliques in lexicographic order.  Returns the cliques of >= k_min vertices, -1 for bad arguments or a clique above k_cap. */
+int64_t orc_maximal_cliques(int64_t nv, const int64_t *rowptr, const int32_t *col, int32_t k_min, int32_t k_cap,
+                            int64_t *hist, int32_t *count, int32_t *largest, int32_t *omega, uint64_t *n_nodes,
+                            int64_t **offset_out, int32_t **verts_out, int64_t *n_verts);
+void orc_free(void *p);
+
+/* (3,4)-nucleus decomposition.  orc_nucleus_count returns the triangles and writes the 4-cliques; orc_nucleus, given both,
+ * fills a, b, c, key0, theta [n_triangles] (triangles in ascending (a, b, c) order), edge_theta [ne] (canonical order, -1
+ * without a triangle), vertex_theta [nv] and quads [4 * n_cliques4]: clique a < b < c < d as the triangle ids of (a,b,c),
+ * (a,b,d), (a,c,d), (b,c,d), the cliques in (triangle (a,b,c), d) order.  theta by a sequential bucket peel.  Returns the
+ * largest theta, -1 without a triangle, -2 when the counts given are not the graph's. */
+int64_t orc_nucleus_count(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t *n_cliques4);
+int32_t orc_nucleus(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t n_triangles, int64_t n_cliques4,
+                    int32_t *a, int32_t *b, int32_t *c, int32_t *key0, int32_t *theta,
+                    int32_t *edge_theta, int32_t *vertex_theta, int32_t *quads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+_u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 _i64 = ctypes.c_int64
 
 
@@ -55,6 +56,20 @@ def lib():
         L.orc_corea_scores.argtypes = [_i32p, _i32p, _i64, ctypes.c_int, _f64p]
         L.orc_run_merge.restype = ctypes.c_int32
         L.orc_run_merge.argtypes = [_i64, _i64p, _i32p, ctypes.c_void_p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double)]
+        _vp = ctypes.c_void_p
+        L.orc_clique_census.restype = ctypes.c_int32
+        L.orc_clique_census.argtypes = [_i64, _i64p, _i32p, ctypes.c_int32, ctypes.c_int32, _u64p, _vp,
+                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]
+        L.orc_maximal_cliques.restype = _i64
+        L.orc_maximal_cliques.argtypes = [_i64, _i64p, _i32p, ctypes.c_int32, ctypes.c_int32, _i64p, _i32p, _i32p,
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64)]
+        L.orc_free.restype = None
+        L.orc_free.argtypes = [_vp]
+        L.orc_nucleus_count.restype = _i64
+        L.orc_nucleus_count.argtypes = [_i64, _i64p, _i32p, ctypes.POINTER(_i64)]
+        L.orc_nucleus.restype = ctypes.c_int32
+        L.orc_nucleus.argtypes = [_i64, _i64p, _i32p, _i64, _i64] + [_i32p] * 8
         _LIB = L
     return _LIB
 
@@ -249,3 +264,193 @@ def ref_run_merge(rowptr, col, susp=None):
     nb, dens = int(out[0]), float(out[1])
     rest = np.array(out[2:], dtype=np.int64).reshape(-1, 2)
     return rest[:, 0].astype(np.int32), rest[:, 1].astype(np.int32), nb, dens
+
+
+# ------------------------------------------------ cliques and nuclei (komb_oracle.h: vertex-rooted, sorted arrays, no trussness)
+SAT = 2 ** 64 - 1
+
+
+def _csr(rowptr, col):
+    return np.ascontiguousarray(rowptr, dtype=np.int64), _colbuf(np.ascontiguousarray(col, dtype=np.int32))
+
+
+def t_max(rowptr, col):
+    """The largest trussness (0 without an edge): what sizes the windows of the clique analyses.  From orc_trussness."""
+    t = trussness(*_csr(rowptr, col))
+    return int(t.max()) if len(t) else 0
+
+
+def _k_cap(rowptr):
+    """No clique has more vertices than the largest degree + 1."""
+    return int(np.diff(rowptr).max()) + 2 if len(rowptr) > 1 else 2
+
+
+def clique_counts(rowptr, col, k_local=0):
+    """orc_clique_census as it is: {"total": uint64[k_cap + 1] indexed by k, "local": uint64[nv] or None, "clique_number",
+    "nodes", "seconds"}."""
+    import time
+    rowptr, col = _csr(rowptr, col)
+    nv = len(rowptr) - 1
+    k_cap = _k_cap(rowptr)
+    total = np.zeros(k_cap + 1, dtype=np.uint64)
+    local = np.zeros(max(nv, 1), dtype=np.uint64) if k_local else None
+    sat, nodes = ctypes.c_int32(), ctypes.c_uint64()
+    t0 = time.perf_counter()
+    omega = lib().orc_clique_census(nv, rowptr, col, k_cap, k_local, total, None if local is None else local.ctypes.data,
+                                    ctypes.byref(sat), ctypes.byref(nodes))
+    if omega < 0:
+        raise ValueError("orc_clique_census: bad arguments")
+    return {"total": total, "local": None if local is None else local[:nv], "clique_number": int(omega), "nodes": int(nodes.value),
+            "seconds": time.perf_counter() - t0}
+
+
+def census_window(counts, tmax, k_lo=2, k_hi=-1, k_local=0):
+    """What komb_clique_census_run reports for a window, from clique_counts(k_local) of the same graph and its t_max:
+    {"k_lo", "k_hi" (as used), "k_local", "t_max", "omega", "flags", "total", "local"}.  ValueError where the library answers
+    KOMB_ERR_ARG."""
+    if k_lo < 2 or (k_hi != -1 and k_hi < k_lo) or k_local < 0:
+        raise ValueError("bad window")
+    if k_hi == -1 or k_hi > tmax:
+        k_hi = max(tmax, k_lo)
+    if k_local and not k_lo <= k_local <= k_hi:
+        raise ValueError("k_local outside the window")
+    assert (counts["local"] is not None) == bool(k_local)
+    all_k = counts["total"]
+    assert counts["clique_number"] <= tmax < len(all_k)
+    total = np.zeros(k_hi - k_lo + 1, dtype=np.uint64)
+    n = max(min(k_hi + 1, len(all_k)) - k_lo, 0)
+    total[:n] = all_k[k_lo:k_lo + n]
+    local = counts["local"].copy() if k_local else None
+    sat = bool((total == SAT).any()) or (k_local and bool((local == SAT).any()))
+    nz = np.flatnonzero(total)
+    return {"k_lo": k_lo, "k_hi": k_hi, "k_local": k_local, "t_max": tmax, "omega": int(nz[-1]) + k_lo if len(nz) else 0,
+            "flags": 1 | (2 if sat else 0), "total": total, "local": local}
+
+
+def clique_census(rowptr, col, k_lo=2, k_hi=-1, k_local=0, tmax=None):
+    """One census of a symmetric CSR as komb_clique_census_run defines it (see census_window)."""
+    tmax = t_max(rowptr, col) if tmax is None else tmax
+    kl = k_local if k_local >= 0 else 0
+    return census_window(clique_counts(rowptr, col, kl), tmax, k_lo, k_hi, k_local)
+
+
+def maximal_cliques_all(rowptr, col, k_min=2, want_list=True):
+    """orc_maximal_cliques as it is: {"hist_all": int64[k_cap + 1] indexed by size (every size), "count", "largest": int32[nv],
+    "omega", "n_cliques", "offset": int64[n + 1], "verts": int32 (None, None without the list), "nodes", "seconds"}; count,
+    largest, omega and the list cover the cliques of >= k_min vertices."""
+    import time
+    rowptr, col = _csr(rowptr, col)
+    nv = len(rowptr) - 1
+    k_cap = _k_cap(rowptr)
+    hist = np.zeros(k_cap + 1, dtype=np.int64)
+    count = np.zeros(max(nv, 1), dtype=np.int32)
+    largest = np.zeros(max(nv, 1), dtype=np.int32)
+    omega, nodes, n_verts = ctypes.c_int32(), ctypes.c_uint64(), ctypes.c_int64()
+    p_off, p_verts = ctypes.c_void_p(), ctypes.c_void_p()
+    t0 = time.perf_counter()
+    n = lib().orc_maximal_cliques(nv, rowptr, col, k_min, k_cap, hist, count, largest, ctypes.byref(omega), ctypes.byref(nodes),
+                                  ctypes.byref(p_off) if want_list else None, ctypes.byref(p_verts) if want_list else None,
+                                  ctypes.byref(n_verts))
+    seconds = time.perf_counter() - t0
+    offset = verts = None
+    if want_list:
+        try:
+            if n >= 0:
+                offset = np.ctypeslib.as_array(ctypes.cast(p_off, ctypes.POINTER(ctypes.c_int64)), (n + 1,)).copy()
+                verts = (np.ctypeslib.as_array(ctypes.cast(p_verts, ctypes.POINTER(ctypes.c_int32)), (n_verts.value,)).copy()
+                         if n_verts.value else np.zeros(0, np.int32))
+        finally:
+            lib().orc_free(p_off)
+            lib().orc_free(p_verts)
+    if n < 0:
+        raise ValueError("orc_maximal_cliques: bad arguments")
+    return {"k_min": k_min, "hist_all": hist, "count": count[:nv], "largest": largest[:nv], "omega": int(omega.value), "n_cliques": int(n),
+            "offset": offset, "verts": verts, "nodes": int(nodes.value), "seconds": seconds}
+
+
+def maximal_view(allc, tmax, k_min=2):
+    """What komb_maximal_cliques_run(k_min) reports, in numpy from the k_min = 2 list of maximal_cliques_all and the graph's
+    t_max: {"k_min", "k_hi", "t_max", "omega", "flags" (3), "n_cliques", "hist", "count", "largest", "offset", "verts"}."""
+    if k_min < 2:
+        raise ValueError("bad k_min")
+    assert allc["k_min"] == 2 and allc["offset"] is not None
+    nv = len(allc["count"])
+    k_hi = max(k_min, tmax)
+    size = np.diff(allc["offset"])
+    assert (size <= max(tmax, 2)).all()
+    keep = size >= k_min
+    hist = np.bincount(size[keep] - k_min, minlength=k_hi - k_min + 1).astype(np.int64)
+    member = np.repeat(keep, size)
+    verts = allc["verts"][member]
+    count = np.bincount(verts, minlength=nv).astype(np.int32)
+    largest = np.zeros(nv, np.int32)
+    np.maximum.at(largest, verts, np.repeat(size[keep], size[keep]).astype(np.int32))
+    offset = np.concatenate([[0], np.cumsum(size[keep])]).astype(np.int64)
+    return {"k_min": k_min, "k_hi": k_hi, "t_max": tmax, "omega": int(size[keep].max()) if keep.any() else 0, "flags": 3,
+            "n_cliques": int(keep.sum()), "hist": hist, "count": count, "largest": largest, "offset": offset, "verts": verts}
+
+
+def maximal_cliques(rowptr, col, k_min=2, tmax=None):
+    """The maximal cliques of >= k_min vertices of a symmetric CSR as komb_maximal_cliques_run defines them (see maximal_view)."""
+    tmax = t_max(rowptr, col) if tmax is None else tmax
+    return maximal_view(maximal_cliques_all(rowptr, col, 2), tmax, k_min)
+
+
+def maximum_cliques(view, tmax=None):
+    """What komb_max_clique_run reports with all three flags, in numpy from a maximal_view whose k_min does not exceed the clique
+    number: {"omega", "upper", "flags" (7), "t_max", "n_max_cliques", "count": int32[nv], "list": int32[n, omega]}."""
+    nv = len(view["count"])
+    size = np.diff(view["offset"])
+    omega = int(size.max()) if len(size) else 0
+    rows = np.flatnonzero(size == omega) if omega else np.zeros(0, np.int64)
+    cl = (view["verts"][(view["offset"][rows][:, None] + np.arange(omega)[None, :]).reshape(-1)].reshape(len(rows), omega)
+          if omega else np.zeros((0, 0), np.int32))
+    return {"omega": omega, "upper": omega, "flags": 7, "t_max": view["t_max"] if tmax is None else tmax, "n_max_cliques": len(rows),
+            "count": np.bincount(cl.reshape(-1), minlength=nv).astype(np.int32), "list": cl.astype(np.int32)}
+
+
+def nucleus(rowptr, col):
+    """orc_nucleus: {"a", "b", "c", "key0", "theta": int32[n_triangles], "edge_theta": int32[ne], "vertex_theta": int32[nv],
+    "quads": int32[n_cliques4, 4] (triangle ids), "info": {"n_triangles", "n_cliques4", "theta_max", "n_levels"}, "seconds"}."""
+    import time
+    rowptr, col = _csr(rowptr, col)
+    nv = len(rowptr) - 1
+    ne = int(rowptr[nv]) // 2
+    t0 = time.perf_counter()
+    nq = ctypes.c_int64()
+    nt = lib().orc_nucleus_count(nv, rowptr, col, ctypes.byref(nq))
+    tri = [np.zeros(max(nt, 1), dtype=np.int32) for _ in range(5)]
+    edge_theta = np.zeros(max(ne, 1), dtype=np.int32)
+    vertex_theta = np.zeros(max(nv, 1), dtype=np.int32)
+    quads = np.zeros(max(4 * nq.value, 1), dtype=np.int32)
+    tmax = lib().orc_nucleus(nv, rowptr, col, nt, nq.value, *tri, edge_theta, vertex_theta, quads)
+    if tmax < -1:
+        raise RuntimeError("orc_nucleus: inconsistent counts")
+    out = {name: x[:nt] for name, x in zip(("a", "b", "c", "key0", "theta"), tri)}
+    out.update(edge_theta=edge_theta[:ne], vertex_theta=vertex_theta[:nv], quads=quads[:4 * nq.value].reshape(-1, 4),
+               info={"n_triangles": int(nt), "n_cliques4": int(nq.value), "theta_max": int(tmax),
+                     "n_levels": len(np.unique(out["theta"]))}, seconds=time.perf_counter() - t0)
+    return out
+
+
+def nuclei_labels(theta, quads, k):
+    """(label, size) int32[n_triangles] of the k-nuclei, k >= 1, from the definition: the 4-cliques whose four triangles all have
+    theta >= k link their triangles; a class's label is its smallest triangle id; -1 / 0 where theta < k."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    theta = np.asarray(theta, np.int64)
+    nt = len(theta)
+    label, size = np.full(nt, -1, np.int32), np.zeros(nt, np.int32)
+    mem = np.flatnonzero(theta >= k)
+    if not len(mem):
+        return label, size
+    q = np.asarray(quads, np.int64).reshape(-1, 4)
+    q = q[(theta[q] >= k).all(axis=1)] if len(q) else q
+    u, v = np.repeat(q[:, 0], 3), q[:, 1:].reshape(-1)
+    _, comp = connected_components(coo_matrix((np.ones(len(u), np.int8), (u, v)), shape=(nt, nt)), directed=False)
+    comp = comp[mem]
+    first = np.full(int(comp.max()) + 1, nt, np.int64)
+    np.minimum.at(first, comp, mem)
+    label[mem] = first[comp]
+    size[mem] = np.bincount(comp)[comp]
+    return label, size
