@@ -454,3 +454,96 @@ def nuclei_labels(theta, quads, k):
     label[mem] = first[comp]
     size[mem] = np.bincount(comp)[comp]
     return label, size
+
+
+# ------------------------------------------------ clique percolation (komb_clique_communities_run), from a list of maximal cliques
+def _member_rows(offset, verts, k):
+    """The member cliques (>= k vertices) of a list: (mem: their indices, ms: their sizes, mv: their vertices, flat, start: the
+    first entry of each in mv)."""
+    offset = np.asarray(offset, np.int64)
+    verts = np.asarray(verts, np.int64)
+    size = np.diff(offset)
+    keep = size >= k
+    mem, ms = np.flatnonzero(keep), size[keep]
+    mv = verts[np.repeat(keep, size)]
+    return mem, ms, mv, np.concatenate([[0], np.cumsum(ms)])[:-1]
+
+
+def clique_communities(nv, offset, verts, k):
+    """Every output of komb_clique_communities_run(k) for the list (offset, verts) of maximal cliques -- ascending tuples in
+    lexicographic order --, from the definition by shared subsets: two cliques of >= k vertices are adjacent when a set of k - 1
+    vertices lies in both, so every (k - 1)-subset of every member clique is written out (per clique size, one column choice at
+    a time), equal subsets get one number (np.unique over the rows), and the communities are the connected components of the
+    bipartite clique -- subset graph.  No pivots, no pair of cliques is ever looked at.
+    {"k", "label", "size": int32[n_cliques of the list], "rep", "n_cliques": int32[n], "offset": int64[n + 1], "verts": int32,
+    "n_comm", "first": int32[nv], "n_member_cliques", "n_communities", "largest", "n_covered", "n_overlap"}."""
+    from itertools import combinations
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    if k < 2:
+        raise ValueError("bad k")
+    n_list = len(offset) - 1
+    mem, ms, mv, start = _member_rows(offset, verts, k)
+    nm = len(mem)
+    label, size = np.full(n_list, -1, np.int32), np.zeros(n_list, np.int32)
+    out = {"k": k, "label": label, "size": size, "rep": np.zeros(0, np.int32), "n_cliques": np.zeros(0, np.int32),
+           "offset": np.zeros(1, np.int64), "verts": np.zeros(0, np.int32), "n_comm": np.zeros(nv, np.int32),
+           "first": np.full(nv, -1, np.int32), "n_member_cliques": nm, "n_communities": 0, "largest": 0, "n_covered": 0, "n_overlap": 0}
+    if nm == 0:
+        return out
+    rows, owner = [], []
+    for s in np.unique(ms).tolist():
+        which = np.flatnonzero(ms == s)                                             # positions among the members
+        mat = mv[start[which][:, None] + np.arange(s)[None, :]]
+        for cols in combinations(range(s), k - 1):
+            rows.append(mat[:, cols])
+            owner.append(which)
+    rows, owner = np.concatenate(rows), np.concatenate(owner)
+    _, sub = np.unique(rows, axis=0, return_inverse=True)
+    sub = sub.reshape(-1)
+    n_sub = int(sub.max()) + 1
+    graph = coo_matrix((np.ones(len(owner), np.int8), (owner, nm + sub)), shape=(nm + n_sub, nm + n_sub))
+    _, comp = connected_components(graph, directed=False)
+    comp = comp[:nm]
+    first_of = np.full(int(comp.max()) + 1, n_list, np.int64)
+    np.minimum.at(first_of, comp, mem)                                              # a community's rep: its smallest clique index
+    rep_of = first_of[comp]
+    reps, number, n_cl = np.unique(rep_of, return_inverse=True, return_counts=True)
+    number = number.reshape(-1)
+    label[mem], size[mem] = rep_of, n_cl[number]
+    key = np.unique(np.repeat(number, ms) * max(nv, 1) + mv)                         # the distinct (community, vertex) pairs, in order
+    c_of, v_of = key // max(nv, 1), key % max(nv, 1)
+    per_comm = np.bincount(c_of, minlength=len(reps))
+    n_comm = np.bincount(v_of, minlength=nv)
+    first = np.full(nv, len(reps), np.int64)
+    np.minimum.at(first, v_of, c_of)
+    first[n_comm == 0] = -1
+    out.update(rep=reps.astype(np.int32), n_cliques=n_cl.astype(np.int32), offset=np.concatenate([[0], np.cumsum(per_comm)]).astype(np.int64),
+               verts=v_of.astype(np.int32), n_comm=n_comm.astype(np.int32), first=first.astype(np.int32), n_communities=len(reps),
+               largest=int(per_comm.max()), n_covered=int((n_comm >= 1).sum()), n_overlap=int((n_comm >= 2).sum()))
+    return out
+
+
+def percolation_pair_tests(nv, offset, verts, k):
+    """info["pair_tests"] of komb_clique_communities_run(k): the pivot rule of the contract restated over whole arrays.  load(v) =
+    the member cliques through v; the pivots of a member clique of s vertices are its s - k + 2 vertices of smallest
+    (load(v), v); the result is the sum, over the member cliques i and their pivots v, of the member cliques j > i through v
+    (the entries of v's row above i: the rows ascend by clique index)."""
+    if k < 2:
+        raise ValueError("bad k")
+    mem, ms, mv, start = _member_rows(offset, verts, k)
+    if not len(mem):
+        return 0
+    load = np.bincount(mv, minlength=max(nv, 1))
+    by_row = np.argsort(mv, kind="stable")                                          # row by row, clique indices ascending inside
+    row_start = np.concatenate([[0], np.cumsum(load)])
+    pos = np.empty(len(mv), np.int64)
+    pos[by_row] = np.arange(len(mv)) - row_start[mv[by_row]]
+    above = load[mv] - 1 - pos
+    total = 0
+    for s in np.unique(ms).tolist():
+        idx = start[ms == s][:, None] + np.arange(s)[None, :]
+        v = mv[idx]
+        pivots = np.argsort(load[v] * max(nv, 1) + v, axis=1, kind="stable")[:, :s - k + 2]
+        total += int(np.take_along_axis(above[idx], pivots, axis=1).sum())
+    return total

@@ -145,3 +145,31 @@ def test_thresholds_members_and_invariants():
         assert int(res["blocks"]["n_edges"].sum()) == info["n_member_edges"]
         assert int(res["blocks"]["n_verts"].sum()) == int(nb.sum())
         assert np.array_equal(res["block"][res["blocks"]["rep"]], res["blocks"]["rep"])
+
+
+def test_block_tree_closed_form():
+    """tests/block_tree.py at a reduced size: what the construction fixes against the Hopcroft-Tarjan reference."""
+    import block_tree as BT
+    t = BT.block_tree(**BT.REDUCED)
+    want = BT.closed_form(t)
+    assert len(t["n_edges"]) == 315 and t["nv"] == int(t["n_verts"].sum()) - 314
+    assert len(np.unique(np.sort(t["uv"], axis=1), axis=0)) == len(t["uv"]) and (t["uv"][:, 0] != t["uv"][:, 1]).all()
+    assert (t["n_edges"] >= t["n_verts"]).all() and (t["n_edges"] <= t["n_verts"] + t["n_verts"] // 3).all()
+    eu, ev = _canon(t["nv"], t["uv"])
+    assert len(eu) == len(t["uv"])
+    res = R.biconnected(t["nv"], eu, ev, np.full(len(eu), 2), 2)
+    for name, value in want["info"].items():
+        assert res["info"][name] == value, name
+    assert np.array_equal(np.sort(res["blocks"]["n_edges"]), want["n_edges"]) and np.array_equal(np.sort(res["blocks"]["n_verts"]), want["n_verts"])
+    assert np.array_equal(BT.sorted_pairs(res["blocks"]["n_edges"], res["blocks"]["n_verts"]), want["pairs"])
+    assert np.array_equal(res["n_blocks"], want["n_blocks"])
+    assert np.array_equal(np.flatnonzero(res["n_blocks"] >= 2), want["articulation"])
+    assert (res["size"] > 1).all() and (res["ecc_label"] == 0).all()
+    # every block of the construction is one class of the reference: the edges of block i carry one label
+    canon = {(int(a), int(b)): j for j, (a, b) in enumerate(zip(eu, ev))}
+    at = 0
+    for n in t["n_edges"].tolist():
+        rows = np.sort(t["uv"][at:at + n], axis=1)
+        labels = {int(res["block"][canon[(int(a), int(b))]]) for a, b in rows}
+        assert len(labels) == 1 and int(res["size"][labels.pop()]) == n
+        at += n

@@ -8,8 +8,10 @@ library's own run_truss() edge list (whose parity other tests own).
 
 What these graphs do NOT do: no class of a replica is larger than a tile copy, so none spans two tiles of one workgroup, and the
 `lead == first` branch (the LDS partial sum for the class a workgroup's first tile starts with) is taken in the first tile only;
-in later tiles every class goes the global-atomic way.  A class across tiles is what the giant components of the generated
-graphs give (test_composite and the full-size tests of the neighbouring files)."""
+in later tiles every class goes the global-atomic way.  A class across the tiles of one workgroup is what the giant components
+of the generated graphs give: for biconnected.hip tests/test_gpu_midsize_structure.py (the giant block of a power-law graph of a
+million edges, a grid that is one block, a tree of blocks with three of more than 300 tiles each), for the others
+test_composite and the mid-size tests of tests/test_gpu_midsize.py."""
 import numpy as np
 import pytest
 

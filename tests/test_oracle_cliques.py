@@ -1,6 +1,8 @@
 """CPU tests of the native references of oracle/komb_oracle.c for the clique analyses and the (3,4)-nucleus decomposition --
-orc_clique_census, orc_maximal_cliques, orc_nucleus and the numpy / scipy helpers of oracle/oracle.py on top of them.  The
-mid-size GPU tests (tests/test_gpu_midsize.py) trust them at sizes the Python restatements cannot reach, so here every output is
+orc_clique_census, orc_maximal_cliques, orc_nucleus and the numpy / scipy helpers of oracle/oracle.py on top of them, clique
+percolation by shared subsets (clique_communities, percolation_pair_tests) among them.  The mid-size GPU tests
+(tests/test_gpu_midsize.py, tests/test_gpu_midsize_structure.py) trust them at sizes the Python restatements cannot reach, so
+here every output is
 tied to what the suite already trusts: on the random and hand graph sets of test_clique_census_ref.py,
 test_maximal_cliques_ref.py, test_max_clique_ref.py, test_nucleus_ref.py and test_nucleus_hierarchy_ref.py it equals the Python
 restatement's, and networkx's where those files use it; the degenerate inputs and K_70 (saturation) are included; and one
@@ -12,6 +14,7 @@ import numpy as np
 import pytest
 
 import clique_census_ref as C
+import clique_communities_ref as P
 import max_clique_ref as Q
 import maximal_cliques_ref as M
 import nucleus_hierarchy_ref as H
@@ -374,6 +377,81 @@ def test_nuclei_worked_examples(built):
     got, h = _check_nuclei(*H.two_k5_sharing_an_edge())                            # theta cannot tell these two apart: the classes do
     label, size = O.nuclei_labels(got["theta"], got["quads"], 2)
     assert sorted(set(label.tolist())) == [0, 3] and size.tolist() == [10] * 20
+
+
+# ---- clique percolation: the subset method and the vectorised pivot rule against the all-pairs restatement
+
+PERCOLATION_FIELDS = ("label", "size", "rep", "n_cliques", "offset", "verts", "n_comm", "first")
+PERCOLATION_INFO = ("k", "n_member_cliques", "n_communities", "largest", "n_covered", "n_overlap")
+PERCOLATION_HUG = [(500, 1225, 2.6, 6), (600, 1200, 2.2, 11)]                      # 3 128 and 2 283 maximal cliques
+PERCOLATION_CASCADE = (200, 90, 2, 9, 1)
+
+
+def _check_percolation(nv, edges, networkx=True):
+    """Every k from 2 to omega + 1 on the native list of the graph: every field of O.clique_communities against
+    clique_communities_ref.solve, O.percolation_pair_tests against its pair_tests, the communities against networkx."""
+    rowptr, col, _, _ = _graph(nv, edges)
+    view = O.maximal_cliques(rowptr, col, 2)
+    cliques = _tuples(view)
+    if networkx:
+        import networkx as nx
+        from networkx.algorithms.community import k_clique_communities
+        g = nx.Graph()
+        g.add_nodes_from(range(nv))
+        g.add_edges_from(R.canonical(edges))
+    for k in range(2, view["omega"] + 2):
+        got = O.clique_communities(nv, view["offset"], view["verts"], k)
+        want = P.solve(nv, cliques, k)
+        for name in PERCOLATION_FIELDS:
+            assert got[name].dtype == want[name].dtype and np.array_equal(got[name], want[name]), (name, k)
+        for name in PERCOLATION_INFO:
+            assert got[name] == want[name], (name, k)
+        assert O.percolation_pair_tests(nv, view["offset"], view["verts"], k) == P.pair_tests(cliques, k), k
+        if networkx:
+            sets = sorted(tuple(got["verts"][got["offset"][c]:got["offset"][c + 1]].tolist()) for c in range(got["n_communities"]))
+            assert sets == sorted(tuple(sorted(c)) for c in k_clique_communities(g, k)), k
+    above = O.clique_communities(nv, view["offset"], view["verts"], view["omega"] + 1)
+    assert (above["n_member_cliques"], above["n_communities"], above["largest"], above["n_covered"], above["n_overlap"]) == (0,) * 5
+    assert above["label"].tolist() == [-1] * len(cliques) and above["offset"].tolist() == [0] and above["first"].tolist() == [-1] * nv
+    assert O.percolation_pair_tests(nv, view["offset"], view["verts"], view["omega"] + 1) == 0
+    return view
+
+
+@pytest.mark.parametrize("i", range(2), ids=lambda i: "nv %d" % PERCOLATION_HUG[i][0])
+def test_percolation_power_law_graphs(K, i):
+    nv = PERCOLATION_HUG[i][0]
+    view = _check_percolation(nv, TQ._canonical(K.gen_hug_edges(*PERCOLATION_HUG[i])))
+    assert view["n_cliques"] == (3128, 2283)[i]
+
+
+@pytest.mark.parametrize("name", sorted(P.HAND_GRAPHS))
+def test_percolation_hand_graphs(built, name):
+    nv, edges = P.HAND_GRAPHS[name]
+    view = _check_percolation(nv, edges)
+    for gname, k, n_comm, tests in P.HAND_TABLE:
+        if gname == name:
+            assert O.clique_communities(nv, view["offset"], view["verts"], k)["n_communities"] == n_comm
+            assert O.percolation_pair_tests(nv, view["offset"], view["verts"], k) == tests
+
+
+def test_percolation_cascade_of_random_cliques(built):
+    view = _check_percolation(PERCOLATION_CASCADE[0], R.clique_union(*PERCOLATION_CASCADE))
+    assert O.clique_communities(PERCOLATION_CASCADE[0], view["offset"], view["verts"], 3)["n_overlap"] > 0
+
+
+def test_percolation_empty_list_and_arguments(built):
+    for nv in (0, 5):
+        for k in (2, 3):
+            got = O.clique_communities(nv, np.zeros(1, np.int64), np.zeros(0, np.int32), k)
+            want = P.solve(nv, [], k)
+            for name in PERCOLATION_FIELDS:
+                assert got[name].dtype == want[name].dtype and np.array_equal(got[name], want[name]), name
+            for name in PERCOLATION_INFO:
+                assert got[name] == want[name], name
+            assert O.percolation_pair_tests(nv, np.zeros(1, np.int64), np.zeros(0, np.int32), k) == 0
+    for call in (O.clique_communities, O.percolation_pair_tests):
+        with pytest.raises(ValueError):
+            call(4, np.asarray([0, 2]), np.asarray([0, 1], np.int32), 1)
 
 
 # ---- one recorded run
