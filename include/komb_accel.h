@@ -32,11 +32,11 @@ extern "C" {
 
 typedef enum komb_status {
     KOMB_OK          =  0,
-    KOMB_ERR_ARG     = -1,   /* bad argument / graph not loaded / out-of-range id   */
+    KOMB_ERR_ARG     = -1,   /* bad argument / out-of-range id / an analysis without a graph */
     KOMB_ERR_DEVICE  = -2,   /* no HIP device, or a HIP call failed                 */
     KOMB_ERR_NOMEM   = -3,   /* host or device allocation failed                    */
     KOMB_ERR_LIMIT   = -4,   /* graph exceeds the 32-bit slot/edge-id design limits */
-    KOMB_ERR_STATE   = -5    /* call order violated (e.g. fetch before run)         */
+    KOMB_ERR_STATE   = -5    /* call order violated (fetch before run, k-core / k-truss without a graph) */
 } komb_status;
 
 typedef struct komb_ctx komb_ctx;
@@ -153,9 +153,9 @@ int         komb_alloc_info(komb_ctx *ctx, int64_t *requests, int32_t *fired, in
  * resident in HBM as a symmetric CSR (rows ascending, the caller's ids).  What
  * only the k-truss path needs is made by the first k-truss call (below).
  * Every result is reported in the caller's vertex ids.
- * A load drops the previous graph and every result on the context before it does anything else, so a load that fails -- an
- * argument, a limit, KOMB_ERR_NOMEM -- leaves NO graph: komb_graph_info and every fetch answer KOMB_ERR_STATE until a load
- * succeeds (komb_graph_from_csr alike). */
+ * A load drops the previous graph and every result on the context before it does anything else, so a load that fails -- an argument, a
+ * limit, KOMB_ERR_NOMEM -- leaves NO graph (komb_graph_from_csr alike).  Until a load succeeds, komb_graph_info / _get_csr / _moments,
+ * komb_densest_block, komb_core_run / _fetch and the komb_truss_* calls answer KOMB_ERR_STATE (komb_truss_unprepare: KOMB_OK), every analysis KOMB_ERR_ARG. */
 int komb_graph_from_edges(komb_ctx *ctx, int64_t nv, int64_t n_raw,
                           const int64_t *uv_pairs);
 

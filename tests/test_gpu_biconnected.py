@@ -30,7 +30,12 @@ def _resolve(k, tr):
 
 
 def _fetch_all(a, k):
-    block, size = a.run_biconnected(k)
+    a.biconnected_run(k)
+    return _fetch_held(a)
+
+
+def _fetch_held(a):
+    block, size = a.biconnected_fetch_edges()
     n_blocks, ecc_label, ecc_size = a.biconnected_fetch_vertices()
     return {"block": block, "size": size, "n_blocks": n_blocks, "ecc_label": ecc_label, "ecc_size": ecc_size,
             "blocks": a.biconnected_fetch_blocks(), "info": a.biconnected_info(), "count": a.biconnected_count()}
@@ -51,9 +56,17 @@ def _invariants(a, k, got):
 
 def _expect(a, k, eu, ev, tr, invariants=True):
     """Run threshold k on a's last k-truss result (eu, ev, tr) and compare everything with the reference."""
-    got = _fetch_all(a, k)
+    got = _compare(a, k, eu, ev, tr, _fetch_all(a, k))
+    if invariants:
+        _invariants(a, k, got)
+    return got
+
+
+def _compare(a, k, eu, ev, tr, got=None, want=None):
+    """The held blocks of threshold k of the k-truss result (eu, ev, tr): everything against the reference."""
+    got = _fetch_held(a) if got is None else got
     kk = _resolve(k, tr)
-    want = R.biconnected(a.nv, eu, ev, tr, kk)
+    want = R.biconnected(a.nv, eu, ev, tr, kk) if want is None else want
     for name in ("block", "size", "n_blocks", "ecc_label", "ecc_size"):
         assert got[name].dtype == np.int32 and len(got[name]) == len(want[name]), (name, k)
         assert np.array_equal(got[name], want[name]), (name, k)
@@ -62,8 +75,6 @@ def _expect(a, k, eu, ev, tr, invariants=True):
         assert np.array_equal(got["blocks"][name], want["blocks"][name]), (name, k)
     assert tuple(got["info"][x] for x in INFO) == (kk,) + R.summary(want), k
     assert got["info"]["ms"] >= 0.0
-    if invariants:
-        _invariants(a, k, got)
     return got
 
 

@@ -32,7 +32,13 @@ def _clique(ids):
 
 def _expect(a, want):
     """Run the community hierarchy on a's k-truss result and compare nodes, node[] and info with the reference forest."""
-    nodes, node = a.run_community_hierarchy()
+    a.community_hierarchy_run()
+    return _compare(a, want)
+
+
+def _compare(a, want):
+    """The held community hierarchy: nodes, node[] and info against the reference forest."""
+    nodes, node = a.community_hierarchy_fetch_nodes(), a.community_hierarchy_fetch_edges()
     info = a.community_hierarchy_info()
     for f in CH.FIELDS:
         assert nodes[f].dtype == np.int32 and len(nodes[f]) == len(want[f]), f

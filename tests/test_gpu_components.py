@@ -25,7 +25,13 @@ def _i64(x):
 
 def _expect(a, kind, k, want, k_used=None):
     """Run (kind, k) on a and compare label, size and info with the reference labels `want`."""
-    label, size = a.run_components(kind, k)
+    a.components_run(kind, k)
+    return _compare(a, kind, k, want, k_used)
+
+
+def _compare(a, kind, k, want, k_used=None):
+    """The held result of a run (kind, k): label, size and info against the reference labels `want`."""
+    label, size = a.components_fetch()
     info = a.components_info()
     tag = (kind, k)
     assert label.dtype == np.int32 and size.dtype == np.int32

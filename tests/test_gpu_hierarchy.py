@@ -24,7 +24,13 @@ def _i64(x):
 
 def _expect(a, kind, want):
     """Run the hierarchy of `kind` on a and compare the node arrays, node[] and info with the reference forest."""
-    nodes, node = a.run_hierarchy(kind)
+    a.hierarchy_run(kind)
+    return _compare(a, kind, want)
+
+
+def _compare(a, kind, want):
+    """The held hierarchy of `kind`: the node arrays, node[] and info against the reference forest."""
+    nodes, node = a.hierarchy_fetch_nodes(), a.hierarchy_fetch_vertices()
     info = a.hierarchy_info()
     for f in H.FIELDS:
         assert nodes[f].dtype == np.int32 and len(nodes[f]) == len(want[f]), (kind, f)

@@ -24,10 +24,16 @@ def _i64(x):
 
 def _expect(a, eu, ev, sup, params):
     """Run params on a's last k-truss result (eu, ev, sup) and compare everything with the restatement."""
-    label, size, role, sim_deg = a.run_structural_clusters(*params)
+    a.structural_clusters_run(*params)
+    return _compare(a, eu, ev, sup, params)
+
+
+def _compare(a, eu, ev, sup, params, want=None):
+    """The held clustering of params of the k-truss result (eu, ev, sup): everything against the restatement."""
+    label, size, role, sim_deg = a.structural_clusters_fetch()
     similar = a.structural_clusters_fetch_edges()
     info = a.structural_clusters_info()
-    want = R.clusters(a.nv, eu, ev, sup, *params)
+    want = R.clusters(a.nv, eu, ev, sup, *params) if want is None else want
     for x in (label, size, role, sim_deg, similar):
         assert x.dtype == np.int32
     assert len(similar) == len(eu) and all(len(x) == a.nv for x in (label, size, role, sim_deg))
