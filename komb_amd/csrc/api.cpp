@@ -28,7 +28,75 @@ int require_device(komb_ctx *ctx)
     return KOMB_OK;
 }
 
+// what every analysis of a k-truss result asks first: a completed run that materialised all of its canonical edges
+int require_full_truss(komb_ctx *ctx, const char *who)
+{
+    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "%s: no completed k-truss result on this graph", who);
+    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
+        KOMB_FAIL(ctx, KOMB_ERR_STATE, "%s: the last k-truss run materialised only the canonical edges [%u, %u) of %lld", who,
+                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    return KOMB_OK;
+}
+
+// the largest trussness of the result, 2 when it has no edge
+int32_t truss_k_max(const komb_ctx *ctx) { return ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2; }
+// a k-truss threshold as the caller gave it (checked: >= K_MAX): K_MAX (KOMB_COMM_K_MAX, KOMB_BICONN_K_MAX: one value) is the
+// largest trussness, anything below 2 runs as 2
+int32_t resolve_truss_k(const komb_ctx *ctx, int32_t k)
+{
+    if (k == KOMB_COMM_K_MAX) k = truss_k_max(ctx);
+    return k < 2 ? 2 : k;
+}
+
+// count elements of a device array into host memory; a null dst or no element is nothing to do
+template <class T> int fetch(komb_ctx *ctx, T *dst, const void *src, size_t count)
+{
+    if (dst && count) KOMB_HIP(ctx, staged_copy(ctx, dst, src, count * sizeof(T), false));
+    return KOMB_OK;
+}
+
 } // namespace
+
+static_assert(KOMB_COMM_K_MAX == KOMB_BICONN_K_MAX, "resolve_truss_k serves both");
+
+// The two openings of an entry point.  Most ask for the device first and then for the graph; the hierarchy-style ones ask for
+// the graph first: a context without one says so whether or not it has a device.  The _DONE variants then ask for the result
+// the entry reads: `done` is its record's flag, `missing` what the message says when it is not there (one text per result).
+#define KOMB_DEV_ENTER(ctx, what)                                                          \
+    do {                                                                                   \
+        KOMB_TRY(require_device(ctx));                                                     \
+        if ((ctx)->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, what ": no graph loaded");         \
+    } while (0)
+#define KOMB_HIER_ENTER(ctx, what)                                                         \
+    do {                                                                                   \
+        if (!(ctx)) return KOMB_ERR_ARG;                                                   \
+        if ((ctx)->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, what ": no graph loaded");         \
+        KOMB_TRY(require_device(ctx));                                                     \
+    } while (0)
+#define KOMB_DEV_ENTER_DONE(ctx, what, done, missing)                                      \
+    do {                                                                                   \
+        KOMB_DEV_ENTER(ctx, what);                                                         \
+        if (!(done)) KOMB_FAIL(ctx, KOMB_ERR_STATE, what ": " missing);                    \
+    } while (0)
+#define KOMB_HIER_ENTER_DONE(ctx, what, done, missing)                                     \
+    do {                                                                                   \
+        KOMB_HIER_ENTER(ctx, what);                                                        \
+        if (!(done)) KOMB_FAIL(ctx, KOMB_ERR_STATE, what ": " missing);                    \
+    } while (0)
+#define NO_ONION "komb_onion_run has not completed on this graph"
+#define NO_COMP "komb_components_run has not completed on this graph"
+#define NO_HIER "komb_hierarchy_run has not completed on this graph"
+#define NO_COMM "no communities of the current k-truss result"
+#define NO_BC "no blocks of the current k-truss result"
+#define NO_DENS "komb_densest_subgraph_run has not completed on this graph"
+#define NO_SC "no structural clustering of the current k-truss result"
+#define NO_NUC "no nucleus decomposition of the current k-truss result"
+#define NO_MC "no maximum-clique search of the current k-truss result"
+#define NO_CC "no clique census of the current k-truss result"
+#define NO_MX "no maximal cliques of the current k-truss result"
+#define NO_PC "no k-clique communities of the current maximal cliques"
+#define NO_NH "no nucleus hierarchy of the current nucleus decomposition"
+#define NO_CH "no community hierarchy of the current k-truss result"
 
 extern "C" {
 
@@ -155,10 +223,9 @@ int komb_set_shard_peel(komb_ctx *ctx, int32_t on)
 int komb_core_fetch(komb_ctx *ctx, int32_t *degree, int32_t *coreness)
 {
     KOMB_TRY(require_device(ctx));
-    if (!ctx->core_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_core_fetch: komb_core_run has not completed");
-    if (ctx->nv == 0) return KOMB_OK;
-    if (degree) KOMB_HIP(ctx, staged_copy(ctx, degree, ctx->d_deg, (size_t)ctx->nv * sizeof(int32_t), false));
-    if (coreness) KOMB_HIP(ctx, staged_copy(ctx, coreness, ctx->d_core, (size_t)ctx->nv * sizeof(int32_t), false));
+    if (!ctx->core.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_core_fetch: komb_core_run has not completed");
+    KOMB_TRY(fetch(ctx, degree, ctx->core.deg, (size_t)ctx->nv));
+    KOMB_TRY(fetch(ctx, coreness, ctx->core.core, (size_t)ctx->nv));
     return KOMB_OK;
 }
 
@@ -170,192 +237,147 @@ int komb_degree_coreness(komb_ctx *ctx, int32_t *degree, int32_t *coreness)
 
 int komb_onion_run(komb_ctx *ctx)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_onion_run: no graph loaded");
+    KOMB_DEV_ENTER(ctx, "komb_onion_run");
     return onion_run(ctx);
 }
 
 int komb_onion_fetch(komb_ctx *ctx, int32_t *layer, int32_t *coreness)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_onion_fetch: no graph loaded");
-    if (!ctx->onion_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_onion_fetch: komb_onion_run has not completed on this graph");
-    if (ctx->nv == 0) return KOMB_OK;
-    if (layer) KOMB_HIP(ctx, staged_copy(ctx, layer, ctx->d_onion_layer, (size_t)ctx->nv * sizeof(int32_t), false));
-    if (coreness) KOMB_HIP(ctx, staged_copy(ctx, coreness, ctx->d_onion_core, (size_t)ctx->nv * sizeof(int32_t), false));
+    KOMB_DEV_ENTER_DONE(ctx, "komb_onion_fetch", ctx->onion.done, NO_ONION);
+    KOMB_TRY(fetch(ctx, layer, ctx->onion.layer, (size_t)ctx->nv));
+    KOMB_TRY(fetch(ctx, coreness, ctx->onion.core, (size_t)ctx->nv));
     return KOMB_OK;
 }
 
 int komb_onion_info(komb_ctx *ctx, int64_t *n_layers, int32_t *max_coreness, double *ms)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_onion_info: no graph loaded");
-    if (!ctx->onion_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_onion_info: komb_onion_run has not completed on this graph");
-    if (n_layers) *n_layers = ctx->onion_layers;
-    if (max_coreness) *max_coreness = ctx->onion_max_core;
-    if (ms) *ms = ctx->onion_ms;
+    KOMB_DEV_ENTER_DONE(ctx, "komb_onion_info", ctx->onion.done, NO_ONION);
+    if (n_layers) *n_layers = ctx->onion.n_layers;
+    if (max_coreness) *max_coreness = ctx->onion.max_core;
+    if (ms) *ms = ctx->onion.ms;
     return KOMB_OK;
 }
 
 int komb_components_run(komb_ctx *ctx, int32_t kind, int32_t k)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_run: no graph loaded");
+    KOMB_DEV_ENTER(ctx, "komb_components_run");
     if (kind != KOMB_COMP_CORE && kind != KOMB_COMP_TRUSS) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_run: unknown kind %d", kind);
     if (k < KOMB_COMP_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_run: bad threshold %d", k);
     if (kind == KOMB_COMP_CORE) {
-        if (k != 0 && !ctx->core_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_run: komb_core_run has not completed on this graph");
+        if (k != 0 && !ctx->core.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_run: komb_core_run has not completed on this graph");
         if (k == KOMB_COMP_K_MAX) k = ctx->nv > 0 ? ctx->stats.max_coreness : 0;
     } else {
-        if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_run: no completed k-truss result on this graph");
-        if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-            KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                      ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
-        if (k == KOMB_COMP_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
+        KOMB_TRY(require_full_truss(ctx, "komb_components_run"));
+        if (k == KOMB_COMP_K_MAX) k = truss_k_max(ctx);      // (no clamp here: a threshold below 2 runs as given)
     }
     return components_run(ctx, kind, k);
 }
 
 int komb_components_fetch(komb_ctx *ctx, int32_t *label, int32_t *size)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_fetch: no graph loaded");
-    if (!ctx->comp_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_fetch: komb_components_run has not completed on this graph");
-    if (ctx->nv == 0) return KOMB_OK;
-    if (label) KOMB_HIP(ctx, staged_copy(ctx, label, ctx->d_comp_label, (size_t)ctx->nv * sizeof(int32_t), false));
-    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_comp_size, (size_t)ctx->nv * sizeof(int32_t), false));
+    KOMB_DEV_ENTER_DONE(ctx, "komb_components_fetch", ctx->comp.done, NO_COMP);
+    KOMB_TRY(fetch(ctx, label, ctx->comp.label, (size_t)ctx->nv));
+    KOMB_TRY(fetch(ctx, size, ctx->comp.size, (size_t)ctx->nv));
     return KOMB_OK;
 }
 
 int komb_components_info(komb_ctx *ctx, int32_t *kind, int32_t *k_used, int64_t *n_members, int64_t *n_components, int64_t *largest, double *ms)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_components_info: no graph loaded");
-    if (!ctx->comp_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_components_info: komb_components_run has not completed on this graph");
-    if (kind) *kind = ctx->comp_kind;
-    if (k_used) *k_used = ctx->comp_k;
-    if (n_members) *n_members = ctx->comp_members;
-    if (n_components) *n_components = ctx->comp_count;
-    if (largest) *largest = ctx->comp_largest;
-    if (ms) *ms = ctx->comp_ms;
+    KOMB_DEV_ENTER_DONE(ctx, "komb_components_info", ctx->comp.done, NO_COMP);
+    if (kind) *kind = ctx->comp.kind;
+    if (k_used) *k_used = ctx->comp.k;
+    if (n_members) *n_members = ctx->comp.members;
+    if (n_components) *n_components = ctx->comp.count;
+    if (largest) *largest = ctx->comp.largest;
+    if (ms) *ms = ctx->comp.ms;
     return KOMB_OK;
 }
-
-// the hierarchy entry points ask for the graph first: a context without one says so whether or not it has a device
-#define KOMB_HIER_ENTER(ctx, what)                                                         \
-    do {                                                                                   \
-        if (!(ctx)) return KOMB_ERR_ARG;                                                   \
-        if ((ctx)->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, what ": no graph loaded");         \
-        KOMB_TRY(require_device(ctx));                                                     \
-    } while (0)
 
 int komb_hierarchy_run(komb_ctx *ctx, int32_t kind)
 {
     KOMB_HIER_ENTER(ctx, "komb_hierarchy_run");
     if (kind != KOMB_COMP_CORE && kind != KOMB_COMP_TRUSS) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_hierarchy_run: unknown kind %d", kind);
     if (kind == KOMB_COMP_CORE) {
-        if (!ctx->core_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_run: komb_core_run has not completed on this graph");
+        if (!ctx->core.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_run: komb_core_run has not completed on this graph");
     } else {
-        if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_run: no completed k-truss result on this graph");
-        if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-            KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                      ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+        KOMB_TRY(require_full_truss(ctx, "komb_hierarchy_run"));
     }
     return hierarchy_run(ctx, kind);
 }
 
 int komb_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes)
 {
-    KOMB_HIER_ENTER(ctx, "komb_hierarchy_count");
-    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_count: komb_hierarchy_run has not completed on this graph");
-    if (n_nodes) *n_nodes = ctx->hier_nodes;
+    KOMB_HIER_ENTER_DONE(ctx, "komb_hierarchy_count", ctx->hier.done, NO_HIER);
+    if (n_nodes) *n_nodes = ctx->hier.n_nodes;
     return KOMB_OK;
 }
 
 int komb_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent, int32_t *size, int32_t *shell)
 {
-    KOMB_HIER_ENTER(ctx, "komb_hierarchy_fetch_nodes");
-    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_fetch_nodes: komb_hierarchy_run has not completed on this graph");
-    if (ctx->hier_nodes == 0) return KOMB_OK;
-    const size_t stride = (size_t)(ctx->nv > 0 ? ctx->nv : 1), bytes = (size_t)ctx->hier_nodes * sizeof(int32_t);
+    KOMB_HIER_ENTER_DONE(ctx, "komb_hierarchy_fetch_nodes", ctx->hier.done, NO_HIER);
+    const size_t stride = (size_t)(ctx->nv > 0 ? ctx->nv : 1);
     int32_t *const out[5] = {k, rep, parent, size, shell};
-    for (int i = 0; i < 5; ++i)
-        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_hier_nodes + i * stride, bytes, false));
+    for (int i = 0; i < 5; ++i) KOMB_TRY(fetch(ctx, out[i], ctx->hier.nodes + i * stride, (size_t)ctx->hier.n_nodes));
     return KOMB_OK;
 }
 
 int komb_hierarchy_fetch_vertices(komb_ctx *ctx, int32_t *node)
 {
-    KOMB_HIER_ENTER(ctx, "komb_hierarchy_fetch_vertices");
-    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_fetch_vertices: komb_hierarchy_run has not completed on this graph");
-    if (ctx->nv > 0 && node) KOMB_HIP(ctx, staged_copy(ctx, node, ctx->d_hier_vnode, (size_t)ctx->nv * sizeof(int32_t), false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_hierarchy_fetch_vertices", ctx->hier.done, NO_HIER);
+    KOMB_TRY(fetch(ctx, node, ctx->hier.vnode, (size_t)ctx->nv));
     return KOMB_OK;
 }
 
 int komb_hierarchy_info(komb_ctx *ctx, int32_t *kind, int64_t *n_nodes, int64_t *n_roots, int32_t *k_max, int32_t *depth, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_hierarchy_info");
-    if (!ctx->hier_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_hierarchy_info: komb_hierarchy_run has not completed on this graph");
-    if (kind) *kind = ctx->hier_kind;
-    if (n_nodes) *n_nodes = ctx->hier_nodes;
-    if (n_roots) *n_roots = ctx->hier_roots;
-    if (k_max) *k_max = ctx->hier_kmax;
-    if (depth) *depth = ctx->hier_depth;
-    if (ms) *ms = ctx->hier_ms;
+    KOMB_HIER_ENTER_DONE(ctx, "komb_hierarchy_info", ctx->hier.done, NO_HIER);
+    if (kind) *kind = ctx->hier.kind;
+    if (n_nodes) *n_nodes = ctx->hier.n_nodes;
+    if (n_roots) *n_roots = ctx->hier.n_roots;
+    if (k_max) *k_max = ctx->hier.kmax;
+    if (depth) *depth = ctx->hier.depth;
+    if (ms) *ms = ctx->hier.ms;
     return KOMB_OK;
 }
 
 int komb_truss_communities_run(komb_ctx *ctx, int32_t k)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_run: no graph loaded");
+    KOMB_DEV_ENTER(ctx, "komb_truss_communities_run");
     if (k < KOMB_COMM_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_run: bad threshold %d", k);
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
-    if (k == KOMB_COMM_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
-    if (k < 2) k = 2;
-    return communities_run(ctx, k);
+    KOMB_TRY(require_full_truss(ctx, "komb_truss_communities_run"));
+    return communities_run(ctx, resolve_truss_k(ctx, k));
 }
 
 int komb_truss_communities_fetch(komb_ctx *ctx, int32_t *label, int32_t *size)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_fetch: no graph loaded");
-    if (!ctx->comm_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_fetch: no communities of the current k-truss result");
-    const size_t bytes = (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0) * sizeof(int32_t);
-    if (bytes == 0) return KOMB_OK;
-    if (label) KOMB_HIP(ctx, staged_copy(ctx, label, ctx->d_comm_label, bytes, false));
-    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_comm_size, bytes, false));
+    KOMB_DEV_ENTER_DONE(ctx, "komb_truss_communities_fetch", ctx->comm.done, NO_COMM);
+    const size_t m = (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0);
+    KOMB_TRY(fetch(ctx, label, ctx->comm.label, m));
+    KOMB_TRY(fetch(ctx, size, ctx->comm.size, m));
     return KOMB_OK;
 }
 
 int komb_truss_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_fetch_vertices: no graph loaded");
-    if (!ctx->comm_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_fetch_vertices: no communities of the current k-truss result");
+    KOMB_DEV_ENTER_DONE(ctx, "komb_truss_communities_fetch_vertices", ctx->comm.done, NO_COMM);
     KOMB_TRY(communities_vertices(ctx));
-    if (ctx->nv > 0 && n_comm) KOMB_HIP(ctx, staged_copy(ctx, n_comm, ctx->d_comm_ncomm, (size_t)ctx->nv * sizeof(int32_t), false));
+    KOMB_TRY(fetch(ctx, n_comm, ctx->comm.ncomm, (size_t)ctx->nv));
     return KOMB_OK;
 }
 
 int komb_truss_communities_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edges, int64_t *n_communities,
                                 int64_t *largest, int64_t *n_multi_vertices, double *ms)
 {
-    KOMB_TRY(require_device(ctx));
-    if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_truss_communities_info: no graph loaded");
-    if (!ctx->comm_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_communities_info: no communities of the current k-truss result");
+    KOMB_DEV_ENTER_DONE(ctx, "komb_truss_communities_info", ctx->comm.done, NO_COMM);
     if (n_multi_vertices) {                              // (the vertex pass runs when somebody asks for what it makes)
         KOMB_TRY(communities_vertices(ctx));
-        *n_multi_vertices = ctx->comm_multi;
+        *n_multi_vertices = ctx->comm.multi;
     }
-    if (k_used) *k_used = ctx->comm_k;
-    if (n_member_edges) *n_member_edges = ctx->comm_members;
-    if (n_communities) *n_communities = ctx->comm_count;
-    if (largest) *largest = ctx->comm_largest;
-    if (ms) *ms = ctx->comm_ms;
+    if (k_used) *k_used = ctx->comm.k;
+    if (n_member_edges) *n_member_edges = ctx->comm.members;
+    if (n_communities) *n_communities = ctx->comm.count;
+    if (largest) *largest = ctx->comm.largest;
+    if (ms) *ms = ctx->comm.ms;
     return KOMB_OK;
 }
 
@@ -363,55 +385,42 @@ int komb_biconnected_run(komb_ctx *ctx, int32_t k)
 {
     KOMB_HIER_ENTER(ctx, "komb_biconnected_run");
     if (k < KOMB_BICONN_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_biconnected_run: bad threshold %d", k);
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
-    if (k == KOMB_BICONN_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
-    if (k < 2) k = 2;
-    return biconnected_run(ctx, k);
+    KOMB_TRY(require_full_truss(ctx, "komb_biconnected_run"));
+    return biconnected_run(ctx, resolve_truss_k(ctx, k));
 }
 
 int komb_biconnected_count(komb_ctx *ctx, int64_t *n_blocks)
 {
-    KOMB_HIER_ENTER(ctx, "komb_biconnected_count");
-    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_count: no blocks of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_biconnected_count", ctx->bc.done, NO_BC);
     if (n_blocks) *n_blocks = ctx->bc.n_blocks;
     return KOMB_OK;
 }
 
 int komb_biconnected_fetch_edges(komb_ctx *ctx, int32_t *block, int32_t *size)
 {
-    KOMB_HIER_ENTER(ctx, "komb_biconnected_fetch_edges");
-    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_fetch_edges: no blocks of the current k-truss result");
-    const size_t bytes = (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0) * sizeof(int32_t);
-    if (bytes == 0) return KOMB_OK;
-    if (block) KOMB_HIP(ctx, staged_copy(ctx, block, ctx->d_bc_block, bytes, false));
-    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_bc_size, bytes, false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_biconnected_fetch_edges", ctx->bc.done, NO_BC);
+    const size_t m = (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0);
+    KOMB_TRY(fetch(ctx, block, ctx->bc.block, m));
+    KOMB_TRY(fetch(ctx, size, ctx->bc.size, m));
     return KOMB_OK;
 }
 
 int komb_biconnected_fetch_vertices(komb_ctx *ctx, int32_t *n_blocks, int32_t *ecc_label, int32_t *ecc_size)
 {
-    KOMB_HIER_ENTER(ctx, "komb_biconnected_fetch_vertices");
-    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_fetch_vertices: no blocks of the current k-truss result");
-    if (ctx->nv == 0) return KOMB_OK;
-    const size_t bytes = (size_t)ctx->nv * sizeof(int32_t);
-    if (n_blocks) KOMB_HIP(ctx, staged_copy(ctx, n_blocks, ctx->d_bc_nblocks, bytes, false));
-    if (ecc_label) KOMB_HIP(ctx, staged_copy(ctx, ecc_label, ctx->d_bc_ecc_label, bytes, false));
-    if (ecc_size) KOMB_HIP(ctx, staged_copy(ctx, ecc_size, ctx->d_bc_ecc_size, bytes, false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_biconnected_fetch_vertices", ctx->bc.done, NO_BC);
+    const size_t nv = (size_t)ctx->nv;
+    KOMB_TRY(fetch(ctx, n_blocks, ctx->bc.nblocks, nv));
+    KOMB_TRY(fetch(ctx, ecc_label, ctx->bc.ecc_label, nv));
+    KOMB_TRY(fetch(ctx, ecc_size, ctx->bc.ecc_size, nv));
     return KOMB_OK;
 }
 
 int komb_biconnected_fetch_blocks(komb_ctx *ctx, int32_t *rep, int32_t *n_edges, int32_t *n_verts)
 {
-    KOMB_HIER_ENTER(ctx, "komb_biconnected_fetch_blocks");
-    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_fetch_blocks: no blocks of the current k-truss result");
-    if (ctx->bc.n_blocks == 0) return KOMB_OK;
-    const size_t n = (size_t)ctx->bc.n_blocks, bytes = n * sizeof(int32_t);
+    KOMB_HIER_ENTER_DONE(ctx, "komb_biconnected_fetch_blocks", ctx->bc.done, NO_BC);
+    const size_t n = (size_t)ctx->bc.n_blocks;
     int32_t *const out[3] = {rep, n_edges, n_verts};
-    for (int i = 0; i < 3; ++i)
-        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_bc_list + i * n, bytes, false));
+    for (int i = 0; i < 3; ++i) KOMB_TRY(fetch(ctx, out[i], ctx->bc.list + i * n, n));
     return KOMB_OK;
 }
 
@@ -419,8 +428,7 @@ int komb_biconnected_info(komb_ctx *ctx, int32_t *k_used, int64_t *n_member_edge
                           int64_t *n_bridges, int64_t *n_articulation, int64_t *largest_block, int64_t *n_ecc, int64_t *largest_ecc,
                           int32_t *depth, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_biconnected_info");
-    if (!ctx->bc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_biconnected_info: no blocks of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_biconnected_info", ctx->bc.done, NO_BC);
     const komb_ctx::Biconnected &r = ctx->bc;
     if (k_used) *k_used = r.k;
     if (n_member_edges) *n_member_edges = r.n_member_edges;
@@ -440,35 +448,31 @@ int komb_densest_subgraph_run(komb_ctx *ctx, int32_t iters)
 {
     KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_run");
     if (iters < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_densest_subgraph_run: bad number of rounds %d", iters);
-    if (!ctx->core_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_run: komb_core_run has not completed on this graph");
+    if (!ctx->core.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_run: komb_core_run has not completed on this graph");
     return densest_run(ctx, iters);
 }
 
 int komb_densest_subgraph_fetch(komb_ctx *ctx, int32_t *member, int32_t *load)
 {
-    KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_fetch");
-    if (!ctx->dens_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_fetch: komb_densest_subgraph_run has not completed on this graph");
-    if (ctx->nv == 0) return KOMB_OK;
-    if (member) KOMB_HIP(ctx, staged_copy(ctx, member, ctx->d_dens_member, (size_t)ctx->nv * sizeof(int32_t), false));
-    if (load) KOMB_HIP(ctx, staged_copy(ctx, load, ctx->d_dens_load, (size_t)ctx->nv * sizeof(int32_t), false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_densest_subgraph_fetch", ctx->dens.done, NO_DENS);
+    KOMB_TRY(fetch(ctx, member, ctx->dens.member, (size_t)ctx->nv));
+    KOMB_TRY(fetch(ctx, load, ctx->dens.load, (size_t)ctx->nv));
     return KOMB_OK;
 }
 
 int komb_densest_subgraph_profile(komb_ctx *ctx, int64_t *n_k, int64_t *m_k)
 {
-    KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_profile");
-    if (!ctx->dens_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_profile: komb_densest_subgraph_run has not completed on this graph");
-    const size_t K = ctx->dens_profile.size() / 2;
-    if (n_k) memcpy(n_k, ctx->dens_profile.data(), K * sizeof(int64_t));
-    if (m_k) memcpy(m_k, ctx->dens_profile.data() + K, K * sizeof(int64_t));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_densest_subgraph_profile", ctx->dens.done, NO_DENS);
+    const size_t K = ctx->dens.profile.size() / 2;
+    if (n_k) memcpy(n_k, ctx->dens.profile.data(), K * sizeof(int64_t));
+    if (m_k) memcpy(m_k, ctx->dens.profile.data() + K, K * sizeof(int64_t));
     return KOMB_OK;
 }
 
 int komb_densest_subgraph_info(komb_ctx *ctx, int32_t *source, int32_t *k_best, int32_t *k_prune, int64_t *n_pruned, int64_t *m_pruned,
                                int64_t *n_sub, int64_t *m_sub, int64_t *load_max, int32_t *iters, int32_t *k_max, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_densest_subgraph_info");
-    if (!ctx->dens_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_densest_subgraph_info: komb_densest_subgraph_run has not completed on this graph");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_densest_subgraph_info", ctx->dens.done, NO_DENS);
     const komb_ctx::Densest &r = ctx->dens;
     if (source) *source = r.source;
     if (k_best) *k_best = r.k_best;
@@ -490,30 +494,24 @@ int komb_structural_clusters_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den
     if (eps_num < 1 || eps_num > eps_den || eps_den > 1000000)
         KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_structural_clusters_run: bad epsilon %d / %d (1 <= eps_num <= eps_den <= 1000000)", eps_num, eps_den);
     if (mu < 2) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_structural_clusters_run: bad mu %d (at least 2)", mu);
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    KOMB_TRY(require_full_truss(ctx, "komb_structural_clusters_run"));
     return structural_run(ctx, eps_num, eps_den, mu);
 }
 
 int komb_structural_clusters_fetch(komb_ctx *ctx, int32_t *label, int32_t *size, int32_t *role, int32_t *sim_deg)
 {
-    KOMB_HIER_ENTER(ctx, "komb_structural_clusters_fetch");
-    if (!ctx->sc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_fetch: no structural clustering of the current k-truss result");
-    if (ctx->nv == 0) return KOMB_OK;
-    const size_t bytes = (size_t)ctx->nv * sizeof(int32_t);
-    if (label) KOMB_HIP(ctx, staged_copy(ctx, label, ctx->d_sc_label, bytes, false));
-    if (size) KOMB_HIP(ctx, staged_copy(ctx, size, ctx->d_sc_size, bytes, false));
-    if (role) KOMB_HIP(ctx, staged_copy(ctx, role, ctx->d_sc_role, bytes, false));
-    if (sim_deg) KOMB_HIP(ctx, staged_copy(ctx, sim_deg, ctx->d_sc_simdeg, bytes, false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_structural_clusters_fetch", ctx->sc.done, NO_SC);
+    const size_t nv = (size_t)ctx->nv;
+    KOMB_TRY(fetch(ctx, label, ctx->sc.label, nv));
+    KOMB_TRY(fetch(ctx, size, ctx->sc.size, nv));
+    KOMB_TRY(fetch(ctx, role, ctx->sc.role, nv));
+    KOMB_TRY(fetch(ctx, sim_deg, ctx->sc.simdeg, nv));
     return KOMB_OK;
 }
 
 int komb_structural_clusters_fetch_edges(komb_ctx *ctx, int32_t *similar)
 {
-    KOMB_HIER_ENTER(ctx, "komb_structural_clusters_fetch_edges");
-    if (!ctx->sc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_fetch_edges: no structural clustering of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_structural_clusters_fetch_edges", ctx->sc.done, NO_SC);
     return structural_fetch_edges(ctx, similar);
 }
 
@@ -521,8 +519,7 @@ int komb_structural_clusters_info(komb_ctx *ctx, int32_t *eps_num, int32_t *eps_
                                   int64_t *n_cores, int64_t *n_borders, int64_t *n_hubs, int64_t *n_outliers, int64_t *n_clusters,
                                   int64_t *largest, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_structural_clusters_info");
-    if (!ctx->sc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_structural_clusters_info: no structural clustering of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_structural_clusters_info", ctx->sc.done, NO_SC);
     const komb_ctx::Structural &r = ctx->sc;
     if (eps_num) *eps_num = r.eps_num;
     if (eps_den) *eps_den = r.eps_den;
@@ -541,54 +538,44 @@ int komb_structural_clusters_info(komb_ctx *ctx, int32_t *eps_num, int32_t *eps_
 int komb_nucleus_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_nucleus_run");
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    KOMB_TRY(require_full_truss(ctx, "komb_nucleus_run"));
     return nucleus_run(ctx);
 }
 
 int komb_nucleus_count(komb_ctx *ctx, int64_t *n_triangles)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_count");
-    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_count: no nucleus decomposition of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_count", ctx->nuc.done, NO_NUC);
     if (n_triangles) *n_triangles = ctx->nuc.n_tri;
     return KOMB_OK;
 }
 
 int komb_nucleus_fetch(komb_ctx *ctx, int32_t *a, int32_t *b, int32_t *c, int32_t *key0, int32_t *theta)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_fetch");
-    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_fetch: no nucleus decomposition of the current k-truss result");
-    const size_t bytes = (size_t)ctx->nuc.n_tri * sizeof(int32_t);
-    if (bytes == 0) return KOMB_OK;
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_fetch", ctx->nuc.done, NO_NUC);
+    const komb_ctx::Nucleus &r = ctx->nuc;
     int32_t *const out[5] = {a, b, c, key0, theta};
-    const int32_t *const src[5] = {ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_nuc_key0, ctx->d_nuc_theta};
-    for (int i = 0; i < 5; ++i)
-        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], src[i], bytes, false));
+    const int32_t *const src[5] = {r.a, r.b, r.c, r.key0, r.theta};
+    for (int i = 0; i < 5; ++i) KOMB_TRY(fetch(ctx, out[i], src[i], (size_t)r.n_tri));
     return KOMB_OK;
 }
 
 int komb_nucleus_fetch_edges(komb_ctx *ctx, int32_t *edge_theta)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_fetch_edges");
-    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_fetch_edges: no nucleus decomposition of the current k-truss result");
-    if (ctx->t_ne > 0 && edge_theta) KOMB_HIP(ctx, staged_copy(ctx, edge_theta, ctx->d_nuc_edge, (size_t)ctx->t_ne * sizeof(int32_t), false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_fetch_edges", ctx->nuc.done, NO_NUC);
+    KOMB_TRY(fetch(ctx, edge_theta, ctx->nuc.edge, (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0)));
     return KOMB_OK;
 }
 
 int komb_nucleus_fetch_vertices(komb_ctx *ctx, int32_t *vertex_theta)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_fetch_vertices");
-    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_fetch_vertices: no nucleus decomposition of the current k-truss result");
-    if (ctx->nv > 0 && vertex_theta) KOMB_HIP(ctx, staged_copy(ctx, vertex_theta, ctx->d_nuc_vertex, (size_t)ctx->nv * sizeof(int32_t), false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_fetch_vertices", ctx->nuc.done, NO_NUC);
+    KOMB_TRY(fetch(ctx, vertex_theta, ctx->nuc.vertex, (size_t)ctx->nv));
     return KOMB_OK;
 }
 
 int komb_nucleus_info(komb_ctx *ctx, int64_t *n_triangles, int64_t *n_cliques4, int32_t *theta_max, int32_t *n_levels, int64_t *n_subrounds, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_info");
-    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_info: no nucleus decomposition of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_info", ctx->nuc.done, NO_NUC);
     const komb_ctx::Nucleus &r = ctx->nuc;
     if (n_triangles) *n_triangles = r.n_tri;
     if (n_cliques4) *n_cliques4 = r.n_clq;
@@ -603,26 +590,21 @@ int komb_max_clique_run(komb_ctx *ctx, int64_t budget)
 {
     KOMB_HIER_ENTER(ctx, "komb_max_clique_run");
     if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_max_clique_run: bad node budget %lld", (long long)budget);
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    KOMB_TRY(require_full_truss(ctx, "komb_max_clique_run"));
     return max_clique_run(ctx, budget);
 }
 
 int komb_max_clique_fetch(komb_ctx *ctx, int32_t *count, int32_t *witness)
 {
-    KOMB_HIER_ENTER(ctx, "komb_max_clique_fetch");
-    if (!ctx->mc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_fetch: no maximum-clique search of the current k-truss result");
-    if (ctx->nv > 0 && count) KOMB_HIP(ctx, staged_copy(ctx, count, ctx->d_mc_count, (size_t)ctx->nv * sizeof(int32_t), false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_max_clique_fetch", ctx->mc.done, NO_MC);
+    KOMB_TRY(fetch(ctx, count, ctx->mc.count, (size_t)ctx->nv));
     if (witness && !ctx->mc.witness.empty()) memcpy(witness, ctx->mc.witness.data(), ctx->mc.witness.size() * sizeof(int32_t));
     return KOMB_OK;
 }
 
 int komb_max_clique_list(komb_ctx *ctx, int64_t cap, int64_t *n_cliques, int32_t *verts)
 {
-    KOMB_HIER_ENTER(ctx, "komb_max_clique_list");
-    if (!ctx->mc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_list: no maximum-clique search of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_max_clique_list", ctx->mc.done, NO_MC);
     const komb_ctx::MaxClique &r = ctx->mc;
     if (!(r.flags & KOMB_MAXCLQ_LISTED))
         KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_max_clique_list: the list was not kept (flags %d, %lld maximum cliques; option MAXCLQ_LIST, the node budget)",
@@ -636,8 +618,7 @@ int komb_max_clique_list(komb_ctx *ctx, int64_t cap, int64_t *n_cliques, int32_t
 int komb_max_clique_info(komb_ctx *ctx, int32_t *omega, int32_t *upper, int32_t *flags, int32_t *t_max, int64_t *n_max_cliques,
                          int64_t *n_roots, int64_t *nodes, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_max_clique_info");
-    if (!ctx->mc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_max_clique_info: no maximum-clique search of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_max_clique_info", ctx->mc.done, NO_MC);
     const komb_ctx::MaxClique &r = ctx->mc;
     if (omega) *omega = r.omega;
     if (upper) *upper = r.upper;
@@ -656,19 +637,15 @@ int komb_clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_
     if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_census_run: bad node budget %lld", (long long)budget);
     if (k_lo < 2 || (k_hi != -1 && k_hi < k_lo) || k_local < 0)
         KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_census_run: bad window k_lo %d, k_hi %d, k_local %d", (int)k_lo, (int)k_hi, (int)k_local);
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    KOMB_TRY(require_full_truss(ctx, "komb_clique_census_run"));
     return clique_census_run(ctx, k_lo, k_hi, k_local, budget);
 }
 
 int komb_clique_census_fetch(komb_ctx *ctx, uint64_t *total, uint64_t *local)
 {
-    KOMB_HIER_ENTER(ctx, "komb_clique_census_fetch");
-    if (!ctx->cc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_fetch: no clique census of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_clique_census_fetch", ctx->cc.done, NO_CC);
     if (local && ctx->cc.k_local == 0) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_fetch: the census ran without a k_local");
-    if (ctx->nv > 0 && local) KOMB_HIP(ctx, staged_copy(ctx, local, ctx->d_cc_local, (size_t)ctx->nv * sizeof(uint64_t), false));
+    KOMB_TRY(fetch(ctx, local, ctx->cc.local, (size_t)ctx->nv));
     if (total) memcpy(total, ctx->cc.total.data(), ctx->cc.total.size() * sizeof(uint64_t));
     return KOMB_OK;
 }
@@ -676,8 +653,7 @@ int komb_clique_census_fetch(komb_ctx *ctx, uint64_t *total, uint64_t *local)
 int komb_clique_census_info(komb_ctx *ctx, int32_t *k_lo, int32_t *k_hi, int32_t *k_local, int32_t *t_max, int32_t *omega, int32_t *flags,
                             int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_clique_census_info");
-    if (!ctx->cc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_census_info: no clique census of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_clique_census_info", ctx->cc.done, NO_CC);
     const komb_ctx::CliqueCensus &r = ctx->cc;
     if (k_lo) *k_lo = r.k_lo;
     if (k_hi) *k_hi = r.k_hi;
@@ -697,28 +673,22 @@ int komb_maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
     KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_run");
     if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_maximal_cliques_run: bad node budget %lld", (long long)budget);
     if (k_min < 2) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_maximal_cliques_run: bad k_min %d", (int)k_min);
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    KOMB_TRY(require_full_truss(ctx, "komb_maximal_cliques_run"));
     return maximal_cliques_run(ctx, k_min, budget);
 }
 
 int komb_maximal_cliques_fetch(komb_ctx *ctx, int64_t *hist, int32_t *count, int32_t *largest)
 {
-    KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_fetch");
-    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_fetch: no maximal cliques of the current k-truss result");
-    const size_t bytes = (size_t)(ctx->nv > 0 ? ctx->nv : 0) * sizeof(int32_t);
-    if (bytes && count) KOMB_HIP(ctx, staged_copy(ctx, count, ctx->d_mx_count, bytes, false));
-    if (bytes && largest) KOMB_HIP(ctx, staged_copy(ctx, largest, ctx->d_mx_count + ctx->nv, bytes, false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_maximal_cliques_fetch", ctx->mx.done, NO_MX);
+    KOMB_TRY(fetch(ctx, count, ctx->mx.count, (size_t)ctx->nv));
+    KOMB_TRY(fetch(ctx, largest, ctx->mx.count + ctx->nv, (size_t)ctx->nv));
     if (hist) memcpy(hist, ctx->mx.hist.data(), ctx->mx.hist.size() * sizeof(int64_t));
     return KOMB_OK;
 }
 
 int komb_maximal_cliques_list(komb_ctx *ctx, int64_t cap_cliques, int64_t cap_verts, int64_t *n_cliques, int64_t *n_verts, int64_t *offset, int32_t *verts)
 {
-    KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_list");
-    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_list: no maximal cliques of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_maximal_cliques_list", ctx->mx.done, NO_MX);
     const komb_ctx::MaximalCliques &r = ctx->mx;
     if (!(r.flags & KOMB_MAXIMAL_LISTED))
         KOMB_FAIL(ctx, KOMB_ERR_LIMIT, "komb_maximal_cliques_list: the list was not kept (flags %d, %lld cliques; option MAXIMAL_LIST, the node budget)",
@@ -737,8 +707,7 @@ int komb_maximal_cliques_list(komb_ctx *ctx, int64_t cap_cliques, int64_t cap_ve
 int komb_maximal_cliques_info(komb_ctx *ctx, int32_t *k_min, int32_t *k_hi, int32_t *t_max, int32_t *omega, int32_t *flags, int64_t *n_cliques,
                               int32_t *max_candidates, int64_t *n_roots, int64_t *nodes, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_maximal_cliques_info");
-    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_maximal_cliques_info: no maximal cliques of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_maximal_cliques_info", ctx->mx.done, NO_MX);
     const komb_ctx::MaximalCliques &r = ctx->mx;
     if (k_min) *k_min = r.k_min;
     if (k_hi) *k_hi = r.k_hi;
@@ -758,7 +727,7 @@ int komb_clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
     KOMB_HIER_ENTER(ctx, "komb_clique_communities_run");
     if (budget < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_communities_run: bad pair-test budget %lld", (long long)budget);
     if (k < 2) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_clique_communities_run: bad k %d", (int)k);
-    if (!ctx->mx_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_run: no maximal cliques of the current k-truss result");
+    if (!ctx->mx.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_run: " NO_MX);
     const komb_ctx::MaximalCliques &r = ctx->mx;
     if (r.k_min > k)
         KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_run: the held maximal cliques have k_min %d, above k %d: the list lacks member cliques",
@@ -771,8 +740,7 @@ int komb_clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
 
 int komb_clique_communities_count(komb_ctx *ctx, int64_t *n_communities, int64_t *n_member_verts)
 {
-    KOMB_HIER_ENTER(ctx, "komb_clique_communities_count");
-    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_count: no k-clique communities of the current maximal cliques");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_clique_communities_count", ctx->pc.done, NO_PC);
     if (n_communities) *n_communities = ctx->pc.n_comm;
     if (n_member_verts) *n_member_verts = (int64_t)ctx->pc.verts.size();
     return KOMB_OK;
@@ -780,8 +748,7 @@ int komb_clique_communities_count(komb_ctx *ctx, int64_t *n_communities, int64_t
 
 int komb_clique_communities_fetch(komb_ctx *ctx, int32_t *label, int32_t *size)
 {
-    KOMB_HIER_ENTER(ctx, "komb_clique_communities_fetch");
-    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_fetch: no k-clique communities of the current maximal cliques");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_clique_communities_fetch", ctx->pc.done, NO_PC);
     const komb_ctx::CliqueCommunities &r = ctx->pc;
     if (label && !r.label.empty()) memcpy(label, r.label.data(), r.label.size() * sizeof(int32_t));
     if (size && !r.size.empty()) memcpy(size, r.size.data(), r.size.size() * sizeof(int32_t));
@@ -790,8 +757,7 @@ int komb_clique_communities_fetch(komb_ctx *ctx, int32_t *label, int32_t *size)
 
 int komb_clique_communities_fetch_communities(komb_ctx *ctx, int32_t *rep, int32_t *n_cliques, int64_t *offset, int32_t *verts)
 {
-    KOMB_HIER_ENTER(ctx, "komb_clique_communities_fetch_communities");
-    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_fetch_communities: no k-clique communities of the current maximal cliques");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_clique_communities_fetch_communities", ctx->pc.done, NO_PC);
     const komb_ctx::CliqueCommunities &r = ctx->pc;
     if (rep && !r.rep.empty()) memcpy(rep, r.rep.data(), r.rep.size() * sizeof(int32_t));
     if (n_cliques && !r.n_cliques.empty()) memcpy(n_cliques, r.n_cliques.data(), r.n_cliques.size() * sizeof(int32_t));
@@ -802,8 +768,7 @@ int komb_clique_communities_fetch_communities(komb_ctx *ctx, int32_t *rep, int32
 
 int komb_clique_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm, int32_t *first)
 {
-    KOMB_HIER_ENTER(ctx, "komb_clique_communities_fetch_vertices");
-    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_fetch_vertices: no k-clique communities of the current maximal cliques");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_clique_communities_fetch_vertices", ctx->pc.done, NO_PC);
     const komb_ctx::CliqueCommunities &r = ctx->pc;
     if (n_comm && !r.v_comm.empty()) memcpy(n_comm, r.v_comm.data(), r.v_comm.size() * sizeof(int32_t));
     if (first && !r.v_first.empty()) memcpy(first, r.v_first.data(), r.v_first.size() * sizeof(int32_t));
@@ -813,8 +778,7 @@ int komb_clique_communities_fetch_vertices(komb_ctx *ctx, int32_t *n_comm, int32
 int komb_clique_communities_info(komb_ctx *ctx, int32_t *k, int32_t *k_min, int64_t *n_member_cliques, int64_t *n_communities, int64_t *largest,
                                  int64_t *n_covered, int64_t *n_overlap, int64_t *pair_tests, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_clique_communities_info");
-    if (!ctx->pc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_clique_communities_info: no k-clique communities of the current maximal cliques");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_clique_communities_info", ctx->pc.done, NO_PC);
     const komb_ctx::CliqueCommunities &r = ctx->pc;
     if (k) *k = r.k;
     if (k_min) *k_min = r.k_min;
@@ -830,36 +794,30 @@ int komb_clique_communities_info(komb_ctx *ctx, int32_t *k, int32_t *k_min, int6
 
 int komb_nucleus_hierarchy_run(komb_ctx *ctx)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_run");
-    if (!ctx->nuc_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_run: no nucleus decomposition of the current k-truss result");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_hierarchy_run", ctx->nuc.done, NO_NUC);
     return nucleus_hierarchy_run(ctx);
 }
 
 int komb_nucleus_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_count");
-    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_count: no nucleus hierarchy of the current nucleus decomposition");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_hierarchy_count", ctx->nh.done, NO_NH);
     if (n_nodes) *n_nodes = ctx->nh.n_nodes;
     return KOMB_OK;
 }
 
 int komb_nucleus_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent, int32_t *size, int32_t *shell)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_fetch_nodes");
-    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_fetch_nodes: no nucleus hierarchy of the current nucleus decomposition");
-    if (ctx->nh.n_nodes == 0) return KOMB_OK;
-    const size_t stride = (size_t)ctx->nh.cap, bytes = (size_t)ctx->nh.n_nodes * sizeof(int32_t);
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_hierarchy_fetch_nodes", ctx->nh.done, NO_NH);
+    const size_t stride = (size_t)ctx->nh.cap;
     int32_t *const out[5] = {k, rep, parent, size, shell};
-    for (int i = 0; i < 5; ++i)
-        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_nh_nodes + i * stride, bytes, false));
+    for (int i = 0; i < 5; ++i) KOMB_TRY(fetch(ctx, out[i], ctx->nh.nodes + i * stride, (size_t)ctx->nh.n_nodes));
     return KOMB_OK;
 }
 
 int komb_nucleus_hierarchy_fetch_triangles(komb_ctx *ctx, int32_t *node)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_fetch_triangles");
-    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_fetch_triangles: no nucleus hierarchy of the current nucleus decomposition");
-    if (ctx->nuc.n_tri > 0 && node) KOMB_HIP(ctx, staged_copy(ctx, node, ctx->d_nh_tnode, (size_t)ctx->nuc.n_tri * sizeof(int32_t), false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_hierarchy_fetch_triangles", ctx->nh.done, NO_NH);
+    KOMB_TRY(fetch(ctx, node, ctx->nh.tnode, (size_t)ctx->nuc.n_tri));
     return KOMB_OK;
 }
 
@@ -874,7 +832,7 @@ int komb_nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int3
 {
     KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_labels");
     if (k < KOMB_NUCLEUS_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_nucleus_hierarchy_labels: bad threshold %d", k);
-    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_labels: no nucleus hierarchy of the current nucleus decomposition");
+    if (!ctx->nh.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_labels: " NO_NH);
     return nucleus_hierarchy_labels(ctx, nucleus_hierarchy_k(ctx, k), label, size);
 }
 
@@ -883,15 +841,14 @@ int komb_nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t
 {
     KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_nuclei");
     if (k < KOMB_NUCLEUS_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_nucleus_hierarchy_nuclei: bad threshold %d", k);
-    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_nuclei: no nucleus hierarchy of the current nucleus decomposition");
+    if (!ctx->nh.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_nuclei: " NO_NH);
     return nucleus_hierarchy_nuclei(ctx, nucleus_hierarchy_k(ctx, k), cap, n_nuclei, rep, n_triangles, n_edges, n_vertices);
 }
 
 int komb_nucleus_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *theta_max, int32_t *depth,
                                 int64_t *n_member_triangles, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_nucleus_hierarchy_info");
-    if (!ctx->nh_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_nucleus_hierarchy_info: no nucleus hierarchy of the current nucleus decomposition");
+    KOMB_HIER_ENTER_DONE(ctx, "komb_nucleus_hierarchy_info", ctx->nh.done, NO_NH);
     const komb_ctx::NucleusHierarchy &r = ctx->nh;
     if (n_nodes) *n_nodes = r.n_nodes;
     if (n_roots) *n_roots = r.n_roots;
@@ -905,38 +862,30 @@ int komb_nucleus_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_root
 int komb_community_hierarchy_run(komb_ctx *ctx)
 {
     KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_run");
-    if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_run: no completed k-truss result on this graph");
-    if (ctx->t_ne > 0 && (ctx->t_k_lo != 0 || (int64_t)ctx->t_k_hi != ctx->t_ne))
-        KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_run: the last k-truss run materialised only the canonical edges [%u, %u) of %lld",
-                  ctx->t_k_lo, ctx->t_k_hi, (long long)ctx->t_ne);
+    KOMB_TRY(require_full_truss(ctx, "komb_community_hierarchy_run"));
     return community_hierarchy_run(ctx);
 }
 
 int komb_community_hierarchy_count(komb_ctx *ctx, int64_t *n_nodes)
 {
-    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_count");
-    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_count: no community hierarchy of the current k-truss result");
-    if (n_nodes) *n_nodes = ctx->ch_nodes;
+    KOMB_HIER_ENTER_DONE(ctx, "komb_community_hierarchy_count", ctx->ch.done, NO_CH);
+    if (n_nodes) *n_nodes = ctx->ch.n_nodes;
     return KOMB_OK;
 }
 
 int komb_community_hierarchy_fetch_nodes(komb_ctx *ctx, int32_t *k, int32_t *rep, int32_t *parent, int32_t *size, int32_t *shell)
 {
-    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_fetch_nodes");
-    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_fetch_nodes: no community hierarchy of the current k-truss result");
-    if (ctx->ch_nodes == 0) return KOMB_OK;
-    const size_t stride = (size_t)ctx->ch_cap, bytes = (size_t)ctx->ch_nodes * sizeof(int32_t);
+    KOMB_HIER_ENTER_DONE(ctx, "komb_community_hierarchy_fetch_nodes", ctx->ch.done, NO_CH);
+    const size_t stride = (size_t)ctx->ch.cap;
     int32_t *const out[5] = {k, rep, parent, size, shell};
-    for (int i = 0; i < 5; ++i)
-        if (out[i]) KOMB_HIP(ctx, staged_copy(ctx, out[i], ctx->d_ch_nodes + i * stride, bytes, false));
+    for (int i = 0; i < 5; ++i) KOMB_TRY(fetch(ctx, out[i], ctx->ch.nodes + i * stride, (size_t)ctx->ch.n_nodes));
     return KOMB_OK;
 }
 
 int komb_community_hierarchy_fetch_edges(komb_ctx *ctx, int32_t *node)
 {
-    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_fetch_edges");
-    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_fetch_edges: no community hierarchy of the current k-truss result");
-    if (ctx->t_ne > 0 && node) KOMB_HIP(ctx, staged_copy(ctx, node, ctx->d_ch_enode, (size_t)ctx->t_ne * sizeof(int32_t), false));
+    KOMB_HIER_ENTER_DONE(ctx, "komb_community_hierarchy_fetch_edges", ctx->ch.done, NO_CH);
+    KOMB_TRY(fetch(ctx, node, ctx->ch.enode, (size_t)(ctx->t_ne > 0 ? ctx->t_ne : 0)));
     return KOMB_OK;
 }
 
@@ -944,23 +893,20 @@ int komb_community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, in
 {
     KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_labels");
     if (k < KOMB_COMM_K_MAX) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_community_hierarchy_labels: bad threshold %d", k);
-    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_labels: no community hierarchy of the current k-truss result");
-    if (k == KOMB_COMM_K_MAX) k = ctx->t_ne > 0 && ctx->stats.max_trussness > 2 ? ctx->stats.max_trussness : 2;
-    if (k < 2) k = 2;
-    return community_hierarchy_labels(ctx, k, label, size);
+    if (!ctx->ch.done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_labels: " NO_CH);
+    return community_hierarchy_labels(ctx, resolve_truss_k(ctx, k), label, size);
 }
 
 int komb_community_hierarchy_info(komb_ctx *ctx, int64_t *n_nodes, int64_t *n_roots, int32_t *k_max, int32_t *depth,
                                   int64_t *n_member_edges, double *ms)
 {
-    KOMB_HIER_ENTER(ctx, "komb_community_hierarchy_info");
-    if (!ctx->ch_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_community_hierarchy_info: no community hierarchy of the current k-truss result");
-    if (n_nodes) *n_nodes = ctx->ch_nodes;
-    if (n_roots) *n_roots = ctx->ch_roots;
-    if (k_max) *k_max = ctx->ch_kmax;
-    if (depth) *depth = ctx->ch_depth;
-    if (n_member_edges) *n_member_edges = ctx->ch_members;
-    if (ms) *ms = ctx->ch_ms;
+    KOMB_HIER_ENTER_DONE(ctx, "komb_community_hierarchy_info", ctx->ch.done, NO_CH);
+    if (n_nodes) *n_nodes = ctx->ch.n_nodes;
+    if (n_roots) *n_roots = ctx->ch.n_roots;
+    if (k_max) *k_max = ctx->ch.kmax;
+    if (depth) *depth = ctx->ch.depth;
+    if (n_member_edges) *n_member_edges = ctx->ch.members;
+    if (ms) *ms = ctx->ch.ms;
     return KOMB_OK;
 }
 
@@ -1079,12 +1025,12 @@ int komb_truss_fetch(komb_ctx *ctx, int32_t *eu, int32_t *ev, int32_t *truss)
 {
     KOMB_TRY(require_device(ctx));
     if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_fetch: komb_truss_run has not completed");
-    const size_t bytes = (size_t)ctx->t_ne * sizeof(int32_t);
-    if (bytes == 0) return KOMB_OK;
+    const size_t m = (size_t)ctx->t_ne;
+    if (m == 0) return KOMB_OK;
     if (eu || ev) KOMB_TRY(truss_edges_canonical(ctx));  // (the endpoints: igraph_edge after igraph_trussness, src/graph.cpp:529-532 -- not part of the timed call)
-    if (eu) KOMB_HIP(ctx, staged_copy(ctx, eu, ctx->d_t_eu, bytes, false));
-    if (ev) KOMB_HIP(ctx, staged_copy(ctx, ev, ctx->d_t_ev, bytes, false));
-    if (truss) KOMB_HIP(ctx, staged_copy(ctx, truss, ctx->d_t_truss, bytes, false));
+    KOMB_TRY(fetch(ctx, eu, ctx->d_t_eu, m));
+    KOMB_TRY(fetch(ctx, ev, ctx->d_t_ev, m));
+    KOMB_TRY(fetch(ctx, truss, ctx->d_t_truss, m));
     return KOMB_OK;
 }
 
@@ -1093,8 +1039,7 @@ int komb_truss_fetch_support(komb_ctx *ctx, int32_t *support)
     KOMB_TRY(require_device(ctx));
     if (!ctx->truss_done) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_truss_fetch_support: komb_truss_run has not completed");
     KOMB_TRY(truss_support_canonical(ctx));              // (made on the first request: the timed step delivers trussness, as igraph_trussness does)
-    const size_t bytes = (size_t)ctx->t_ne * sizeof(int32_t);
-    if (bytes && support) KOMB_HIP(ctx, staged_copy(ctx, support, ctx->d_t_sup, bytes, false));
+    KOMB_TRY(fetch(ctx, support, ctx->d_t_sup, (size_t)ctx->t_ne));
     return KOMB_OK;
 }
 

@@ -440,32 +440,23 @@ __global__ void k_bc_no_vertices(uint32_t nv, int32_t *__restrict__ n_blocks, in
 
 } // namespace
 
-void biconnected_drop(komb_ctx *ctx)
-{
-    ctx->pool.put(ctx->d_bc_block); ctx->pool.put(ctx->d_bc_size); ctx->pool.put(ctx->d_bc_nblocks);
-    ctx->pool.put(ctx->d_bc_ecc_label); ctx->pool.put(ctx->d_bc_ecc_size); ctx->pool.put(ctx->d_bc_list);
-    ctx->d_bc_block = ctx->d_bc_size = ctx->d_bc_nblocks = ctx->d_bc_ecc_label = ctx->d_bc_ecc_size = ctx->d_bc_list = nullptr;
-    ctx->bc = komb_ctx::Biconnected{};
-    ctx->bc_done = false;
-}
-
 // k is checked and resolved by the caller (api.cpp): >= 2
 int biconnected_run(komb_ctx *ctx, int32_t k)
 {
     hipStream_t s = ctx->stream;
     const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv;
-    biconnected_drop(ctx);
-    ctx->bc.k = k;
+    ctx->bc = {};                                        // a run that fails leaves no result (include/komb_accel.h)
+    komb_ctx::Biconnected res;                           // goes back to the pool unless it is installed
+    res.k = k;
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
 
     Range r_all("komb_biconnected_run");
-    struct Fail { komb_ctx *c; bool armed = true; ~Fail() { if (armed) biconnected_drop(c); } } fail{ctx};
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_bc_block, (size_t)m * sizeof(int32_t)));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_bc_size, (size_t)m * sizeof(int32_t)));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_bc_nblocks, (size_t)nv * sizeof(int32_t)));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_bc_ecc_label, (size_t)nv * sizeof(int32_t)));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_bc_ecc_size, (size_t)nv * sizeof(int32_t)));
-    int32_t *block = ctx->d_bc_block, *size = ctx->d_bc_size, *n_blocks = ctx->d_bc_nblocks, *ecc_label = ctx->d_bc_ecc_label;
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.block.slot(&ctx->pool), (size_t)m * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.size.slot(&ctx->pool), (size_t)m * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.nblocks.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.ecc_label.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.ecc_size.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
+    int32_t *block = res.block, *size = res.size, *n_blocks = res.nblocks, *ecc_label = res.ecc_label;
     const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *truss = ctx->d_t_truss;
     const int vgrid = bc_grid(nv), egrid = bc_grid(m);
 
@@ -485,11 +476,11 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
     }
     if (nm == 0) {                                       // no member edge: nothing to traverse
         if (m > 0) k_bc_no_edges<<<egrid, kBlock, 0, s>>>((uint32_t)m, block, size);
-        if (nv > 0) k_bc_no_vertices<<<vgrid, kBlock, 0, s>>>((uint32_t)nv, n_blocks, ecc_label, ctx->d_bc_ecc_size);
-        ctx->bc.ms = ctx->timer.stop(s);
+        if (nv > 0) k_bc_no_vertices<<<vgrid, kBlock, 0, s>>>((uint32_t)nv, n_blocks, ecc_label, res.ecc_size);
+        res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
-        ctx->bc_done = true;
-        fail.armed = false;
+        res.done = true;
+        ctx->bc = std::move(res);
         return KOMB_OK;
     }
     if (2ull * nm > 0xFFFFFFFFull)
@@ -567,16 +558,16 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
     k_bc_flatten<false><<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_epar);
     k_bc_ecc_label<<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_level, d_epar, ecc_label);
     k_bc_ecc_count<<<tail_v, kBlock, 0, s>>>((uint32_t)nv, ecc_label, d_ecnt);
-    k_bc_vfinish<<<tail_v, kBlock, 0, s>>>((uint32_t)nv, ecc_label, d_ecnt, n_blocks, d_edges, ctx->d_bc_ecc_size, d_ctl);
+    k_bc_vfinish<<<tail_v, kBlock, 0, s>>>((uint32_t)nv, ecc_label, d_ecnt, n_blocks, d_edges, res.ecc_size, d_ctl);
 
     // ---- the block list
     r_part.next("biconnected: block list");
     KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_flag, m + 1));      // (in place: is_rep[] becomes the position in the list)
     uint32_t nb = 0;
     KOMB_HIP(ctx, d2h(ctx, &nb, d_flag + m, sizeof(uint32_t)));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_bc_list, 3 * (size_t)(nb ? nb : 1) * sizeof(int32_t)));
-    if (nb) k_bc_list<<<egrid, kBlock, 0, s>>>((uint32_t)m, block, size, d_flag, d_pos, d_eblk, d_tree, ctx->d_bc_list, ctx->d_bc_list + nb,
-                                               ctx->d_bc_list + 2 * (size_t)nb);
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.list.slot(&ctx->pool), 3 * (size_t)(nb ? nb : 1) * sizeof(int32_t)));
+    if (nb) k_bc_list<<<egrid, kBlock, 0, s>>>((uint32_t)m, block, size, d_flag, d_pos, d_eblk, d_tree, res.list, res.list + nb,
+                                               res.list + 2 * (size_t)nb);
     const double ms = ctx->timer.stop(s);
     KOMB_HIP(ctx, hipGetLastError());
     BiconnCtl h;
@@ -584,12 +575,12 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
     if (h.n_member_edges != nm || h.tail != nmv || h.pre_next != nmv)
         KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_biconnected_run: inconsistent counts (%u of %u member edges, %u of %u vertices numbered)",
                   h.n_member_edges, nm, h.pre_next, nmv);
-    ctx->bc.n_member_edges = (int64_t)nm; ctx->bc.n_member_vertices = (int64_t)nmv; ctx->bc.n_blocks = (int64_t)nb;
-    ctx->bc.n_bridges = (int64_t)h.n_bridges; ctx->bc.n_articulation = (int64_t)h.n_articulation; ctx->bc.largest_block = (int64_t)h.largest_block;
-    ctx->bc.n_ecc = (int64_t)h.n_ecc; ctx->bc.largest_ecc = (int64_t)h.largest_ecc;
-    ctx->bc.depth = depth; ctx->bc.ms = ms;
-    ctx->bc_done = true;
-    fail.armed = false;
+    res.n_member_edges = (int64_t)nm; res.n_member_vertices = (int64_t)nmv; res.n_blocks = (int64_t)nb;
+    res.n_bridges = (int64_t)h.n_bridges; res.n_articulation = (int64_t)h.n_articulation; res.largest_block = (int64_t)h.largest_block;
+    res.n_ecc = (int64_t)h.n_ecc; res.largest_ecc = (int64_t)h.largest_ecc;
+    res.depth = depth; res.ms = ms;
+    res.done = true;
+    ctx->bc = std::move(res);
     return KOMB_OK;
 }
 

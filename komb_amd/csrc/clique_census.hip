@@ -192,14 +192,6 @@ __global__ void k_cc_saturated(const unsigned long long *__restrict__ total, uin
 
 } // namespace
 
-void clique_census_drop(komb_ctx *ctx)
-{
-    ctx->pool.put(ctx->d_cc_local);
-    ctx->d_cc_local = nullptr;
-    ctx->cc = komb_ctx::CliqueCensus{};
-    ctx->cc_done = false;
-}
-
 // the k-truss result it needs, the budget's sign and 2 <= k_lo are checked by the caller (api.cpp); the rest of the window needs
 // t_max.  The result is built on the side and replaces the previous one only when the run has succeeded.
 int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local, int64_t budget)
@@ -208,8 +200,7 @@ int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local
     const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv > 0 ? ctx->nv : 0;
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
     Range r_all("komb_clique_census_run");
-    struct Fresh { komb_ctx *c; unsigned long long *local; ~Fresh() { c->pool.put(local); } } fresh{ctx, nullptr};
-    komb_ctx::CliqueCensus res;
+    komb_ctx::CliqueCensus res;                          // goes back to the pool unless it is installed
     const long long limit = budget == 0 ? kClqDefaultBudget : std::min<long long>(budget, kClqMaxBudget);
     DevBufs bufs(ctx);
     ClqCtl h{};
@@ -229,8 +220,8 @@ int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local
     res.k_lo = k_lo; res.k_hi = k_hi; res.k_local = k_local; res.t_max = t_max;
     res.total.assign(n_k, 0);
     if (k_local) {
-        KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.local, (size_t)nv * sizeof(unsigned long long)));
-        if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.local, 0, (size_t)nv * sizeof(unsigned long long), s));
+        KOMB_HIP(ctx, ctx->pool.get((void **)res.local.slot(&ctx->pool), (size_t)nv * sizeof(unsigned long long)));
+        if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(res.local, 0, (size_t)nv * sizeof(unsigned long long), s));
     }
     res.flags = KOMB_CENSUS_COMPLETE;
     if (m > 0 && k_lo <= t_max) {                        // (above t_max there is nothing to count)
@@ -256,7 +247,7 @@ int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local
         A.pivot_max = !(pv && strcmp(pv, "first") == 0);
         A.budget = (unsigned long long)limit;
         A.binom = d_binom; A.binom_stride = (uint32_t)bs;
-        A.local = fresh.local;
+        A.local = res.local;
         // ---- the largest |P| at need k_lo
         A.count_only = true;
         const int count_grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kClqGrid);
@@ -297,11 +288,8 @@ int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local
         fprintf(stderr, "komb clique census: %lld edges, t_max %d, window %d .. %d, k_local %d, omega %d, flags %d, largest candidate set %d, %lld roots, "
                 "%lld nodes of %lld, run %.3f ms\n", (long long)m, res.t_max, res.k_lo, res.k_hi, res.k_local, res.omega, res.flags, res.max_p,
                 (long long)res.n_roots, (long long)res.nodes, limit, res.ms);
-    clique_census_drop(ctx);
-    ctx->d_cc_local = fresh.local;
-    fresh.local = nullptr;
+    res.done = true;
     ctx->cc = std::move(res);
-    ctx->cc_done = true;
     return KOMB_OK;
 }
 

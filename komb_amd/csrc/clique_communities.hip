@@ -296,12 +296,6 @@ inline int pc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
 } // namespace
 
-void clique_communities_drop(komb_ctx *ctx)
-{
-    ctx->pc = komb_ctx::CliqueCommunities{};
-    ctx->pc_done = false;
-}
-
 // the held list (listed, k_min <= k), 2 <= k and the budget's sign are checked by the caller (api.cpp).  The result is built on the
 // side and replaces the previous one only when the run has succeeded.
 int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
@@ -471,8 +465,8 @@ int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
                 "%lld pair tests of %llu, %u links, %lld communities, largest %lld, covered %lld, overlap %lld, run %.3f ms\n", (int)k, (int)res.k_min,
                 (long long)nc, (long long)res.n_member, smax, (long long)entries, group, (long long)res.pair_tests, limit, links_seen, (long long)res.n_comm,
                 (long long)res.largest, (long long)res.n_covered, (long long)res.n_overlap, res.ms);
+    res.done = true;
     ctx->pc = std::move(res);
-    ctx->pc_done = true;
     return KOMB_OK;
 }
 

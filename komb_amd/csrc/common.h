@@ -269,6 +269,31 @@ struct DevPool {
     }
 };
 
+// One device array of a result and where it came from: a block of a pool, or (pool == nullptr) a hipMalloc made through
+// dev_malloc.  Move-only; it allocates nothing: an allocation call fills slot(), and whatever the handle holds goes back where
+// it came from when the handle is reset, assigned to or destroyed.  A result is a struct of these (komb_ctx), so dropping it
+// is `ctx->x = {}` and installing a finished one is one move.
+template <class T> struct DevArr {
+    T *p = nullptr;
+    DevPool *pool = nullptr;
+    DevArr() = default;
+    DevArr(DevArr &&o) noexcept : p(o.p), pool(o.pool) { o.p = nullptr; }
+    DevArr &operator=(DevArr &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; pool = o.pool; o.p = nullptr; }
+        return *this;
+    }
+    ~DevArr() { reset(); }
+    void reset()
+    {
+        if (p) { if (pool) pool->put(p); else (void)hipFree(p); }
+        p = nullptr;
+    }
+    T **slot(DevPool *from) { reset(); pool = from; return &p; }   // what `from`->get() or (null) dev_malloc writes the array to
+    T *get() const { return p; }
+    operator T *() const { return p; }
+};
+
 // Everything the k-truss path derives from a symmetric CSR before it enumerates a triangle (truss_prep.hip): the
 // (degree,id) renumbering, the oriented CSR in those INTERNAL ids, the canonical edge list and the internal edge id of
 // every canonical edge, the per-vertex lines and the task table of the enumeration.  Built on the first k-truss call
@@ -291,7 +316,7 @@ struct TrussPrep {
 
 struct komb_ctx {
     komb_opts opts{};
-    DevPool pool;
+    DevPool pool;                            // (declared before every result record: it outlives their handles when the context is deleted)
     std::string err;
     bool device_ok = false;
     int device = 0;
@@ -308,156 +333,172 @@ struct komb_ctx {
     // ---- the k-truss side of the graph, made when a k-truss call first needs it
     TrussPrep prep;
 
+    // ---- the results of the analyses: one record each -- its device arrays (DevArr: they go back where they came from when the
+    // record is dropped, `ctx->x = {}`, or replaced), its summary and host vectors, and `done`.  DESIGN.md section 3 says who
+    // drops whom.
+
     // ---- k-core results
-    int32_t *d_deg = nullptr;                // [nv] degree (a2), ORIGINAL ids
-    int32_t *d_core = nullptr;               // [nv] coreness (a3), ORIGINAL ids
-    bool core_done = false;
+    struct Core {
+        DevArr<int32_t> deg;                 // [nv] degree (a2), ORIGINAL ids
+        DevArr<int32_t> core;                // [nv] coreness (a3), ORIGINAL ids
+        bool done = false;
+    } core;
 
     // ---- onion decomposition results (onion.hip): arrays of their own, none of k-core's
-    int32_t *d_onion_layer = nullptr;        // [nv] layer, ORIGINAL ids
-    int32_t *d_onion_core = nullptr;         // [nv] coreness the vertex left at
-    int64_t onion_layers = 0;                // largest layer number of the last run
-    int32_t onion_max_core = 0;
-    double onion_ms = 0.0;                   // device time of the last run (HIP events)
-    bool onion_done = false;
+    struct Onion {
+        DevArr<int32_t> layer;               // [nv] layer, ORIGINAL ids
+        DevArr<int32_t> core;                // [nv] coreness the vertex left at
+        int64_t n_layers = 0;                // largest layer number of the last run
+        int32_t max_core = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
+    } onion;
 
     // ---- connected components of a k-core / k-truss subgraph (components.hip): a snapshot in arrays of its own
-    int32_t *d_comp_label = nullptr;         // [nv] smallest ORIGINAL id of the vertex' component, -1 for a non-member
-    int32_t *d_comp_size = nullptr;          // [nv] vertices of that component, 0 for a non-member
-    int32_t comp_kind = 0, comp_k = 0;       // what the last run was asked for (k resolved)
-    int64_t comp_members = 0, comp_count = 0, comp_largest = 0;
-    double comp_ms = 0.0;                    // device time of the last run (HIP events)
-    bool comp_done = false;
+    struct Components {
+        DevArr<int32_t> label;               // [nv] smallest ORIGINAL id of the vertex' component, -1 for a non-member
+        DevArr<int32_t> size;                // [nv] vertices of that component, 0 for a non-member
+        int32_t kind = 0, k = 0;             // what the last run was asked for (k resolved)
+        int64_t members = 0, count = 0, largest = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
+    } comp;
 
     // ---- component hierarchy (hierarchy.hip): the nesting forest of the k-core / k-truss components, a snapshot in arrays of its own
-    int32_t *d_hier_nodes = nullptr;         // [5 * max(nv, 1)] k | rep | parent | size | shell, each a block of max(nv, 1) words with hier_nodes in use
-    int32_t *d_hier_vnode = nullptr;         // [nv] the node of every vertex, -1 for a non-member
-    int32_t hier_kind = 0, hier_kmax = 0, hier_depth = 0;
-    int64_t hier_nodes = 0, hier_roots = 0;
-    double hier_ms = 0.0;                    // device time of the last run (HIP events)
-    bool hier_done = false;
+    struct Hierarchy {
+        DevArr<int32_t> nodes;               // [5 * max(nv, 1)] k | rep | parent | size | shell, each a block of max(nv, 1) words with n_nodes in use
+        DevArr<int32_t> vnode;               // [nv] the node of every vertex, -1 for a non-member
+        int32_t kind = 0, kmax = 0, depth = 0;
+        int64_t n_nodes = 0, n_roots = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
+    } hier;
 
     // ---- densest-subgraph search (densest.hip): a snapshot in arrays of its own (pool blocks), dropped with the graph
-    int32_t *d_dens_member = nullptr;        // [nv] 1 for a vertex of the result, 0 otherwise
-    int32_t *d_dens_load = nullptr;          // [nv] Frank-Wolfe load of the vertex, 0 outside the pruned set
     struct Densest {
+        DevArr<int32_t> member;              // [nv] 1 for a vertex of the result, 0 otherwise
+        DevArr<int32_t> load;                // [nv] Frank-Wolfe load of the vertex, 0 outside the pruned set
         int32_t source = 0, k_best = 0, k_prune = 0, iters = 0, k_max = 0;
         int64_t n_pruned = 0, m_pruned = 0, n_sub = 0, m_sub = 0, load_max = 0;
         double ms = 0.0;                     // device time of the last run (HIP events)
         bool local = false;                  // the rounds ran in the single-workgroup LDS kernel
+        std::vector<int64_t> profile;        // n_k[k_max + 1] | m_k[k_max + 1] of the last run
+        bool done = false;
     } dens;
-    std::vector<int64_t> dens_profile;       // n_k[k_max + 1] | m_k[k_max + 1] of the last run
-    bool dens_done = false;
 
     // ---- k-truss communities (communities.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
-    int32_t *d_comm_label = nullptr;         // [t_ne] smallest canonical edge index of the edge's community, -1 for a non-member
-    int32_t *d_comm_size = nullptr;          // [t_ne] edges of that community, 0 for a non-member
-    int32_t *d_comm_ncomm = nullptr;         // [nv] distinct communities at the vertex: made by the first fetch_vertices / info after a run
-    int32_t comm_k = 0;                      // the threshold of the last run (resolved)
-    int64_t comm_members = 0, comm_count = 0, comm_largest = 0, comm_multi = 0;
-    double comm_ms = 0.0, comm_ms_vertices = 0.0;   // device time of the run | of the vertex pass (HIP events)
-    bool comm_done = false, comm_v_ready = false;
+    struct Communities {
+        DevArr<int32_t> label;               // [t_ne] smallest canonical edge index of the edge's community, -1 for a non-member
+        DevArr<int32_t> size;                // [t_ne] edges of that community, 0 for a non-member
+        DevArr<int32_t> ncomm;               // [nv] distinct communities at the vertex: made by the first fetch_vertices / info after a run
+        int32_t k = 0;                       // the threshold of the last run (resolved)
+        int64_t members = 0, count = 0, largest = 0, multi = 0;
+        double ms = 0.0, ms_vertices = 0.0;  // device time of the run | of the vertex pass (HIP events)
+        bool done = false, v_ready = false;
+    } comm;
 
     // ---- biconnected components (biconnected.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
-    int32_t *d_bc_block = nullptr;           // [t_ne] smallest canonical edge index of the edge's block, -1 for a non-member
-    int32_t *d_bc_size = nullptr;            // [t_ne] edges of that block, 0 for a non-member (1: a bridge)
-    int32_t *d_bc_nblocks = nullptr;         // [nv] blocks that contain the vertex (>= 2: an articulation point)
-    int32_t *d_bc_ecc_label = nullptr;       // [nv] smallest ORIGINAL id of the vertex' 2-edge-connected component, -1 for a non-member
-    int32_t *d_bc_ecc_size = nullptr;        // [nv] vertices of that component, 0 for a non-member
-    int32_t *d_bc_list = nullptr;            // [3 * n_blocks] rep | n_edges | n_verts of the blocks in ascending rep order
     struct Biconnected {
+        DevArr<int32_t> block;               // [t_ne] smallest canonical edge index of the edge's block, -1 for a non-member
+        DevArr<int32_t> size;                // [t_ne] edges of that block, 0 for a non-member (1: a bridge)
+        DevArr<int32_t> nblocks;             // [nv] blocks that contain the vertex (>= 2: an articulation point)
+        DevArr<int32_t> ecc_label;           // [nv] smallest ORIGINAL id of the vertex' 2-edge-connected component, -1 for a non-member
+        DevArr<int32_t> ecc_size;            // [nv] vertices of that component, 0 for a non-member
+        DevArr<int32_t> list;                // [3 * n_blocks] rep | n_edges | n_verts of the blocks in ascending rep order
         int32_t k = 0, depth = 0;            // the threshold of the last run (resolved) | the levels of its spanning forest
         int64_t n_member_edges = 0, n_member_vertices = 0, n_blocks = 0, n_bridges = 0, n_articulation = 0, largest_block = 0,
                 n_ecc = 0, largest_ecc = 0;
         double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
     } bc;
-    bool bc_done = false;
 
     // ---- k-truss community hierarchy (community_hierarchy.hip): the nesting forest of the communities over all k, in pool blocks
     // of its own, indexed like the k-truss result it was computed from and dropped with it (truss_free)
-    int32_t *d_ch_nodes = nullptr;           // [5 * ch_cap] k | rep | parent | size | shell, each a block of ch_cap words with ch_nodes in use
-    int32_t *d_ch_enode = nullptr;           // [t_ne] the node of every canonical edge, -1 for a non-member
-    int64_t ch_cap = 1, ch_nodes = 0, ch_roots = 0, ch_members = 0;
-    int32_t ch_kmax = 2, ch_depth = 0;
-    double ch_ms = 0.0;                      // device time of the last run (HIP events)
-    bool ch_done = false;
+    struct CommunityHierarchy {
+        DevArr<int32_t> nodes;               // [5 * cap] k | rep | parent | size | shell, each a block of cap words with n_nodes in use
+        DevArr<int32_t> enode;               // [t_ne] the node of every canonical edge, -1 for a non-member
+        int64_t cap = 1, n_nodes = 0, n_roots = 0, members = 0;
+        int32_t kmax = 2, depth = 0;
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
+    } ch;
 
     // ---- structural clustering (structural.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
-    int32_t *d_sc_label = nullptr;           // [nv] the cluster of the vertex (smallest ORIGINAL id of its cores' class), -1 for a hub / an outlier
-    int32_t *d_sc_size = nullptr;            // [nv] vertices that carry that label, 0 for label -1
-    int32_t *d_sc_role = nullptr;            // [nv] KOMB_SC_*
-    int32_t *d_sc_simdeg = nullptr;          // [nv] similar edges at the vertex
-    uint8_t *d_sc_similar = nullptr;         // [t_ne] 1 for a similar edge
     struct Structural {
+        DevArr<int32_t> label;               // [nv] the cluster of the vertex (smallest ORIGINAL id of its cores' class), -1 for a hub / an outlier
+        DevArr<int32_t> size;                // [nv] vertices that carry that label, 0 for label -1
+        DevArr<int32_t> role;                // [nv] KOMB_SC_*
+        DevArr<int32_t> simdeg;              // [nv] similar edges at the vertex
+        DevArr<uint8_t> similar;             // [t_ne] 1 for a similar edge
         int32_t eps_num = 0, eps_den = 0, mu = 0;
         int64_t n_similar = 0, n_cores = 0, n_borders = 0, n_hubs = 0, n_outliers = 0, n_clusters = 0, largest = 0;
         double ms = 0.0, ms_similar = 0.0;   // device time of the last run | of its similarity pass (HIP events)
+        bool done = false;
     } sc;
-    bool sc_done = false;
 
     // ---- (3,4)-nucleus decomposition (nucleus.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
-    int32_t *d_nuc_a = nullptr, *d_nuc_b = nullptr, *d_nuc_c = nullptr;   // [n_tri] the triangles a < b < c in ascending (a, b, c) order, ORIGINAL ids
-    int32_t *d_nuc_key0 = nullptr;           // [n_tri + 1] the 4-cliques of the result the triangle lies in
-    int32_t *d_nuc_theta = nullptr;          // [n_tri] its nucleus number
-    int32_t *d_nuc_edge = nullptr;           // [t_ne] largest theta over the triangles through the canonical edge, -1 without one
-    int32_t *d_nuc_vertex = nullptr;         // [nv] the same per vertex
     struct Nucleus {
+        DevArr<int32_t> a, b, c;             // [n_tri] the triangles a < b < c in ascending (a, b, c) order, ORIGINAL ids
+        DevArr<int32_t> key0;                // [n_tri + 1] the 4-cliques of the result the triangle lies in
+        DevArr<int32_t> theta;               // [n_tri] its nucleus number
+        DevArr<int32_t> edge;                // [t_ne] largest theta over the triangles through the canonical edge, -1 without one
+        DevArr<int32_t> vertex;              // [nv] the same per vertex
         int64_t n_tri = 0, n_clq = 0, n_subrounds = 0;
         int32_t theta_max = -1, n_levels = 0;
         double ms = 0.0, ms_tri = 0.0, ms_clq = 0.0, ms_peel = 0.0;   // device time of the last run | of its passes (HIP events; option NUC_DEBUG prints them)
+        bool done = false;
     } nuc;
-    bool nuc_done = false;
 
     // ---- (3,4)-nucleus hierarchy (nucleus_hierarchy.hip): the k-nuclei as connected classes and their nesting forest over all k,
     // in pool blocks of its own, indexed like the nucleus result it was computed from and dropped with it (nucleus_drop)
-    int32_t *d_nh_nodes = nullptr;           // [5 * nh.cap] k | rep | parent | size | shell, each a block of nh.cap words with nh.n_nodes in use
-    int32_t *d_nh_tnode = nullptr;           // [n_tri] the node of every triangle, -1 where theta == 0
     struct NucleusHierarchy {
+        DevArr<int32_t> nodes;               // [5 * cap] k | rep | parent | size | shell, each a block of cap words with n_nodes in use
+        DevArr<int32_t> tnode;               // [n_tri] the node of every triangle, -1 where theta == 0
         int64_t cap = 1, n_nodes = 0, n_roots = 0, n_members = 0;
         int32_t theta_max = -1, depth = 0;
         double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
     } nh;
-    bool nh_done = false;
 
     // ---- maximum-clique search (max_clique.hip): the per-vertex counts in a pool block of their own, the witness and the sorted list
     // on the host; they describe the k-truss result they were computed from and are dropped with it (truss_free)
-    int32_t *d_mc_count = nullptr;           // [nv] maximum cliques through the vertex (not enumerated: 1 on the witness)
     struct MaxClique {
+        DevArr<int32_t> count;               // [nv] maximum cliques through the vertex (not enumerated: 1 on the witness)
         int32_t omega = 0, upper = 0, flags = 0, t_max = 0;
         int64_t n_max = -1, n_roots = 0, nodes = 0;
         double ms = 0.0;                     // device time of the last run (HIP events)
         std::vector<int32_t> witness;        // [omega] ascending
         std::vector<int32_t> list;           // [n_max * omega] with KOMB_MAXCLQ_LISTED: ascending tuples in lexicographic order
+        bool done = false;
     } mc;
-    bool mc_done = false;
 
     // ---- clique census (clique_census.hip): the per-vertex counts in a pool block of their own (only with a k_local), the totals on
     // the host; they describe the k-truss result they were computed from and are dropped with it (truss_free)
-    unsigned long long *d_cc_local = nullptr;   // [nv] k_local-cliques through the vertex, saturating
     struct CliqueCensus {
+        DevArr<unsigned long long> local;    // [nv] k_local-cliques through the vertex, saturating
         int32_t k_lo = 0, k_hi = 0, k_local = 0, t_max = 0, omega = 0, flags = 0, max_p = 0;
         int64_t n_roots = 0, nodes = 0;
         double ms = 0.0;                     // device time of the last run (HIP events)
         std::vector<uint64_t> total;         // [k_hi - k_lo + 1] k-cliques, saturating
+        bool done = false;
     } cc;
-    bool cc_done = false;
 
     // ---- maximal cliques (maximal_cliques.hip): the per-vertex counts in a pool block of their own, the histogram and the sorted
     // list on the host; they describe the k-truss result they were computed from and are dropped with it (truss_free)
-    int32_t *d_mx_count = nullptr;           // [2 * nv] reported cliques through the vertex | the size of the largest one
     struct MaximalCliques {
+        DevArr<int32_t> count;               // [2 * nv] reported cliques through the vertex | the size of the largest one
         int32_t k_min = 0, k_hi = 0, t_max = 0, omega = 0, flags = 0, max_q = 0;
         int64_t n_cliques = 0, n_roots = 0, nodes = 0;
         double ms = 0.0;                     // device time of the last run (HIP events)
         std::vector<int64_t> hist;           // [k_hi - k_min + 1] maximal cliques of k_min + i vertices
         std::vector<int64_t> offset;         // [n_cliques + 1] with KOMB_MAXIMAL_LISTED: clique i is verts[offset[i], offset[i + 1])
         std::vector<int32_t> verts;          // ascending tuples in lexicographic order
+        bool done = false;
     } mx;
-    bool mx_done = false;
 
     // ---- k-clique communities (clique_communities.hip): computed on the device, kept on the host; they describe the held list
     // of maximal cliques and are dropped with it (maximal_cliques_drop)
@@ -470,8 +511,8 @@ struct komb_ctx {
         std::vector<int64_t> offset;         // [n_comm + 1] community c is verts[offset[c], offset[c + 1]), ascending and distinct
         std::vector<int32_t> verts;
         std::vector<int32_t> v_comm, v_first;   // [nv] the communities through the vertex | the smallest of them (-1)
+        bool done = false;
     } pc;
-    bool pc_done = false;
 
     // ---- k-truss results (canonical order)
     int64_t t_ne = -1;                      // edges of the (sub)graph last run
@@ -496,6 +537,12 @@ struct komb_ctx {
 
     komb_stats stats{};
 };
+
+// what depends on what: the nucleus hierarchy indexes the nucleus result's triangles, the k-clique communities describe the
+// held list of maximal cliques -- either goes with what it was computed from (truss_free in ktruss.hip drops both pairs and
+// the other results of a k-truss result; graph_free in graph_build.hip those of the graph)
+inline void nucleus_drop(komb_ctx *ctx) { ctx->nh = {}; ctx->nuc = {}; }
+inline void maximal_cliques_drop(komb_ctx *ctx) { ctx->pc = {}; ctx->mx = {}; }
 
 // every device allocation outside the pool (the resident graph, the k-core results, the graph build's scratch): hipMalloc,
 // then the POISON fill when that option is set
@@ -684,32 +731,22 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k);   // components.hip:
 int hierarchy_run(komb_ctx *ctx, int32_t kind);               // hierarchy.hip: kind and the results it needs checked by the caller
 int communities_run(komb_ctx *ctx, int32_t k);                // communities.hip: k checked and resolved by the caller
 int communities_vertices(komb_ctx *ctx);                      // communities.hip: n_comm[] and the multi-community count, made on first request
-void communities_drop(komb_ctx *ctx);                         // communities.hip: the result goes with the k-truss result it indexes
 int biconnected_run(komb_ctx *ctx, int32_t k);                // biconnected.hip: k checked and resolved by the caller
-void biconnected_drop(komb_ctx *ctx);                         // biconnected.hip: the result goes with the k-truss result it indexes
 int community_hierarchy_run(komb_ctx *ctx);                   // community_hierarchy.hip: the k-truss result it needs checked by the caller
 int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
-void community_hierarchy_drop(komb_ctx *ctx);                 // community_hierarchy.hip: the result goes with the k-truss result it indexes
 int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu);   // structural.hip: the parameters and the k-truss result it needs checked by the caller
 int structural_fetch_edges(komb_ctx *ctx, int32_t *similar);  // structural.hip: similar[] of the last run as 0 | 1 words (host output)
-void structural_drop(komb_ctx *ctx);                          // structural.hip: the result goes with the k-truss result it indexes
 int nucleus_run(komb_ctx *ctx);                               // nucleus.hip: the k-truss result it needs checked by the caller
-void nucleus_drop(komb_ctx *ctx);                             // nucleus.hip: the result goes with the k-truss result it indexes
 int nucleus_hierarchy_run(komb_ctx *ctx);                     // nucleus_hierarchy.hip: the nucleus result it needs checked by the caller
 int nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
 int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_nuclei, int32_t *rep, int32_t *n_triangles,
                              int32_t *n_edges, int32_t *n_vertices);   // k checked and resolved by the caller; host outputs
-void nucleus_hierarchy_drop(komb_ctx *ctx);                   // nucleus_hierarchy.hip: the result goes with the nucleus result it indexes
 int max_clique_run(komb_ctx *ctx, int64_t budget);            // max_clique.hip: the k-truss result it needs and the budget checked by the caller
-void max_clique_drop(komb_ctx *ctx);                          // max_clique.hip: the result goes with the k-truss result it describes
 // clique_census.hip: the k-truss result it needs, the budget's sign and 2 <= k_lo checked by the caller, the rest of the window here (it needs t_max)
 int clique_census_run(komb_ctx *ctx, int32_t k_lo, int32_t k_hi, int32_t k_local, int64_t budget);
-void clique_census_drop(komb_ctx *ctx);                       // clique_census.hip: the result goes with the k-truss result it describes
 int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget);   // maximal_cliques.hip: the k-truss result it needs, the budget's sign and 2 <= k_min checked by the caller
-void maximal_cliques_drop(komb_ctx *ctx);                     // maximal_cliques.hip: the result goes with the k-truss result it describes
 // clique_communities.hip: the held list of maximal cliques (listed, k_min <= k), 2 <= k and the budget's sign checked by the caller
 int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget);
-void clique_communities_drop(komb_ctx *ctx);                  // clique_communities.hip: the result goes with the maximal cliques it describes
 int densest_run(komb_ctx *ctx, int32_t iters);               // densest.hip: the graph, iters and the k-core result checked by the caller
 int truss_run(komb_ctx *ctx, const uint8_t *vmask_host, int rank, int world, komb_allreduce_fn fn, void *user);
 int merge_run(komb_ctx *ctx, const double *susp_host, int32_t *order, int32_t *side, int64_t *n_block, double *max_density);

@@ -280,29 +280,20 @@ inline uint32_t comm_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dfl
 
 } // namespace
 
-void communities_drop(komb_ctx *ctx)
-{
-    ctx->pool.put(ctx->d_comm_label); ctx->pool.put(ctx->d_comm_size); ctx->pool.put(ctx->d_comm_ncomm);
-    ctx->d_comm_label = ctx->d_comm_size = ctx->d_comm_ncomm = nullptr;
-    ctx->comm_done = ctx->comm_v_ready = false;
-}
-
 // k is checked and resolved by the caller (api.cpp): >= 2
 int communities_run(komb_ctx *ctx, int32_t k)
 {
     hipStream_t s = ctx->stream;
     const int64_t m = ctx->t_ne, nv = ctx->nv;
-    communities_drop(ctx);
-    ctx->comm_k = k;
-    ctx->comm_members = ctx->comm_count = ctx->comm_largest = ctx->comm_multi = 0;
-    ctx->comm_ms = ctx->comm_ms_vertices = 0.0;
-    if (m <= 0) { ctx->comm_done = true; return KOMB_OK; }
+    ctx->comm = {};                                  // a run that fails leaves no result (include/komb_accel.h)
+    komb_ctx::Communities res;                       // goes back to the pool unless it is installed
+    res.k = k;
+    if (m <= 0) { res.done = true; ctx->comm = std::move(res); return KOMB_OK; }
     KOMB_TRY(truss_edges_canonical(ctx));            // (a whole-graph result whose endpoints no fetch has asked for yet)
 
     Range r_all("komb_truss_communities_run");
-    struct Fail { komb_ctx *c; bool armed = true; ~Fail() { if (armed) communities_drop(c); } } fail{ctx};
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_comm_label, (size_t)m * sizeof(int32_t)));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_comm_size, (size_t)m * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.label.slot(&ctx->pool), (size_t)m * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.size.slot(&ctx->pool), (size_t)m * sizeof(int32_t)));
     DevBufs bufs(ctx);
     CommCtl *d_ctl = nullptr;
     uint32_t *d_flag = nullptr, *d_pos = nullptr, *d_rs = nullptr, *d_re = nullptr;
@@ -341,28 +332,28 @@ int communities_run(komb_ctx *ctx, int32_t k)
     k_comm_flatten<true><<<grid, kBlock, 0, s>>>(d_nm, d_parent);
     const int tail_grid = grid < kCommTailGrid ? grid : kCommTailGrid;
     k_comm_count<<<tail_grid, kBlock, 0, s>>>(d_nm, d_parent, d_cnt);
-    k_comm_finish<<<tail_grid, kBlock, 0, s>>>((uint32_t)m, truss, k, d_pos, d_parent, d_kept, d_cnt, ctx->d_comm_label, ctx->d_comm_size, d_ctl);
+    k_comm_finish<<<tail_grid, kBlock, 0, s>>>((uint32_t)m, truss, k, d_pos, d_parent, d_kept, d_cnt, res.label, res.size, d_ctl);
     const double ms = ctx->timer.stop(s);
     KOMB_HIP(ctx, hipGetLastError());
     CommCtl h;
     KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(CommCtl)));
-    ctx->comm_members = (int64_t)h.n_members; ctx->comm_count = (int64_t)h.n_communities; ctx->comm_largest = (int64_t)h.largest;
-    ctx->comm_ms = ms;
-    ctx->comm_done = true;
-    fail.armed = false;
+    res.members = (int64_t)h.n_members; res.count = (int64_t)h.n_communities; res.largest = (int64_t)h.largest;
+    res.ms = ms;
+    res.done = true;
+    ctx->comm = std::move(res);
     return KOMB_OK;
 }
 
 // n_comm[nv] and the number of vertices in more than one community, made by the first fetch_vertices / info after a run
 int communities_vertices(komb_ctx *ctx)
 {
-    if (ctx->comm_v_ready) return KOMB_OK;
+    if (ctx->comm.v_ready) return KOMB_OK;
     hipStream_t s = ctx->stream;
-    const int64_t m = ctx->t_ne, nv = ctx->nv, nm = ctx->comm_members;
-    if (!ctx->d_comm_ncomm) KOMB_HIP(ctx, ctx->pool.get((void **)&ctx->d_comm_ncomm, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
-    ctx->comm_multi = 0;
+    const int64_t m = ctx->t_ne, nv = ctx->nv, nm = ctx->comm.members;
+    if (!ctx->comm.ncomm) KOMB_HIP(ctx, ctx->pool.get((void **)ctx->comm.ncomm.slot(&ctx->pool), (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
+    ctx->comm.multi = 0;
     ctx->timer.start(s);
-    KOMB_HIP(ctx, hipMemsetAsync(ctx->d_comm_ncomm, 0, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t), s));
+    KOMB_HIP(ctx, hipMemsetAsync(ctx->comm.ncomm, 0, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t), s));
     if (nm > 0) {
         Range r_all("komb_truss_communities: vertices");
         DevBufs bufs(ctx);
@@ -375,23 +366,23 @@ int communities_vertices(komb_ctx *ctx)
         KOMB_HIP(ctx, bufs.alloc(&d_keys, 2 * (size_t)nm));
         KOMB_HIP(ctx, bufs.alloc(&d_tmp, 2 * (size_t)nm));
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(CommCtl), s));
-        k_comm_vflag<<<comm_grid(m + 1), kBlock, 0, s>>>(ctx->d_comm_label, (uint32_t)m, d_flag);
+        k_comm_vflag<<<comm_grid(m + 1), kBlock, 0, s>>>(ctx->comm.label, (uint32_t)m, d_flag);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
-        k_comm_keys<<<comm_grid(m), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, ctx->d_comm_label, (uint32_t)m, d_pos, d_keys);
+        k_comm_keys<<<comm_grid(m), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, ctx->comm.label, (uint32_t)m, d_pos, d_keys);
         int vb = 1;
         while (vb < 31 && (1ll << vb) < nv) ++vb;
         KOMB_TRY(prim_sort_u64(ctx, d_keys, d_tmp, 2 * nm, 32 + vb, &sorted));
         uint64_t *uniq = sorted == d_keys ? d_tmp : d_keys;
         int64_t n_u = 0;
         KOMB_TRY(prim_unique_u64(ctx, sorted, uniq, 2 * nm, &n_u));
-        k_comm_runs<<<comm_grid(n_u), kBlock, 0, s>>>(uniq, (uint32_t)n_u, ctx->d_comm_ncomm, d_ctl);
+        k_comm_runs<<<comm_grid(n_u), kBlock, 0, s>>>(uniq, (uint32_t)n_u, ctx->comm.ncomm, d_ctl);
         KOMB_HIP(ctx, hipGetLastError());
         CommCtl h;
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(CommCtl)));
-        ctx->comm_multi = (int64_t)h.n_multi;
+        ctx->comm.multi = (int64_t)h.n_multi;
     }
-    ctx->comm_ms_vertices = ctx->timer.stop(s);
-    ctx->comm_v_ready = true;
+    ctx->comm.ms_vertices = ctx->timer.stop(s);
+    ctx->comm.v_ready = true;
     return KOMB_OK;
 }
 

@@ -261,13 +261,6 @@ inline uint32_t ch_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
 
 } // namespace
 
-void community_hierarchy_drop(komb_ctx *ctx)
-{
-    ctx->pool.put(ctx->d_ch_nodes); ctx->pool.put(ctx->d_ch_enode);
-    ctx->d_ch_nodes = ctx->d_ch_enode = nullptr;
-    ctx->ch_done = false;
-}
-
 // the state it needs is checked by the caller (api.cpp).  The result is built in blocks of its own and replaces the
 // previous one only when the run has succeeded.
 int community_hierarchy_run(komb_ctx *ctx)
@@ -277,15 +270,9 @@ int community_hierarchy_run(komb_ctx *ctx)
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));             // (a whole-graph result whose endpoints no fetch has asked for yet)
 
     Range r_all("komb_community_hierarchy_run");
-    struct Fresh {                                               // the new result: goes back to the pool unless it is installed
-        komb_ctx *c; int32_t *nodes = nullptr, *enode = nullptr;
-        ~Fresh() { c->pool.put(nodes); c->pool.put(enode); }
-    } fresh{ctx};
-    int64_t n_nodes = 0, n_roots = 0, n_members = 0;
-    int32_t k_max = 2, depth = 0;
+    komb_ctx::CommunityHierarchy res;                            // the new result: goes back to the pool unless it is installed
     size_t cap_nodes = 1;
-    double ms = 0.0;
-    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.enode, (size_t)(m > 0 ? m : 1) * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.enode.slot(&ctx->pool), (size_t)(m > 0 ? m : 1) * sizeof(int32_t)));
 
     if (m > 0) {
         DevBufs bufs(ctx);
@@ -398,7 +385,7 @@ int community_hierarchy_run(komb_ctx *ctx)
                 const uint32_t sh_b = moff[k], sh_n = moff[k + 1] - moff[k];
                 const uint32_t r_b = roff[k], r_n = roff[k + 1] - roff[k];
                 if (!sh_n) continue;                                                    // (a record of weight k has an edge of trussness k)
-                if (li == 0) k_max = k;
+                if (li == 0) res.kmax = k;
                 if (r_n) k_ch_link<<<forest_grid(r_n), kBlock, 0, s>>>(recs, r_b, r_n, nm, parent, d_ctl, log, nm);
                 forest_level(ctx, f, k, li, false, mord, sh_b, sh_n, r_n < nm ? r_n : nm);      // at most this many hooks at this level
                 ++li;
@@ -411,30 +398,26 @@ int community_hierarchy_run(komb_ctx *ctx)
             n = h.f.n_nodes;
             if (n > 0) {
                 cap_nodes = n;
-                KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.nodes, 5 * cap_nodes * sizeof(int32_t)));
-                ForestNodes out{fresh.nodes, fresh.nodes + cap_nodes, fresh.nodes + 2 * cap_nodes,
-                                (uint32_t *)fresh.nodes + 3 * cap_nodes, (uint32_t *)fresh.nodes + 4 * cap_nodes};
+                KOMB_HIP(ctx, ctx->pool.get((void **)res.nodes.slot(&ctx->pool), 5 * cap_nodes * sizeof(int32_t)));
+                ForestNodes out{res.nodes, res.nodes + cap_nodes, res.nodes + 2 * cap_nodes,
+                                (uint32_t *)res.nodes.get() + 3 * cap_nodes, (uint32_t *)res.nodes.get() + 4 * cap_nodes};
                 KOMB_TRY(forest_tail(ctx, bufs, f, n, bits, out, rank, kept, mvals, mvals2));    // (the members' sort has served: n <= nm)
             }
-            k_ch_edges_out<<<grid, kBlock, 0, s>>>((uint32_t)m, truss, d_pos, mnode, rank, n, fresh.enode);
+            k_ch_edges_out<<<grid, kBlock, 0, s>>>((uint32_t)m, truss, d_pos, mnode, rank, n, res.enode);
         } else {
-            k_ch_edges_out<<<grid, kBlock, 0, s>>>((uint32_t)m, truss, d_pos, nullptr, nullptr, 0u, fresh.enode);
+            k_ch_edges_out<<<grid, kBlock, 0, s>>>((uint32_t)m, truss, d_pos, nullptr, nullptr, 0u, res.enode);
         }
-        ms = ctx->timer.stop(s);
+        res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(ChCtl)));
-        n_nodes = (int64_t)n; n_roots = (int64_t)h.f.n_roots; depth = h.f.depth; n_members = (int64_t)nm;
-        if (n == 0) k_max = 2;
+        res.n_nodes = (int64_t)n; res.n_roots = (int64_t)h.f.n_roots; res.depth = h.f.depth; res.members = (int64_t)nm;
+        if (n == 0) res.kmax = 2;
     }
-    if (!fresh.nodes) KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.nodes, 5 * cap_nodes * sizeof(int32_t)));
+    if (!res.nodes) KOMB_HIP(ctx, ctx->pool.get((void **)res.nodes.slot(&ctx->pool), 5 * cap_nodes * sizeof(int32_t)));
 
-    community_hierarchy_drop(ctx);
-    ctx->d_ch_nodes = fresh.nodes; ctx->d_ch_enode = fresh.enode;
-    fresh.nodes = fresh.enode = nullptr;
-    ctx->ch_cap = (int64_t)cap_nodes;
-    ctx->ch_nodes = n_nodes; ctx->ch_roots = n_roots; ctx->ch_members = n_members;
-    ctx->ch_kmax = k_max; ctx->ch_depth = depth; ctx->ch_ms = ms;
-    ctx->ch_done = true;
+    res.cap = (int64_t)cap_nodes;
+    res.done = true;
+    ctx->ch = std::move(res);
     return KOMB_OK;
 }
 
@@ -448,9 +431,9 @@ int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t
     int32_t *d_label = nullptr, *d_size = nullptr;
     KOMB_HIP(ctx, bufs.alloc(&d_label, (size_t)m));
     KOMB_HIP(ctx, bufs.alloc(&d_size, (size_t)m));
-    const int32_t *nodes = ctx->d_ch_nodes;
-    const size_t c = (size_t)ctx->ch_cap;
-    k_ch_labels<<<forest_grid(m), kBlock, 0, s>>>((uint32_t)m, k, ctx->d_ch_enode, (uint32_t)ctx->ch_nodes, nodes, nodes + c, nodes + 2 * c,
+    const int32_t *nodes = ctx->ch.nodes;
+    const size_t c = (size_t)ctx->ch.cap;
+    k_ch_labels<<<forest_grid(m), kBlock, 0, s>>>((uint32_t)m, k, ctx->ch.enode, (uint32_t)ctx->ch.n_nodes, nodes, nodes + c, nodes + 2 * c,
                                               nodes + 3 * c, d_label, d_size);
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, hipStreamSynchronize(s));

@@ -253,7 +253,7 @@ void comp_link_rows(komb_ctx *ctx, bool sample, int32_t k, int32_t *parent, cons
     hipStream_t s = ctx->stream;
     const uint32_t nv = (uint32_t)ctx->nv;
     const int grid = comp_grid(nv);
-    const uint32_t *rp = ctx->d_o_rowptr; const int32_t *col = ctx->d_o_col, *core = ctx->d_core;
+    const uint32_t *rp = ctx->d_o_rowptr; const int32_t *col = ctx->d_o_col, *core = ctx->core.core;
     if (sample) {
         k_comp_sample<kAll><<<grid, kBlock, 0, s>>>(rp, col, core, k, nv, parent, flag);
         k_comp_flatten<false><<<grid, kBlock, 0, s>>>(nv, parent, flag);
@@ -273,14 +273,14 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k)
 {
     const int64_t nv = ctx->nv;
     hipStream_t s = ctx->stream;
-    ctx->comp_done = false;
-    if (!ctx->d_comp_label) {
+    ctx->comp.done = false;
+    if (!ctx->comp.label) {
         const size_t bytes = (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t);
-        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_comp_label, bytes, &ctx->d_comp_size, bytes));
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, ctx->comp.label.slot(nullptr), bytes, ctx->comp.size.slot(nullptr), bytes));
     }
-    ctx->comp_kind = kind; ctx->comp_k = k;
-    ctx->comp_members = ctx->comp_count = ctx->comp_largest = 0; ctx->comp_ms = 0.0;
-    if (nv == 0) { ctx->comp_done = true; return KOMB_OK; }
+    ctx->comp.kind = kind; ctx->comp.k = k;
+    ctx->comp.members = ctx->comp.count = ctx->comp.largest = 0; ctx->comp.ms = 0.0;
+    if (nv == 0) { ctx->comp.done = true; return KOMB_OK; }
 
     const bool truss = kind == KOMB_COMP_TRUSS;
     const int64_t m = truss ? ctx->t_ne : 0;
@@ -296,14 +296,14 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k)
     const char *so = ctx_opt(ctx, "COMP_SAMPLE");
     const bool sample = so ? strcmp(so, "0") != 0 : true;
 
-    int32_t *parent = ctx->d_comp_label, *flag = ctx->d_comp_size;
+    int32_t *parent = ctx->comp.label, *flag = ctx->comp.size;
     const int grid = comp_grid(nv);
     const bool all = !truss && k == 0;
     // (core kind above the largest coreness: nobody is a member, and nothing is linked)
     const bool none = truss || (k > 0 && k > ctx->stats.max_coreness);
     ctx->timer.start(s);
     KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(CompCtl), s));
-    k_comp_init<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->d_core, k, all, none, parent, flag, d_cnt);
+    k_comp_init<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->core.core, k, all, none, parent, flag, d_cnt);
     if (truss) {
         if (m > 0) k_comp_truss<<<comp_grid(m), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, ctx->d_t_truss, (uint32_t)m, k, parent, flag);
     } else if (!none && ctx->ne > 0) {
@@ -316,14 +316,14 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k)
     k_comp_flatten<true><<<grid, kBlock, 0, s>>>((uint32_t)nv, parent, flag);
     const int tail_grid = grid < kCompTailGrid ? grid : kCompTailGrid;
     k_comp_count<<<tail_grid, kBlock, 0, s>>>((uint32_t)nv, parent, d_cnt);
-    k_comp_finish<<<tail_grid, kBlock, 0, s>>>((uint32_t)nv, parent, d_cnt, ctx->d_comp_size, d_ctl);
+    k_comp_finish<<<tail_grid, kBlock, 0, s>>>((uint32_t)nv, parent, d_cnt, ctx->comp.size, d_ctl);
     const double ms = ctx->timer.stop(s);
     KOMB_HIP(ctx, hipGetLastError());
     CompCtl h;
     KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(CompCtl)));
-    ctx->comp_members = (int64_t)h.n_members; ctx->comp_count = (int64_t)h.n_components; ctx->comp_largest = (int64_t)h.largest;
-    ctx->comp_ms = ms;
-    ctx->comp_done = true;
+    ctx->comp.members = (int64_t)h.n_members; ctx->comp.count = (int64_t)h.n_components; ctx->comp.largest = (int64_t)h.largest;
+    ctx->comp.ms = ms;
+    ctx->comp.done = true;
     return KOMB_OK;
 }
 

@@ -489,18 +489,17 @@ int densest_run(komb_ctx *ctx, int32_t iters)
 {
     const int64_t nv = ctx->nv;
     hipStream_t s = ctx->stream;
-    if (!ctx->d_dens_member) {                               // the result's own arrays: pool blocks, kept until the graph goes
-        void *a = nullptr, *b = nullptr;
-        KOMB_HIP(ctx, ctx->pool.get(&a, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
-        const hipError_t e = ctx->pool.get(&b, (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t));
-        if (e != hipSuccess) { ctx->pool.put(a); KOMB_HIP(ctx, e); }
-        ctx->d_dens_member = (int32_t *)a; ctx->d_dens_load = (int32_t *)b;
+    if (!ctx->dens.member) {                                 // the result's own arrays: pool blocks, kept until the graph goes
+        DevArr<int32_t> a, b;                                // (both or neither)
+        KOMB_HIP(ctx, ctx->pool.get((void **)a.slot(&ctx->pool), (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
+        KOMB_HIP(ctx, ctx->pool.get((void **)b.slot(&ctx->pool), (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t)));
+        ctx->dens.member = std::move(a); ctx->dens.load = std::move(b);
     }
     if (nv == 0) {
-        ctx->dens = komb_ctx::Densest{};
-        ctx->dens.iters = iters;
-        ctx->dens_profile.assign(2, 0);
-        ctx->dens_done = true;
+        komb_ctx::Densest r;                                 // an empty summary on the arrays the context holds
+        r.member = std::move(ctx->dens.member); r.load = std::move(ctx->dens.load);
+        r.iters = iters; r.profile.assign(2, 0); r.done = true;
+        ctx->dens = std::move(r);
         return KOMB_OK;
     }
 
@@ -531,12 +530,12 @@ int densest_run(komb_ctx *ctx, int32_t iters)
     KOMB_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)2 * K * sizeof(uint32_t), s));
     KOMB_HIP(ctx, hipMemsetAsync(d_hdeg, 0, (size_t)heavy_cap * sizeof(uint32_t), s));
     KOMB_HIP(ctx, hipMemsetAsync(d_hcur, 0, (size_t)heavy_cap * sizeof(uint32_t), s));
-    if (K <= kDenLdsBins) den_row_pass(ctx, DenHist<true>{ctx->d_core, K, d_hist}, (size_t)2 * K * sizeof(uint32_t), d_ctl, d_heavy, heavy_cap);
-    else den_row_pass(ctx, DenHist<false>{ctx->d_core, K, d_hist}, 0, d_ctl, d_heavy, heavy_cap);
+    if (K <= kDenLdsBins) den_row_pass(ctx, DenHist<true>{ctx->core.core, K, d_hist}, (size_t)2 * K * sizeof(uint32_t), d_ctl, d_heavy, heavy_cap);
+    else den_row_pass(ctx, DenHist<false>{ctx->core.core, K, d_hist}, 0, d_ctl, d_heavy, heavy_cap);
     k_den_profile<<<1, kBlock, 0, s>>>(K, d_hist, d_prof, d_prof + K, d_ctl);
-    k_den_mark<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->d_core, d_ctl, d_flag);
+    k_den_mark<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->core.core, d_ctl, d_flag);
     KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pid, nv));
-    den_row_pass(ctx, DenCount{ctx->d_core, d_cnt, d_hdeg, 0u, 0u, 0u}, 0, d_ctl, d_heavy, heavy_cap);
+    den_row_pass(ctx, DenCount{ctx->core.core, d_cnt, d_hdeg, 0u, 0u, 0u}, 0, d_ctl, d_heavy, heavy_cap);
     KOMB_TRY(prim_exclusive_sum_u32(ctx, d_cnt, d_off, nv));
     k_den_total<<<1, kBlock, 0, s>>>((uint32_t)nv, d_flag, d_pid, d_cnt, d_off, d_hdeg, heavy_cap, d_ctl);
     double ms = ctx->timer.stop(s);
@@ -581,7 +580,7 @@ int densest_run(komb_ctx *ctx, int32_t iters)
     }
     ctx->timer.start(s);
     if (rounds) {
-        den_row_pass(ctx, DenFill{ctx->d_core, d_pid, d_off, d_pairs, d_hcur, m_p, 0u}, 0, d_ctl, d_heavy, heavy_cap);
+        den_row_pass(ctx, DenFill{ctx->core.core, d_pid, d_off, d_pairs, d_hcur, m_p, 0u}, 0, d_ctl, d_heavy, heavy_cap);
         if (local) {
             k_den_local<<<1, kDenLocalBlock, (size_t)n_p * 2 * sizeof(uint32_t), s>>>(d_pairs, (uint32_t)m_p, (uint32_t)n_p, iters, d_load);
         } else {
@@ -604,17 +603,17 @@ int densest_run(komb_ctx *ctx, int32_t iters)
     k_den_decide<<<1, kWave, 0, s>>>(rounds ? (uint32_t)part_grid : 0u, d_part, d_ctl);
     KOMB_HIP(ctx, hipGetLastError());
     // from here on the previous result is overwritten
-    k_den_out<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->d_core, d_pid, d_load, d_rank, d_ctl, ctx->d_dens_member, ctx->d_dens_load);
+    k_den_out<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->core.core, d_pid, d_load, d_rank, d_ctl, ctx->dens.member, ctx->dens.load);
     ms += ctx->timer.stop(s);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = d2h(ctx, &h, d_ctl, sizeof(DenCtl));
-    if (e != hipSuccess) { ctx->dens_done = false; KOMB_HIP(ctx, e); }
+    if (e != hipSuccess) { ctx->dens.done = false; KOMB_HIP(ctx, e); }
     komb_ctx::Densest &r = ctx->dens;
     r.source = h.source; r.k_best = h.k_best; r.k_prune = h.k_prune; r.iters = iters; r.k_max = k_max;
     r.n_pruned = (int64_t)n_p; r.m_pruned = (int64_t)m_p; r.n_sub = (int64_t)h.n_sub; r.m_sub = (int64_t)h.m_sub;
     r.load_max = (int64_t)h.load_max; r.ms = ms; r.local = local;
-    ctx->dens_profile.swap(profile);
-    ctx->dens_done = true;
+    r.profile.swap(profile);
+    r.done = true;
     return KOMB_OK;
 }
 

@@ -286,24 +286,19 @@ void warm_up(komb_ctx *ctx)
 
 void graph_free(komb_ctx *ctx)
 {
-    void *all[] = {ctx->d_o_rowptr, ctx->d_o_col, ctx->d_deg, ctx->d_core, ctx->d_onion_layer, ctx->d_onion_core,
-                   ctx->d_comp_label, ctx->d_comp_size, ctx->d_hier_nodes, ctx->d_hier_vnode};
     truss_free(ctx);
     prep_free(ctx, &ctx->prep);
-    for (void *p : all) if (p) (void)hipFree(p);
-    ctx->d_o_rowptr = nullptr; ctx->d_o_col = nullptr; ctx->d_deg = nullptr; ctx->d_core = nullptr;
-    ctx->d_onion_layer = nullptr; ctx->d_onion_core = nullptr;
-    ctx->d_comp_label = nullptr; ctx->d_comp_size = nullptr; ctx->comp_done = false;
-    ctx->d_hier_nodes = nullptr; ctx->d_hier_vnode = nullptr; ctx->hier_done = false;
-    ctx->nv = -1; ctx->ne = 0; ctx->core_done = false; ctx->onion_done = false;
+    // the results with the graph's lifetime (those of a k-truss result went with truss_free)
+    ctx->core = {}; ctx->onion = {}; ctx->comp = {}; ctx->hier = {}; ctx->dens = {};
+    if (ctx->d_o_rowptr) (void)hipFree(ctx->d_o_rowptr);
+    if (ctx->d_o_col) (void)hipFree(ctx->d_o_col);
+    ctx->d_o_rowptr = nullptr; ctx->d_o_col = nullptr;
+    ctx->nv = -1; ctx->ne = 0;
     ctx->cap_hint.nv = -1; ctx->cap_hint.m = -1;
     if (ctx->d_ceu) ctx->pool.put(ctx->d_ceu);
     if (ctx->d_cev) ctx->pool.put(ctx->d_cev);
     ctx->d_ceu = ctx->d_cev = nullptr;
-    if (ctx->d_dens_member) ctx->pool.put(ctx->d_dens_member);
-    if (ctx->d_dens_load) ctx->pool.put(ctx->d_dens_load);
-    ctx->d_dens_member = ctx->d_dens_load = nullptr; ctx->dens_done = false;
-    ctx->pool.clear();                                   // scratch sized for the old graph
+    ctx->pool.clear();                                   // scratch sized for the old graph; no record holds a block of it any more
 }
 
 int graph_from_edges(komb_ctx *ctx, int64_t nv, int64_t n_raw, const int64_t *uv)

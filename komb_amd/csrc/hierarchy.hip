@@ -173,14 +173,14 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
     hipStream_t s = ctx->stream;
     const bool truss = kind == KOMB_COMP_TRUSS;
     const size_t cap = (size_t)(nv > 0 ? nv : 1);            // nodes <= vertices (forest.hip)
-    if (!ctx->d_hier_nodes)
-        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_hier_nodes, 5 * cap * sizeof(int32_t), &ctx->d_hier_vnode, cap * sizeof(int32_t)));
+    if (!ctx->hier.nodes)
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, ctx->hier.nodes.slot(nullptr), 5 * cap * sizeof(int32_t), ctx->hier.vnode.slot(nullptr), cap * sizeof(int32_t)));
     // The result arrays are written by the last kernels of the run only, behind every allocation of the run, and the figures
     // are installed at the end: a run that fails for memory leaves the previous result readable (include/komb_accel.h).
     if (nv == 0) {
-        ctx->hier_kind = kind; ctx->hier_nodes = ctx->hier_roots = 0; ctx->hier_depth = 0; ctx->hier_ms = 0.0;
-        ctx->hier_kmax = truss ? 2 : 0;
-        ctx->hier_done = true;
+        ctx->hier.kind = kind; ctx->hier.n_nodes = ctx->hier.n_roots = 0; ctx->hier.depth = 0; ctx->hier.ms = 0.0;
+        ctx->hier.kmax = truss ? 2 : 0;
+        ctx->hier.done = true;
         return KOMB_OK;
     }
 
@@ -242,7 +242,7 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
         forest_offsets(ctx, (uint32_t)m, sorted_keys, levels, d_second);
         k_hier_keys_lvl<<<grid, kBlock, 0, s>>>((uint32_t)nv, lvl, vkeys, vvals);
     } else {
-        k_hier_keys_core<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->d_core, ctx->d_o_rowptr, levels, vkeys, vvals, d_second);
+        k_hier_keys_core<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->core.core, ctx->d_o_rowptr, levels, vkeys, vvals, d_second);
     }
     KOMB_TRY(prim_sort_pairs_u32_u32(ctx, vkeys, vkeys2, vvals, vvals2, nv, bits, &sorted_keys, &vord));
     forest_offsets(ctx, (uint32_t)nv, sorted_keys, levels, d_voff);
@@ -274,11 +274,11 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
             hooks = e_n < (uint64_t)nv ? e_n : (uint64_t)nv;
         } else {
             if (k > 0) {                                     // (coreness 0: no row has an entry)
-                k_hier_rows<<<forest_grid(sh_n), kBlock, 0, s>>>(ctx->d_o_rowptr, ctx->d_o_col, ctx->d_core, k, vord, sh_b, sh_n, parent, d_ctl,
+                k_hier_rows<<<forest_grid(sh_n), kBlock, 0, s>>>(ctx->d_o_rowptr, ctx->d_o_col, ctx->core.core, k, vord, sh_b, sh_n, parent, d_ctl,
                                                                d_heavy, heavy_cap, log, (uint32_t)nv);
                 if (second[k])
                     k_hier_heavy<<<dim3(second[k] < (uint32_t)kHierHeavyGrid ? second[k] : kHierHeavyGrid, kHierHeavyChunks), kBlock, 0, s>>>(
-                        ctx->d_o_rowptr, ctx->d_o_col, ctx->d_core, k, parent, d_ctl, d_heavy, heavy_done, second[k], heavy_cap, log, (uint32_t)nv);
+                        ctx->d_o_rowptr, ctx->d_o_col, ctx->core.core, k, parent, d_ctl, d_heavy, heavy_done, second[k], heavy_cap, log, (uint32_t)nv);
                 heavy_done += second[k];
             }
             hooks = (uint64_t)nv - voff[k];                  // the vertices of coreness >= k
@@ -295,20 +295,20 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
         KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_hierarchy_run: inconsistent state (%u long rows queued, %u counted)", h.n_heavy, heavy_done);
     const uint32_t n = h.f.n_nodes;
 
-    ForestNodes out{ctx->d_hier_nodes, ctx->d_hier_nodes + cap, ctx->d_hier_nodes + 2 * cap,
-                    (uint32_t *)ctx->d_hier_nodes + 3 * cap, (uint32_t *)ctx->d_hier_nodes + 4 * cap};
+    ForestNodes out{ctx->hier.nodes, ctx->hier.nodes + cap, ctx->hier.nodes + 2 * cap,
+                    (uint32_t *)ctx->hier.nodes.get() + 3 * cap, (uint32_t *)ctx->hier.nodes.get() + 4 * cap};
     int32_t *rank = cur;                                      // (cur[] has served; n <= nv)
     if (n > 0) KOMB_TRY(forest_tail(ctx, bufs, f, n, bits, out, rank, nullptr, vvals, vvals2));   // (the vertices' sort has served: n <= nv)
-    ctx->hier_done = false;                                   // from here on the previous result is being overwritten
-    k_hier_vertices_out<<<grid, kBlock, 0, s>>>((uint32_t)nv, vnode, rank, ctx->d_hier_vnode);
+    ctx->hier.done = false;                                   // from here on the previous result is being overwritten
+    k_hier_vertices_out<<<grid, kBlock, 0, s>>>((uint32_t)nv, vnode, rank, ctx->hier.vnode);
     const double ms = ctx->timer.stop(s);
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(HierCtl)));
-    ctx->hier_kind = kind;
-    ctx->hier_nodes = (int64_t)n; ctx->hier_roots = (int64_t)h.f.n_roots; ctx->hier_depth = h.f.depth;
-    ctx->hier_kmax = n > 0 ? k_top : k_min;
-    ctx->hier_ms = ms;
-    ctx->hier_done = true;
+    ctx->hier.kind = kind;
+    ctx->hier.n_nodes = (int64_t)n; ctx->hier.n_roots = (int64_t)h.f.n_roots; ctx->hier.depth = h.f.depth;
+    ctx->hier.kmax = n > 0 ? k_top : k_min;
+    ctx->hier.ms = ms;
+    ctx->hier.done = true;
     return KOMB_OK;
 }
 

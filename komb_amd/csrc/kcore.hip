@@ -244,10 +244,10 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
     if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_STATE, "komb_core_run: no graph loaded");
     const int64_t nv = ctx->nv;
     hipStream_t s = ctx->stream;
-    ctx->core_done = false;
-    if (!ctx->d_deg) {
+    ctx->core.done = false;
+    if (!ctx->core.deg) {
         const size_t bytes = (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t);
-        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_deg, bytes, &ctx->d_core, bytes));
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, ctx->core.deg.slot(nullptr), bytes, ctx->core.core.slot(nullptr), bytes));
     }
     komb_stats &stt = ctx->stats;
     stt.core_levels = stt.core_subrounds = stt.core_launches = 0;
@@ -256,7 +256,7 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
     if (ctx_flag(ctx, "SHARD_ENGINE")) sharded = true;          // (one rank: the sharded engine without a collective -- a test of its logic)
     stt.shard_exchanges = 0; stt.ms_exchange = 0.0; stt.exchange_words = 0;
     stt.engine_flags = sharded ? KOMB_ENGINE_SHARD_PEEL : 0;
-    if (nv == 0) { ctx->core_done = true; return KOMB_OK; }
+    if (nv == 0) { ctx->core.done = true; return KOMB_OK; }
 
     Range r_all("komb_core_run");
     DevBufs bufs(ctx);
@@ -297,10 +297,10 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
     int64_t g = (nv + kBlock - 1) / kBlock;
     const int grid_init = (int)(g > 1024 ? 1024 : g);
     const int grid = peel_grid(nv);
-    CoreProblem P{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, d_degw, ctx->d_core};
+    CoreProblem P{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, d_degw, ctx->core.core};
     ctx->timer.start(s);
     peel_ctrl_pre(s, d_grp);
-    k_core_init<<<grid_init, kBlock, 0, s>>>(ctx->d_o_rowptr, nv, ctx->d_deg, d_degw, ctx->d_core, d_grp + kInitOff);
+    k_core_init<<<grid_init, kBlock, 0, s>>>(ctx->d_o_rowptr, nv, ctx->core.deg, d_degw, ctx->core.core, d_grp + kInitOff);
     peel_ctrl_init(s, d_ctrl, d_grp, (uint32_t)nv, tail_limit);
     // LDS tail: the live vertices are those of `list` (or all nv when list is null) whose core[] is still an alive marker
     auto run_tail = [&](const int32_t *list, uint32_t n_in) -> int {
@@ -308,9 +308,9 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
         KOMB_HIP(ctx, hipMemsetAsync(T.cnt, 0, 4 * sizeof(uint32_t), s));
         KOMB_HIP(ctx, hipMemsetAsync(T.rows, 0, (size_t)kCoreTailV * kCoreTailWords * sizeof(unsigned long long), s));
         int64_t gm = ((int64_t)n_in + kBlock - 1) / kBlock;
-        k_ctail_mark<<<(int)(gm < 1 ? 1 : (gm > 1024 ? 1024 : gm)), kBlock, 0, s>>>(list, n_in, ctx->d_core, T);
+        k_ctail_mark<<<(int)(gm < 1 ? 1 : (gm > 1024 ? 1024 : gm)), kBlock, 0, s>>>(list, n_in, ctx->core.core, T);
         k_ctail_rows<<<dim3(kCoreTailV, 8), kBlock, 0, s>>>(ctx->d_o_rowptr, ctx->d_o_col, T);
-        k_core_tail<false><<<1, 1024, 0, s>>>(d_ctrl, T, d_degw, ctx->d_core, nullptr);
+        k_core_tail<false><<<1, 1024, 0, s>>>(d_ctrl, T, d_degw, ctx->core.core, nullptr);
         KOMB_HIP(ctx, d2h(ctx, &ctx->h_ctrl[0], d_ctrl, sizeof(PeelCtrl)));
         return KOMB_OK;
     };
@@ -324,10 +324,10 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
         (void)hipEventRecord(ev[0], s);
         KOMB_HIP(ctx, hipMemsetAsync(d_livebits, 0, live_words * sizeof(unsigned long long), s));
         LocalStats ls;
-        const int rc = local_finish(ctx, bufs, hc, d_ctrl, (uint32_t)nv, ctx->d_core, d_degw, Q.live[hc.live_sel],
-            (uint32_t)kWave * CoreLocal::kU, sizeof(uint32_t), local_item_limit(ctx, std::max<uint64_t>(kCoreLocalItems, (uint64_t)ctx->ne / 3)), 0u, false, 0, ctx->d_core,
+        const int rc = local_finish(ctx, bufs, hc, d_ctrl, (uint32_t)nv, ctx->core.core, d_degw, Q.live[hc.live_sel],
+            (uint32_t)kWave * CoreLocal::kU, sizeof(uint32_t), local_item_limit(ctx, std::max<uint64_t>(kCoreLocalItems, (uint64_t)ctx->ne / 3)), 0u, false, 0, ctx->core.core,
             [&](const LocalGraph &lg, const int32_t *num, void *items, PeelCtrl *d_cctrl, int32_t launch) {
-                CoreCollect C{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, ctx->d_core, d_livebits, num, lg.off, lg.cur, (uint32_t *)items};
+                CoreCollect C{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, ctx->core.core, d_livebits, num, lg.off, lg.cur, (uint32_t *)items};
                 k_peel_step<CoreCollect><<<grid, kPeelBlock, 0, s>>>(d_cctrl, d_grp, Q, C, launch);
             },
             [&](const LocalGraph &lg, void *items, uint64_t total, LocalCtrl *d_lctrl, uint32_t *d_cnt, int *launches) -> int {
@@ -356,7 +356,7 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
         // local finish under the replicated peel's rule, after one exchange of the live degrees (shard_dev.h)
         uint32_t iw[2] = {0u, 0u};
         KOMB_HIP(ctx, d2h(ctx, iw, d_grp + kInitOff, sizeof(iw)));     // isolated vertices; the smallest positive degree
-        ShardCore SP{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, d_degw, ctx->d_core, 0u, 0u};
+        ShardCore SP{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, d_degw, ctx->core.core, 0u, 0u};
         shard_bounds((uint64_t)nv, rank, world, &SP.lo, &SP.hi);
         ShardStats ss;
         st = shard_peel(ctx, bufs, SP, d_degw, (uint32_t)nv, iw[0], (int32_t)iw[1], rank, world, fn, user, Q, d_ctrl,
@@ -404,7 +404,7 @@ int core_run(komb_ctx *ctx, int rank, int world, komb_allreduce_fn fn, void *use
     stt.core_subrounds = ctx->h_ctrl[0].n_rounds;
     stt.core_launches = launches;
     stt.max_coreness = ctx->h_ctrl[0].max_level;
-    ctx->core_done = true;
+    ctx->core.done = true;
     return KOMB_OK;
 }
 

@@ -277,14 +277,14 @@ struct TrussLocal {
 
 void truss_free(komb_ctx *ctx)
 {
-    communities_drop(ctx);                   // (its labels index this result's canonical edges)
-    community_hierarchy_drop(ctx);           // (so do the community hierarchy's reps and node[])
-    biconnected_drop(ctx);                   // (and the blocks' reps and block[])
-    structural_drop(ctx);                    // (and the structural clustering's similar[]; its d and sim_deg are this result's)
-    nucleus_drop(ctx);                       // (and the nucleus decomposition's triangles and edge_theta[])
-    max_clique_drop(ctx);                    // (and the maximum cliques: they are this result's)
-    clique_census_drop(ctx);                 // (and the clique census)
-    maximal_cliques_drop(ctx);               // (and the maximal cliques)
+    ctx->comm = {};                          // (its labels index this result's canonical edges)
+    ctx->ch = {};                            // (so do the community hierarchy's reps and node[])
+    ctx->bc = {};                            // (and the blocks' reps and block[])
+    ctx->sc = {};                            // (and the structural clustering's similar[]; its d and sim_deg are this result's)
+    nucleus_drop(ctx);                       // (and the nucleus decomposition's triangles and edge_theta[], with its hierarchy)
+    ctx->mc = {};                            // (and the maximum cliques: they are this result's)
+    ctx->cc = {};                            // (and the clique census)
+    maximal_cliques_drop(ctx);               // (and the maximal cliques, with their k-clique communities)
     if (ctx->t_own_edges) { ctx->pool.put(ctx->d_t_eu); ctx->pool.put(ctx->d_t_ev); }
     ctx->pool.put(ctx->d_t_truss);
     ctx->pool.put(ctx->d_t_sup);

@@ -231,14 +231,6 @@ int McRun::launch(int mode, uint32_t need, int grid_cap)
 
 } // namespace
 
-void max_clique_drop(komb_ctx *ctx)
-{
-    ctx->pool.put(ctx->d_mc_count);
-    ctx->d_mc_count = nullptr;
-    ctx->mc = komb_ctx::MaxClique{};
-    ctx->mc_done = false;
-}
-
 // the k-truss result it needs and the budget's sign are checked by the caller (api.cpp).  The result is built on the side and
 // replaces the previous one only when the run has succeeded.
 int max_clique_run(komb_ctx *ctx, int64_t budget)
@@ -247,12 +239,11 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
     const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv > 0 ? ctx->nv : 0;
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
     Range r_all("komb_max_clique_run");
-    struct Fresh { komb_ctx *c; int32_t *count; ~Fresh() { c->pool.put(count); } } fresh{ctx, nullptr};
-    komb_ctx::MaxClique res;
+    komb_ctx::MaxClique res;                             // goes back to the pool unless it is installed
     const long long limit = budget == 0 ? kClqDefaultBudget : std::min<long long>(budget, kClqMaxBudget);
     const bool seed = !ctx_opt(ctx, "MAXCLQ_SEED") || ctx_flag(ctx, "MAXCLQ_SEED");
     const long long list_cap = clq_opt(ctx, "MAXCLQ_LIST", kMcListDefault, 0, 1ll << 24);
-    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.count, (size_t)nv * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.count.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
     DevBufs bufs(ctx);
     EventSet evs;
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
@@ -261,7 +252,7 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
     bool timed = false;
 
     ctx->timer.start(s);
-    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.count, 0, (size_t)nv * sizeof(int32_t), s));
+    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(res.count, 0, (size_t)nv * sizeof(int32_t), s));
     if (m == 0) {                                        // no edge: omega = 0, nothing to list, all of it proven
         res.flags = KOMB_MAXCLQ_EXACT | KOMB_MAXCLQ_ENUMERATED | KOMB_MAXCLQ_LISTED;
         res.n_max = 0;
@@ -320,7 +311,7 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
         bool enumerated = false;
         if (exact && !run.h.stopped) {
             A.omega = omega;
-            A.count = fresh.count;
+            A.count = res.count;
             A.list_cap = (unsigned long long)list_cap;
             KOMB_HIP(ctx, bufs.alloc(&A.list, (size_t)list_cap * omega));
             KOMB_TRY(run.launch(MC_ENUM, omega, kClqGrid));
@@ -347,8 +338,8 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
             }
         } else {                                         // the counts are the witness' own
             res.n_max = -1;
-            KOMB_HIP(ctx, hipMemsetAsync(fresh.count, 0, (size_t)nv * sizeof(int32_t), s));
-            k_mc_mark<<<(int)((omega + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_wit, omega, fresh.count);
+            KOMB_HIP(ctx, hipMemsetAsync(res.count, 0, (size_t)nv * sizeof(int32_t), s));
+            k_mc_mark<<<(int)((omega + kBlock - 1) / kBlock), kBlock, 0, s>>>(d_wit, omega, res.count);
             KOMB_HIP(ctx, hipGetLastError());
         }
         (void)hipEventRecord(e3, s);
@@ -366,11 +357,8 @@ int max_clique_run(komb_ctx *ctx, int64_t budget)
                 res.upper, res.flags, (long long)res.n_max, (long long)res.n_roots, (unsigned long long)nodes_seed, (unsigned long long)nodes_search,
                 (unsigned long long)((uint64_t)res.nodes - nodes_seed - nodes_search), limit, res.ms, f[0], f[1], f[2]);
     }
-    max_clique_drop(ctx);
-    ctx->d_mc_count = fresh.count;
-    fresh.count = nullptr;
+    res.done = true;
     ctx->mc = std::move(res);
-    ctx->mc_done = true;
     return KOMB_OK;
 }
 

@@ -243,15 +243,6 @@ bool mx_sort_list(const std::vector<int32_t> &raw, size_t n, std::vector<int64_t
 
 } // namespace
 
-void maximal_cliques_drop(komb_ctx *ctx)
-{
-    clique_communities_drop(ctx);                        // (and the k-clique communities: they are this list's)
-    ctx->pool.put(ctx->d_mx_count);
-    ctx->d_mx_count = nullptr;
-    ctx->mx = komb_ctx::MaximalCliques{};
-    ctx->mx_done = false;
-}
-
 // the k-truss result it needs, the budget's sign and 2 <= k_min are checked by the caller (api.cpp).  The result is built on the
 // side and replaces the previous one only when the run has succeeded.
 int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
@@ -260,19 +251,18 @@ int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
     const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv > 0 ? ctx->nv : 0;
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
     Range r_all("komb_maximal_cliques_run");
-    struct Fresh { komb_ctx *c; int32_t *count; ~Fresh() { c->pool.put(count); } } fresh{ctx, nullptr};
-    komb_ctx::MaximalCliques res;
+    komb_ctx::MaximalCliques res;                        // goes back to the pool unless it is installed
     const long long limit = budget == 0 ? kClqDefaultBudget : std::min<long long>(budget, kClqMaxBudget);
     const long long list_cap = clq_opt(ctx, "MAXIMAL_LIST", kMxListDefault, 0, kMxListMax);
     DevBufs bufs(ctx);
     ClqCtl h{};
     MxArgs A{};
     KOMB_HIP(ctx, bufs.alloc(&A.ctl, 1));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.count, (size_t)std::max<int64_t>(2 * nv, 1) * sizeof(int32_t)));   // count[nv] | largest[nv]
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.count.slot(&ctx->pool), (size_t)std::max<int64_t>(2 * nv, 1) * sizeof(int32_t)));   // count[nv] | largest[nv]
 
     ctx->timer.start(s);
     KOMB_HIP(ctx, hipMemsetAsync(A.ctl, 0, sizeof(ClqCtl), s));
-    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.count, 0, (size_t)(2 * nv) * sizeof(int32_t), s));
+    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(res.count, 0, (size_t)(2 * nv) * sizeof(int32_t), s));
     const uint32_t um = (uint32_t)m;
     if (m > 0) KOMB_TRY(clq_tmax(ctx, "komb_maximal_cliques_run", A.ctl, 0u, &h));
     const int32_t t_max = (int32_t)h.t_max;
@@ -310,7 +300,7 @@ int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
         const char *pv = ctx_opt(ctx, "MAXIMAL_PIVOT");
         A.pivot_max = !(pv && strcmp(pv, "first") == 0);
         A.budget = (unsigned long long)limit;
-        A.count = fresh.count; A.largest = fresh.count + nv;
+        A.count = res.count; A.largest = res.count + nv;
         // ---- the largest |X| + |P| at need k_min
         A.count_only = true;
         const int count_grid = (int)std::min<uint32_t>(A.n_chunks, (uint32_t)kClqGrid);
@@ -362,11 +352,9 @@ int maximal_cliques_run(komb_ctx *ctx, int32_t k_min, int64_t budget)
         fprintf(stderr, "komb maximal cliques: %lld edges, t_max %d, k_min %d, omega %d, flags %d, %lld cliques, largest candidate list %d, %lld roots, "
                 "%lld nodes of %lld, run %.3f ms\n", (long long)m, res.t_max, res.k_min, res.omega, res.flags, (long long)res.n_cliques, res.max_q,
                 (long long)res.n_roots, (long long)res.nodes, limit, res.ms);
-    maximal_cliques_drop(ctx);
-    ctx->d_mx_count = fresh.count;
-    fresh.count = nullptr;
+    ctx->pc = {};                            // (the k-clique communities describe the list that goes)
+    res.done = true;
     ctx->mx = std::move(res);
-    ctx->mx_done = true;
     return KOMB_OK;
 }
 

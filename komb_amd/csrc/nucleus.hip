@@ -416,27 +416,7 @@ inline uint32_t nuc_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt
     return v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
 }
 
-struct NucBlocks {                          // the arrays of one result: pool blocks
-    int32_t *a = nullptr, *b = nullptr, *c = nullptr, *key0 = nullptr, *theta = nullptr, *edge = nullptr, *vertex = nullptr;
-};
-
-void nuc_put(komb_ctx *ctx, NucBlocks &b)
-{
-    ctx->pool.put(b.a); ctx->pool.put(b.b); ctx->pool.put(b.c); ctx->pool.put(b.key0); ctx->pool.put(b.theta);
-    ctx->pool.put(b.edge); ctx->pool.put(b.vertex);
-    b = NucBlocks{};
-}
-
 } // namespace
-
-void nucleus_drop(komb_ctx *ctx)
-{
-    nucleus_hierarchy_drop(ctx);             // (the nuclei and their forest index this result's triangles)
-    NucBlocks b{ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_nuc_key0, ctx->d_nuc_theta, ctx->d_nuc_edge, ctx->d_nuc_vertex};
-    nuc_put(ctx, b);
-    ctx->d_nuc_a = ctx->d_nuc_b = ctx->d_nuc_c = ctx->d_nuc_key0 = ctx->d_nuc_theta = ctx->d_nuc_edge = ctx->d_nuc_vertex = nullptr;
-    ctx->nuc_done = false;
-}
 
 // the k-truss result it needs is checked by the caller (api.cpp).  The result is built in blocks of its own and replaces the
 // previous one only when the run has succeeded.
@@ -446,8 +426,7 @@ int nucleus_run(komb_ctx *ctx)
     const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv > 0 ? ctx->nv : 0;
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
     Range r_all("komb_nucleus_run");
-    struct Fresh { komb_ctx *c; NucBlocks b; ~Fresh() { nuc_put(c, b); } } fresh{ctx};   // goes back to the pool unless it is installed
-    komb_ctx::Nucleus res;
+    komb_ctx::Nucleus res;                               // goes back to the pool unless it is installed
     const uint32_t n_short = nuc_opt_u32(ctx, "NUC_SHORT", kNucShort);       // (tests: every unit through the wave / the queued path)
     uint32_t n_heavy = nuc_opt_u32(ctx, "NUC_HEAVY", kNucHeavy);
     if (n_heavy <= n_short) n_heavy = n_short + 1;
@@ -456,8 +435,8 @@ int nucleus_run(komb_ctx *ctx)
 
     const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev;
     const uint32_t um = (uint32_t)m;
-    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.edge, (size_t)m * sizeof(int32_t)));
-    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.vertex, (size_t)nv * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.edge.slot(&ctx->pool), (size_t)m * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.vertex.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
     DevBufs bufs(ctx);
     EventSet evs;
     hipEvent_t e_t0 = nullptr, e_t1 = nullptr, e_q0 = nullptr, e_q1 = nullptr, e_p1 = nullptr;
@@ -471,8 +450,8 @@ int nucleus_run(komb_ctx *ctx)
 
     ctx->timer.start(s);
     KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(NucCtl), s));
-    if (m > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.b.edge, 0xFF, (size_t)m * sizeof(int32_t), s));
-    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.b.vertex, 0xFF, (size_t)nv * sizeof(int32_t), s));
+    if (m > 0) KOMB_HIP(ctx, hipMemsetAsync(res.edge, 0xFF, (size_t)m * sizeof(int32_t), s));
+    if (nv > 0) KOMB_HIP(ctx, hipMemsetAsync(res.vertex, 0xFF, (size_t)nv * sizeof(int32_t), s));
     (void)hipEventRecord(e_t0, s);
     if (m > 0) {
         // ---- triangles
@@ -505,12 +484,12 @@ int nucleus_run(komb_ctx *ctx)
             uint32_t *tri_ptr = d_cnt;
             KOMB_TRY(prim_exclusive_sum_u32(ctx, d_cnt, tri_ptr, m + 1));
             NucTri o;
-            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.a, (size_t)T * sizeof(int32_t)));
-            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.b, (size_t)T * sizeof(int32_t)));
-            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.c, (size_t)T * sizeof(int32_t)));
-            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.key0, ((size_t)T + 1) * sizeof(int32_t)));   // (+ 1: the scan's last entry)
-            KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.theta, (size_t)T * sizeof(int32_t)));
-            o.a = fresh.b.a; o.b = fresh.b.b; o.c = fresh.b.c;
+            KOMB_HIP(ctx, ctx->pool.get((void **)res.a.slot(&ctx->pool), (size_t)T * sizeof(int32_t)));
+            KOMB_HIP(ctx, ctx->pool.get((void **)res.b.slot(&ctx->pool), (size_t)T * sizeof(int32_t)));
+            KOMB_HIP(ctx, ctx->pool.get((void **)res.c.slot(&ctx->pool), (size_t)T * sizeof(int32_t)));
+            KOMB_HIP(ctx, ctx->pool.get((void **)res.key0.slot(&ctx->pool), ((size_t)T + 1) * sizeof(int32_t)));   // (+ 1: the scan's last entry)
+            KOMB_HIP(ctx, ctx->pool.get((void **)res.theta.slot(&ctx->pool), (size_t)T * sizeof(int32_t)));
+            o.a = res.a; o.b = res.b; o.c = res.c;
             KOMB_HIP(ctx, bufs.alloc(&o.j, (size_t)T));
             KOMB_HIP(ctx, bufs.alloc(&o.pac, (size_t)T));
             KOMB_HIP(ctx, bufs.alloc(&o.pbc, (size_t)T));
@@ -523,7 +502,7 @@ int nucleus_run(komb_ctx *ctx)
             uint32_t *d_qcnt = nullptr, *d_inc_ptr = nullptr, *d_cur = nullptr, *d_inc = nullptr, *d_dead = nullptr, *d_queue = nullptr;
             int32_t *d_key = nullptr;
             uint4 *d_clq = nullptr;
-            uint32_t *key0 = (uint32_t *)fresh.b.key0;
+            uint32_t *key0 = (uint32_t *)res.key0.get();
             KOMB_HIP(ctx, bufs.alloc(&d_qcnt, (size_t)T + 1));   // counts, then q_ptr
             (void)hipEventRecord(e_q0, s);
             k_nuc_clq<false><<<nuc_grid(T + 1), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, d_qcnt, nullptr, nullptr, nullptr, d_ctl, n_short);
@@ -556,19 +535,19 @@ int nucleus_run(komb_ctx *ctx)
 
             // ---- the peel
             KOMB_HIP(ctx, hipMemcpyAsync(d_key, key0, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            KOMB_HIP(ctx, hipMemsetAsync(fresh.b.theta, 0xFF, (size_t)T * sizeof(int32_t), s));
+            KOMB_HIP(ctx, hipMemsetAsync(res.theta, 0xFF, (size_t)T * sizeof(int32_t), s));
             uint32_t *queue[2] = {d_queue, d_queue + T};
             const int sweep = nuc_sweep(T);
             int64_t remaining = T;
             while (remaining > 0) {
                 k_nuc_level_begin<<<1, 1, 0, s>>>(d_ctl);
-                k_nuc_min<<<sweep, kBlock, 0, s>>>(uT, fresh.b.theta, d_key, d_ctl);
-                k_nuc_collect<<<sweep, kBlock, 0, s>>>(uT, fresh.b.theta, d_key, d_ctl, queue[0]);
+                k_nuc_min<<<sweep, kBlock, 0, s>>>(uT, res.theta, d_key, d_ctl);
+                k_nuc_collect<<<sweep, kBlock, 0, s>>>(uT, res.theta, d_key, d_ctl, queue[0]);
                 int sel = 0, grid = sweep;                       // (the first frontier's length is on the device only)
                 bool first = true;
                 for (;;) {
-                    k_nuc_stamp<<<grid, kBlock, 0, s>>>(d_ctl, sel, queue[sel], uT, fresh.b.theta);
-                    k_nuc_walk<<<grid, kBlock, 0, s>>>(d_ctl, sel, queue[sel], queue[sel ^ 1], uT, d_inc_ptr, d_inc, d_clq, d_dead, fresh.b.theta, d_key, n_short);
+                    k_nuc_stamp<<<grid, kBlock, 0, s>>>(d_ctl, sel, queue[sel], uT, res.theta);
+                    k_nuc_walk<<<grid, kBlock, 0, s>>>(d_ctl, sel, queue[sel], queue[sel ^ 1], uT, d_inc_ptr, d_inc, d_clq, d_dead, res.theta, d_key, n_short);
                     KOMB_HIP(ctx, hipGetLastError());
                     KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));      // the one host read of the sub-round
                     const int64_t done = h.n_q[sel], next = h.n_q[sel ^ 1];
@@ -584,7 +563,7 @@ int nucleus_run(komb_ctx *ctx)
                 }
             }
             (void)hipEventRecord(e_p1, s);
-            k_nuc_out<<<nuc_grid(T), kBlock, 0, s>>>(uT, o, fresh.b.theta, fresh.b.edge, fresh.b.vertex);
+            k_nuc_out<<<nuc_grid(T), kBlock, 0, s>>>(uT, o, res.theta, res.edge, res.vertex);
             KOMB_HIP(ctx, hipGetLastError());
         }
     }
@@ -602,12 +581,9 @@ int nucleus_run(komb_ctx *ctx)
         fprintf(stderr, "komb nucleus: %lld edges, %lld triangles, %lld cliques, theta_max %d, %d levels, %lld sub-rounds, run %.3f ms, "
                 "triangle pass %.3f ms, clique pass %.3f ms, peel %.3f ms\n", (long long)m, (long long)T, (long long)Q, res.theta_max,
                 res.n_levels, (long long)res.n_subrounds, res.ms, res.ms_tri, res.ms_clq, res.ms_peel);
-    nucleus_drop(ctx);
-    ctx->d_nuc_a = fresh.b.a; ctx->d_nuc_b = fresh.b.b; ctx->d_nuc_c = fresh.b.c; ctx->d_nuc_key0 = fresh.b.key0;
-    ctx->d_nuc_theta = fresh.b.theta; ctx->d_nuc_edge = fresh.b.edge; ctx->d_nuc_vertex = fresh.b.vertex;
-    fresh.b = NucBlocks{};
-    ctx->nuc = res;
-    ctx->nuc_done = true;
+    ctx->nh = {};                            // (the nuclei and their forest index the triangles of the result that goes)
+    res.done = true;
+    ctx->nuc = std::move(res);
     return KOMB_OK;
 }
 

@@ -318,22 +318,15 @@ inline uint32_t nh_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
 int nh_labels_dev(komb_ctx *ctx, int32_t k, int32_t *d_label, int32_t *d_size)
 {
     const int64_t T = ctx->nuc.n_tri;
-    const int32_t *nodes = ctx->d_nh_nodes;
+    const int32_t *nodes = ctx->nh.nodes;
     const size_t c = (size_t)ctx->nh.cap;
-    k_nh_labels<<<forest_grid(T), kBlock, 0, ctx->stream>>>((uint32_t)T, k, ctx->d_nh_tnode, (uint32_t)ctx->nh.n_nodes, nodes, nodes + c, nodes + 2 * c,
+    k_nh_labels<<<forest_grid(T), kBlock, 0, ctx->stream>>>((uint32_t)T, k, ctx->nh.tnode, (uint32_t)ctx->nh.n_nodes, nodes, nodes + c, nodes + 2 * c,
                                                         nodes + 3 * c, d_label, d_size);
     KOMB_HIP(ctx, hipGetLastError());
     return KOMB_OK;
 }
 
 } // namespace
-
-void nucleus_hierarchy_drop(komb_ctx *ctx)
-{
-    ctx->pool.put(ctx->d_nh_nodes); ctx->pool.put(ctx->d_nh_tnode);
-    ctx->d_nh_nodes = ctx->d_nh_tnode = nullptr;
-    ctx->nh_done = false;
-}
 
 // the nucleus result it needs is checked by the caller (api.cpp).  The result is built in blocks of its own and replaces the
 // previous one only when the run has succeeded.
@@ -344,14 +337,10 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
     const int64_t T = ctx->nuc.n_tri, Q = ctx->nuc.n_clq;
 
     Range r_all("komb_nucleus_hierarchy_run");
-    struct Fresh {                                               // the new result: goes back to the pool unless it is installed
-        komb_ctx *c; int32_t *nodes = nullptr, *tnode = nullptr;
-        ~Fresh() { c->pool.put(nodes); c->pool.put(tnode); }
-    } fresh{ctx};
-    komb_ctx::NucleusHierarchy res;
+    komb_ctx::NucleusHierarchy res;                              // the new result: goes back to the pool unless it is installed
     res.theta_max = ctx->nuc.theta_max;
     size_t cap_nodes = 1;
-    KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.tnode, (size_t)(T > 0 ? T : 1) * sizeof(int32_t)));
+    KOMB_HIP(ctx, ctx->pool.get((void **)res.tnode.slot(&ctx->pool), (size_t)(T > 0 ? T : 1) * sizeof(int32_t)));
 
     ctx->timer.start(s);
     if (Q > 0) {
@@ -363,12 +352,12 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         const uint32_t levels = (uint32_t)res.theta_max + 1u;    // level numbers 0 .. levels - 1
         const int bits = forest_bits(levels);
         const uint32_t n_short = nh_opt_u32(ctx, "NUC_SHORT", kNhShort);      // (tests: every triangle through the wave / its lane)
-        const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *theta = ctx->d_nuc_theta;
+        const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *theta = ctx->nuc.theta;
 
         NhCtl *d_ctl = nullptr;
         uint32_t *d_rs = nullptr, *d_re = nullptr, *tri_ptr = nullptr, *d_flag = nullptr, *d_pos = nullptr, *cnt = nullptr, *rkeys2 = nullptr, *ridx2 = nullptr;
         int32_t *parent = nullptr, *cur = nullptr, *claimk = nullptr, *mnode = nullptr;
-        NucTri o{ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, nullptr, nullptr, nullptr};
+        NucTri o{ctx->nuc.a, ctx->nuc.b, ctx->nuc.c, nullptr, nullptr, nullptr};
         NhStream st{nullptr, nullptr, nullptr, uQ};
         KOMB_HIP(ctx, bufs.alloc(&d_ctl, 1));
         KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
@@ -469,28 +458,25 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         const uint32_t n = h.f.n_nodes;
         int32_t *rank = cur;                                     // (cur[] has served when the ranks are made; nodes <= members <= triangles)
         cap_nodes = n;
-        KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.nodes, 5 * cap_nodes * sizeof(int32_t)));
-        ForestNodes out{fresh.nodes, fresh.nodes + cap_nodes, fresh.nodes + 2 * cap_nodes,
-                        (uint32_t *)fresh.nodes + 3 * cap_nodes, (uint32_t *)fresh.nodes + 4 * cap_nodes};
+        KOMB_HIP(ctx, ctx->pool.get((void **)res.nodes.slot(&ctx->pool), 5 * cap_nodes * sizeof(int32_t)));
+        ForestNodes out{res.nodes, res.nodes + cap_nodes, res.nodes + 2 * cap_nodes,
+                        (uint32_t *)res.nodes.get() + 3 * cap_nodes, (uint32_t *)res.nodes.get() + 4 * cap_nodes};
         KOMB_TRY(forest_tail(ctx, bufs, f, n, bits, out, rank, nullptr, mvals, mvals2));   // (the members' sort has served: n <= nm)
-        k_nh_tri_out<<<forest_grid(T), kBlock, 0, s>>>(uT, theta, mnode, rank, n, fresh.tnode);
+        k_nh_tri_out<<<forest_grid(T), kBlock, 0, s>>>(uT, theta, mnode, rank, n, res.tnode);
         res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NhCtl)));
         res.n_nodes = (int64_t)n; res.n_roots = (int64_t)h.f.n_roots; res.depth = h.f.depth; res.n_members = (int64_t)nm;
     } else {
-        if (T > 0) KOMB_HIP(ctx, hipMemsetAsync(fresh.tnode, 0xFF, (size_t)T * sizeof(int32_t), s));   // no clique: no nucleus
+        if (T > 0) KOMB_HIP(ctx, hipMemsetAsync(res.tnode, 0xFF, (size_t)T * sizeof(int32_t), s));   // no clique: no nucleus
         res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
     }
-    if (!fresh.nodes) KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.nodes, 5 * cap_nodes * sizeof(int32_t)));
+    if (!res.nodes) KOMB_HIP(ctx, ctx->pool.get((void **)res.nodes.slot(&ctx->pool), 5 * cap_nodes * sizeof(int32_t)));
     res.cap = (int64_t)cap_nodes;
 
-    nucleus_hierarchy_drop(ctx);
-    ctx->d_nh_nodes = fresh.nodes; ctx->d_nh_tnode = fresh.tnode;
-    fresh.nodes = fresh.tnode = nullptr;
-    ctx->nh = res;
-    ctx->nh_done = true;
+    res.done = true;
+    ctx->nh = std::move(res);
     return KOMB_OK;
 }
 
@@ -550,7 +536,7 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
         KOMB_HIP(ctx, bufs.alloc(&vuniq, n_keys));
         KOMB_HIP(ctx, bufs.alloc(&euniq, n_keys));
         KOMB_HIP(ctx, bufs.alloc(&d_out, 4 * (size_t)n_nuc));
-        k_nh_keys<<<forest_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, ctx->d_nuc_a, ctx->d_nuc_b, ctx->d_nuc_c, ctx->d_t_eu, ctx->d_t_ev,
+        k_nh_keys<<<forest_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, ctx->nuc.a, ctx->nuc.b, ctx->nuc.c, ctx->d_t_eu, ctx->d_t_ev,
                                                 (uint32_t)m, vkeys, ekeys);
         KOMB_HIP(ctx, hipGetLastError());
         int64_t n_v = 0, n_e = 0;

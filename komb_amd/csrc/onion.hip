@@ -88,14 +88,14 @@ int onion_run(komb_ctx *ctx)
     if (ctx->nv < 0) KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_onion_run: no graph loaded");
     const int64_t nv = ctx->nv;
     hipStream_t s = ctx->stream;
-    ctx->onion_done = false;
-    if (!ctx->d_onion_layer) {
+    ctx->onion.done = false;
+    if (!ctx->onion.layer) {
         const size_t bytes = (size_t)(nv > 0 ? nv : 1) * sizeof(int32_t);
-        KOMB_HIP(ctx, dev_malloc_pair(ctx, &ctx->d_onion_layer, bytes, &ctx->d_onion_core, bytes));
+        KOMB_HIP(ctx, dev_malloc_pair(ctx, ctx->onion.layer.slot(nullptr), bytes, ctx->onion.core.slot(nullptr), bytes));
     }
     if (nv == 0) {
-        ctx->onion_layers = 0; ctx->onion_max_core = 0; ctx->onion_ms = 0.0;
-        ctx->onion_done = true;
+        ctx->onion.n_layers = 0; ctx->onion.max_core = 0; ctx->onion.ms = 0.0;
+        ctx->onion.done = true;
         return KOMB_OK;
     }
 
@@ -133,10 +133,10 @@ int onion_run(komb_ctx *ctx)
     const int64_t g = (nv + kBlock - 1) / kBlock;
     const int grid_init = (int)(g > 1024 ? 1024 : g);
     const int grid = peel_grid(nv);
-    OnionProblem P{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, d_degw, ctx->d_onion_core, ctx->d_onion_layer};
+    OnionProblem P{(uint32_t)nv, ctx->d_o_rowptr, ctx->d_o_col, d_degw, ctx->onion.core, ctx->onion.layer};
     ctx->timer.start(s);
     peel_ctrl_pre(s, d_grp);
-    k_onion_init<<<grid_init, kBlock, 0, s>>>(ctx->d_o_rowptr, nv, d_degw, ctx->d_onion_core, ctx->d_onion_layer, d_grp + kInitOff);
+    k_onion_init<<<grid_init, kBlock, 0, s>>>(ctx->d_o_rowptr, nv, d_degw, ctx->onion.core, ctx->onion.layer, d_grp + kInitOff);
     peel_ctrl_init(s, d_ctrl, d_grp, (uint32_t)nv, tail_limit);
     k_onion_round_base<<<1, 64, 0, s>>>(d_ctrl, d_grp);
     // the live vertices are those of `list` (or all nv when list is null) whose coreness is still an alive marker
@@ -145,9 +145,9 @@ int onion_run(komb_ctx *ctx)
         KOMB_HIP(ctx, hipMemsetAsync(T.cnt, 0, 4 * sizeof(uint32_t), s));
         KOMB_HIP(ctx, hipMemsetAsync(T.rows, 0, (size_t)kCoreTailV * kCoreTailWords * sizeof(unsigned long long), s));
         const int64_t gm = ((int64_t)n_in + kBlock - 1) / kBlock;
-        k_ctail_mark<<<(int)(gm < 1 ? 1 : (gm > 1024 ? 1024 : gm)), kBlock, 0, s>>>(list, n_in, ctx->d_onion_core, T);
+        k_ctail_mark<<<(int)(gm < 1 ? 1 : (gm > 1024 ? 1024 : gm)), kBlock, 0, s>>>(list, n_in, ctx->onion.core, T);
         k_ctail_rows<<<dim3(kCoreTailV, 8), kBlock, 0, s>>>(ctx->d_o_rowptr, ctx->d_o_col, T);
-        k_core_tail<true><<<1, 1024, 0, s>>>(d_ctrl, T, d_degw, ctx->d_onion_core, ctx->d_onion_layer);
+        k_core_tail<true><<<1, 1024, 0, s>>>(d_ctrl, T, d_degw, ctx->onion.core, ctx->onion.layer);
         KOMB_HIP(ctx, d2h(ctx, &ctx->h_ctrl[0], d_ctrl, sizeof(PeelCtrl)));
         return KOMB_OK;
     };
@@ -173,10 +173,10 @@ int onion_run(komb_ctx *ctx)
     const double ms = ctx->timer.stop(s);
     KOMB_TRY(st);
     if (ctx->h_ctrl[0].done != 1) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "onion peel ended in an inconsistent state");
-    ctx->onion_layers = (int64_t)ctx->h_ctrl[0].round - 1;       // the counter has moved past the last layer
-    ctx->onion_max_core = ctx->h_ctrl[0].max_level;
-    ctx->onion_ms = ms;
-    ctx->onion_done = true;
+    ctx->onion.n_layers = (int64_t)ctx->h_ctrl[0].round - 1;       // the counter has moved past the last layer
+    ctx->onion.max_core = ctx->h_ctrl[0].max_level;
+    ctx->onion.ms = ms;
+    ctx->onion.done = true;
     return KOMB_OK;
 }
 

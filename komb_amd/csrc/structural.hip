@@ -259,27 +259,7 @@ __global__ void k_sc_widen(const uint8_t *__restrict__ similar, uint32_t m, int3
     if (i < m) out[i] = similar[i] ? 1 : 0;
 }
 
-struct ScBlocks {                           // the arrays of one result: pool blocks
-    int32_t *label = nullptr, *size = nullptr, *role = nullptr, *simdeg = nullptr;
-    uint8_t *similar = nullptr;
-};
-
-void sc_put(komb_ctx *ctx, ScBlocks &b)
-{
-    ctx->pool.put(b.label); ctx->pool.put(b.size); ctx->pool.put(b.role); ctx->pool.put(b.simdeg); ctx->pool.put(b.similar);
-    b = ScBlocks{};
-}
-
 } // namespace
-
-void structural_drop(komb_ctx *ctx)
-{
-    ScBlocks b{ctx->d_sc_label, ctx->d_sc_size, ctx->d_sc_role, ctx->d_sc_simdeg, ctx->d_sc_similar};
-    sc_put(ctx, b);
-    ctx->d_sc_label = ctx->d_sc_size = ctx->d_sc_role = ctx->d_sc_simdeg = nullptr;
-    ctx->d_sc_similar = nullptr;
-    ctx->sc_done = false;
-}
 
 // the parameters and the k-truss result it needs are checked by the caller (api.cpp).  The result is built in blocks of its
 // own and replaces the previous one only when the run has succeeded.
@@ -292,15 +272,14 @@ int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu)
         KOMB_TRY(truss_support_canonical(ctx));         // (... whose supports no fetch has put in canonical order yet)
     }
     Range r_all("komb_structural_clusters_run");
-    struct Fresh { komb_ctx *c; ScBlocks b; ~Fresh() { sc_put(c, b); } } fresh{ctx};   // goes back to the pool unless it is installed
-    komb_ctx::Structural res;
+    komb_ctx::Structural res;                            // goes back to the pool unless it is installed
     res.eps_num = eps_num; res.eps_den = eps_den; res.mu = mu;
     if (nv > 0) {
-        KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.label, (size_t)nv * sizeof(int32_t)));
-        KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.size, (size_t)nv * sizeof(int32_t)));
-        KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.role, (size_t)nv * sizeof(int32_t)));
-        KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.simdeg, (size_t)nv * sizeof(int32_t)));
-        KOMB_HIP(ctx, ctx->pool.get((void **)&fresh.b.similar, (size_t)(m > 0 ? m : 1)));
+        KOMB_HIP(ctx, ctx->pool.get((void **)res.label.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
+        KOMB_HIP(ctx, ctx->pool.get((void **)res.size.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
+        KOMB_HIP(ctx, ctx->pool.get((void **)res.role.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
+        KOMB_HIP(ctx, ctx->pool.get((void **)res.simdeg.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
+        KOMB_HIP(ctx, ctx->pool.get((void **)res.similar.slot(&ctx->pool), (size_t)(m > 0 ? m : 1)));
         DevBufs bufs(ctx);
         ScCtl *d_ctl = nullptr;
         uint32_t *d_deg = nullptr, *d_cnt = nullptr;
@@ -318,7 +297,7 @@ int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu)
 
         const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *sup = ctx->d_t_sup;
         const bool whole = !ctx->t_own_edges;               // d(v) is the resident row length; a vmask result counts its endpoints
-        uint32_t *simdeg = (uint32_t *)fresh.b.simdeg;
+        uint32_t *simdeg = (uint32_t *)res.simdeg.get();
         const uint32_t un = (uint32_t)nv, um = (uint32_t)m, umu = (uint32_t)mu;
         const uint64_t num2 = (uint64_t)eps_num * (uint64_t)eps_num, den2 = (uint64_t)eps_den * (uint64_t)eps_den;
         const int gv = sc_grid(nv), ge = sc_grid(m);
@@ -328,19 +307,19 @@ int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu)
         if (m > 0) {
             if (!whole) k_sc_degree<<<ge, kBlock, 0, s>>>(eu, ev, um, d_deg);
             (void)hipEventRecord(e0, s);
-            k_sc_similar<<<ge, kBlock, 0, s>>>(eu, ev, sup, um, d_deg, num2, den2, fresh.b.similar, simdeg, d_ctl);
+            k_sc_similar<<<ge, kBlock, 0, s>>>(eu, ev, sup, um, d_deg, num2, den2, res.similar, simdeg, d_ctl);
             (void)hipEventRecord(e1, s);
-            k_sc_link<<<ge, kBlock, 0, s>>>(eu, ev, fresh.b.similar, um, simdeg, umu, d_parent);
-            k_sc_flatten<false><<<gv, kBlock, 0, s>>>(un, simdeg, umu, d_parent, fresh.b.label);
+            k_sc_link<<<ge, kBlock, 0, s>>>(eu, ev, res.similar, um, simdeg, umu, d_parent);
+            k_sc_flatten<false><<<gv, kBlock, 0, s>>>(un, simdeg, umu, d_parent, res.label);
         }
-        k_sc_flatten<true><<<gv, kBlock, 0, s>>>(un, simdeg, umu, d_parent, fresh.b.label);
+        k_sc_flatten<true><<<gv, kBlock, 0, s>>>(un, simdeg, umu, d_parent, res.label);
         if (m > 0) {
-            k_sc_border<<<ge, kBlock, 0, s>>>(eu, ev, fresh.b.similar, um, simdeg, umu, fresh.b.label);
-            k_sc_hub<<<ge, kBlock, 0, s>>>(eu, ev, um, fresh.b.label, d_lo, d_hi);
+            k_sc_border<<<ge, kBlock, 0, s>>>(eu, ev, res.similar, um, simdeg, umu, res.label);
+            k_sc_hub<<<ge, kBlock, 0, s>>>(eu, ev, um, res.label, d_lo, d_hi);
         }
         const int tail_grid = gv < kScTailGrid ? gv : kScTailGrid;
-        k_sc_count<<<tail_grid, kBlock, 0, s>>>(un, fresh.b.label, d_cnt);
-        k_sc_finish<<<tail_grid, kBlock, 0, s>>>(un, simdeg, umu, d_lo, d_hi, d_cnt, fresh.b.label, fresh.b.size, fresh.b.role, d_ctl);
+        k_sc_count<<<tail_grid, kBlock, 0, s>>>(un, res.label, d_cnt);
+        k_sc_finish<<<tail_grid, kBlock, 0, s>>>(un, simdeg, umu, d_lo, d_hi, d_cnt, res.label, res.size, res.role, d_ctl);
         res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
         ScCtl h;
@@ -356,12 +335,8 @@ int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu)
             fprintf(stderr, "komb structural: %lld vertices, %lld edges, run %.3f ms, similarity pass %.3f ms\n",
                     (long long)nv, (long long)m, res.ms, res.ms_similar);
     }
-    structural_drop(ctx);
-    ctx->d_sc_label = fresh.b.label; ctx->d_sc_size = fresh.b.size; ctx->d_sc_role = fresh.b.role; ctx->d_sc_simdeg = fresh.b.simdeg;
-    ctx->d_sc_similar = fresh.b.similar;
-    fresh.b = ScBlocks{};
-    ctx->sc = res;
-    ctx->sc_done = true;
+    res.done = true;
+    ctx->sc = std::move(res);
     return KOMB_OK;
 }
 
@@ -373,7 +348,7 @@ int structural_fetch_edges(komb_ctx *ctx, int32_t *similar)
     DevBufs bufs(ctx);
     int32_t *d_out = nullptr;
     KOMB_HIP(ctx, bufs.alloc(&d_out, (size_t)m));
-    k_sc_widen<<<sc_grid(m), kBlock, 0, ctx->stream>>>(ctx->d_sc_similar, (uint32_t)m, d_out);
+    k_sc_widen<<<sc_grid(m), kBlock, 0, ctx->stream>>>(ctx->sc.similar, (uint32_t)m, d_out);
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     KOMB_HIP(ctx, staged_copy(ctx, similar, d_out, (size_t)m * sizeof(int32_t), false));
