@@ -29,7 +29,7 @@ namespace komb {
 namespace {
 
 constexpr int kLdsLine = 10;                    // words of a line kept in LDS: 4 signature blocks, start, length
-constexpr int kWCand = 128;                     // parked candidates per wavefront
+constexpr int kWCand = 5 * kWave;               // parked candidates per wavefront (4 bytes each): up to 63 wait when a trip of the tests parks up to 4 per lane
 constexpr uint32_t kScratchRec = (uint32_t)kTriCap * (kTriCap - 1) / 2 + 128;     // records of a staged sub-range at most (+ one LDS buffer's slack)
 
 // MODE: TRI_COUNT (supports only: own[] by plain stores, other[] by atomics) or TRI_SINGLE (the record-stream build:
@@ -48,13 +48,14 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
     // C(kTriCap, 2) triangles, which fits: only rows too long to stage send their own-role entries through the record stream.
     // ablate (debug builds, KOMB_TRI_ABLATE; breaks results on purpose): 1 = survivors are dropped (no look-up), 2 = no candidate tests, 4 = no line loads, 8 = look-ups find nothing
     constexpr bool STREAM = MODE == TRI_SINGLE;
+    static_assert(kWCand >= kWave - 1 + 4 * kWave, "a trip of the candidate tests parks up to 4 per lane on top of what waits");
     __shared__ int32_t sh_col[kTriWaves][kTriCap];
     __shared__ uint32_t sh_cnt[kTriWaves][kTriCap];
     __shared__ uint32_t sh_orow[kTriWaves][kWedgeV + 1];
     __shared__ uint32_t sh_pref[kTriWaves][kWave];
     __shared__ uint32_t sh_rend[kTriWaves][kWave];
     __shared__ uint2 sh_rec[kTriWaves][kTriRec];
-    __shared__ uint2 sh_cand[kTriWaves][kWCand];
+    __shared__ uint32_t sh_cand[kTriWaves][kWCand];
     // of every edge's line LDS keeps what the candidate tests read -- the signature -- and start / length; the six pivots stay in
     // the registers of the edge's lane and reach a survivor's lane by shuffle (8 KB of LDS less per workgroup: 4 instead of 3
     // workgroups per CU)
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
     uint32_t *s_cnt = sh_cnt[w], *s_orow = sh_orow[w], *s_pref = sh_pref[w], *s_rend = sh_rend[w];
     uint2 *s_rec = sh_rec[w];
     uint3 *s_tri = reinterpret_cast<uint3 *>(sh_rec[w]);
-    uint2 *s_cand = sh_cand[w];
+    uint32_t *s_cand = sh_cand[w];
     uint32_t (*s_line)[kLdsLine] = sh_line[w];
     uint8_t *s_rid = sh_rid[w];
     const int64_t gw = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
         const uint32_t rank = (uint32_t)__popcll(m & lanemask_lt());
         const uint32_t left = (uint32_t)min((unsigned long long)c, rec_end - rec_pos);    // (wave-uniform) positions left in the current claim
         unsigned long long q = rec_pos + rank;
-        if (left < c) {                                          // the claim runs out inside this append: the rest goes to a new one
+        if (__builtin_expect(left < c, 0)) {                     // the claim runs out inside this append (once per kRecChunk records): the rest goes to a new one
             unsigned long long got = 0;
             if (lane == 0) got = atomicAdd(ts.cursor, (unsigned long long)kRecChunk);
             const uint32_t glo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)got);
@@ -92,6 +93,16 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
             rec_end = fresh + kRecChunk;
         } else rec_pos += c;
         if (has && q < ts.cap) { ts.key[q] = key; ts.val[q] = val; }
+    };
+    // all 64 lanes call: the entries of the triangle {e, i, jj} of the lanes with `has` become records -- the third-role entry
+    // (jj's) and / or the two own-role entries (e's, i's); `third` and `own_role` are wave-uniform.  (One append in a loop
+    // over the roles makes the code 700 instructions shorter and the kernel 0.06 ms slower: DESIGN.md Appendix A)
+    auto emit = [&](bool has, uint32_t e, uint32_t i, uint32_t jj, bool third, bool own_role) {
+        if (third) rec_append(has, jj, make_int2((int)e, (int)i));
+        if (own_role) {
+            rec_append(has, e, make_int2((int)i, (int)jj));
+            rec_append(has, i, make_int2((int)e, (int)jj));
+        }
     };
 
     // the heaviest tasks (the last ones: hub rows) go first
@@ -129,29 +140,26 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
         }
         __builtin_amdgcn_wave_barrier();
 
+        // what waits in the record buffer (wave-uniform): parked triangles of an unstaged sub-range, records of a staged one.
+        // ONE counter for the two uses: two, both reset behind the look-up, ended up as a private array in scratch memory
+        uint32_t n_buf = 0;
         // ---- unstaged sub-range: triangles are parked and handled 64 at a time, all three roles through records / global counters
-        uint32_t n_tri = 0;                                     // parked triangles (wave-uniform)
         auto flush_tris = [&]() {
             __builtin_amdgcn_wave_barrier();
-            for (uint32_t b0 = 0; b0 < n_tri; b0 += kWave) {
+            for (uint32_t b0 = 0; b0 < n_buf; b0 += kWave) {
                 const uint32_t x = b0 + (uint32_t)lane;
-                const bool has = x < n_tri;
+                const bool has = x < n_buf;
                 const uint3 tr = has ? s_tri[x] : make_uint3(0u, 0u, 0u);
                 const uint32_t e = S0 + tr.x, i = S0 + tr.y, jj = tr.z;
                 if (MODE == TRI_COUNT) {
                     if (has) { atomicAdd(&other[e], 1u); atomicAdd(&other[i], 1u); atomicAdd(&other[jj], 1u); }
-                } else {
-                    rec_append(has, e, make_int2((int)i, (int)jj));
-                    rec_append(has, i, make_int2((int)e, (int)jj));
-                    rec_append(has, jj, make_int2((int)e, (int)i));
-                }
+                } else emit(has, e, i, jj, true, true);
             }
             __builtin_amdgcn_wave_barrier();
-            n_tri = 0;
         };
 
         // ---- staged sub-range: record = (e_rel | i_rel << 8 | cursor_e << 16 | cursor_i << 24, j); see truss_tri.h
-        uint32_t n_rec = 0, n_done = 0;                         // wave-uniform: records, records whose third role is written
+        uint32_t n_done = 0;                                    // wave-uniform: records whose third role is written
         uint32_t n_scr = 0;                                     // wave-uniform: records moved to the wavefront's scratch
         uint2 *scr = scratch ? scratch + (size_t)gw * kScratchRec : nullptr;
         bool spilled = false;                                   // wave-uniform: the own-role entries are records too
@@ -162,105 +170,17 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
                 const bool has = x < hi;
                 const uint2 rc = has ? s_rec[x] : make_uint2(0u, 0u);
                 const uint32_t e = S0 + (rc.x & 0xFFu), i = S0 + ((rc.x >> 8) & 0xFFu), jj = rc.y;
-                if (third) rec_append(has, jj, make_int2((int)e, (int)i));
-                if (own_role) {
-                    rec_append(has, e, make_int2((int)i, (int)jj));
-                    rec_append(has, i, make_int2((int)e, (int)jj));
-                }
+                emit(has, e, i, jj, third, own_role);
             }
             __builtin_amdgcn_wave_barrier();
         };
 
-        // candidates that pass the signature are parked as (lane of their edge in the batch | slot of c in row a << 6, c)
-        // and looked up in N+(b) densely, 64 at a time; p0 = the batch's first slot
+        // candidates that pass the signature are parked as (lane of their edge in the batch | slot of c in row a << 6) and
+        // looked up in N+(b) densely, 64 at a time, from the top of the buffer (what stays parked stays in place).  c itself is
+        // read again from the row (LDS for a staged sub-range): 4 bytes per parked candidate instead of 8.  The look-up, with
+        // the record hand-over behind it, stands at ONE place of the batch loop
         uint32_t n_cand = 0;                                    // wave-uniform
         int32_t pv0 = 0, pv1 = 0, pv2 = 0, pv3 = 0, pv4 = 0, pv5 = 0;      // the pivots of this lane's edge of the current batch
-        auto search_cands = [&](uint32_t p0) {
-            __builtin_amdgcn_wave_barrier();
-            if (ablate & 1) n_cand = 0;
-            for (uint32_t b0 = 0; b0 < n_cand; b0 += kWave) {
-                const uint32_t x = b0 + (uint32_t)lane;
-                uint32_t t = 0, i_rel = 0, l = 0, n = 0;
-                int32_t c = 0;
-                const bool have = x < n_cand;
-                if (have) {
-                    const uint2 cd = s_cand[x];
-                    t = cd.x & 63u; i_rel = cd.x >> 6; c = (int32_t)cd.y;
-                }
-                // the pivots of the candidate's edge, from the registers of that edge's lane (all lanes take part in the shuffles)
-                const int32_t p0v = __shfl(pv0, (int)t), p1v = __shfl(pv1, (int)t), p2v = __shfl(pv2, (int)t);
-                const int32_t p3v = __shfl(pv3, (int)t), p4v = __shfl(pv4, (int)t), p5v = __shfl(pv5, (int)t);
-                if (have) {
-                    const uint32_t *ln = s_line[t];
-                    l = ln[8];
-                    const uint32_t len = ln[9], seg = (len + (uint32_t)kPivots) / (uint32_t)(kPivots + 1);
-                    // segment of c: the number of pivots <= c (the pivots are ascending; unused ones are INT32_MAX)
-                    uint32_t sidx;
-                    if (p3v <= c) sidx = p5v <= c ? 6u : (p4v <= c ? 5u : 4u);
-                    else sidx = p1v <= c ? (p2v <= c ? 3u : 2u) : (p0v <= c ? 1u : 0u);
-                    const uint32_t lo = sidx * seg;
-                    l += lo;
-                    n = lo < len ? min(seg, len - lo) : 0u;
-                }
-                // segments longer than 8 elements (rows longer than 56) are halved in global memory first
-                while (__ballot(n > 8u)) {
-                    const bool on = n > 8u;
-                    const uint32_t half = n >> 1;
-                    const int32_t pvv = on ? ocol[l + half] : 0;
-                    const bool go = on && pvv <= c;                           // c, if present, is at or behind l + half
-                    l = go ? l + half : l;
-                    n = on ? (go ? n - half : half) : n;
-                }
-                // the segment: up to 8 consecutive elements, two 16-byte loads issued together
-                uint32_t pos = 0xFFFFFFFFu;
-                if (n) {
-                    const Int4U q0 = *reinterpret_cast<const Int4U *>(ocol + l);
-                    Int4U q1 = {0, 0, 0, 0};
-                    if (n > 4u) q1 = *reinterpret_cast<const Int4U *>(ocol + l + 4);
-                    pos = q0.x == c ? 0u : (n > 1u && q0.y == c) ? 1u : (n > 2u && q0.z == c) ? 2u : (n > 3u && q0.w == c) ? 3u :
-                          (n > 4u && q1.x == c) ? 4u : (n > 5u && q1.y == c) ? 5u : (n > 6u && q1.z == c) ? 6u : (n > 7u && q1.w == c) ? 7u : 0xFFFFFFFFu;
-                }
-                const bool hit = pos != 0xFFFFFFFFu && !((ablate & 8) && c != -1);          // (ablate 8: the look-up's loads happen, no triangle is reported)
-                l += hit ? pos : 0u;
-                const uint64_t hm = __ballot(hit);
-                if (!hm) continue;
-                const uint32_t e_rel = p0 + t;
-                if (!staged) {
-                    if (hit) s_tri[n_tri + (uint32_t)__popcll(hm & lanemask_lt())] = make_uint3(e_rel, i_rel, l);
-                    n_tri += (uint32_t)__popcll(hm);
-                    if (n_tri >= (uint32_t)kTriBuf - kWave) flush_tris();
-                    continue;
-                }
-                if (hit) {
-                    const uint32_t ce = atomicAdd(&s_cnt[e_rel], 1u), ci = atomicAdd(&s_cnt[i_rel], 1u);
-                    if (MODE == TRI_COUNT) atomicAdd(&other[l], 1u);
-                    else s_rec[n_rec + (uint32_t)__popcll(hm & lanemask_lt())] = make_uint2(e_rel | (i_rel << 8) | (ce << 16) | (ci << 24), l);
-                }
-                if (MODE == TRI_SINGLE) {
-                    n_rec += (uint32_t)__popcll(hm);
-                    if (n_rec - n_done >= (uint32_t)kWave) {                 // 64 or more are waiting: one dense pass over all of them
-                        drain(n_done, n_rec, true, spilled);
-                        n_done = n_rec;
-                    }
-                    if (n_rec > (uint32_t)kTriRec - kWave) {
-                        // the buffer is full: the sub-range gives up its dense block -- everything kept so far, and what follows, become records
-                        if (!spilled && scr && n_scr + n_rec <= kScratchRec) {
-                            drain(n_done, n_rec, true, false);                    // their third-role records go out now
-                            for (uint32_t x = (uint32_t)lane; x < n_rec; x += kWave) scr[n_scr + x] = s_rec[x];
-                            n_scr += n_rec;
-                            if (lane == 0) atomicAdd(dense_cursor + 1, 1ull);     // statistics
-                        } else if (!spilled) {
-                            drain(n_done, n_rec, true, false);
-                            drain(0, n_rec, false, true);
-                            spilled = true;
-                        } else drain(n_done, n_rec, true, true);
-                        n_rec = 0; n_done = 0;
-                    }
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            n_cand = 0;
-        };
 
         // The line of the NEXT batch's edge is requested before this batch's candidates are tested: its trip to memory runs
         // beside the tests (LDS work) instead of before them.  16 registers per lane.
@@ -301,7 +221,8 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
             __builtin_amdgcn_wave_barrier();
             s_pref[lane] = incl; s_rend[lane] = rend;
             __builtin_amdgcn_wave_barrier();
-            for (uint32_t it0 = 0; it0 < ((ablate & 2) ? 0u : total); it0 += kWave) {
+            const uint32_t n_it = (ablate & 2) ? 0u : total;
+            for (uint32_t it0 = 0; it0 < n_it; it0 += kWave) {
                 const uint32_t it = it0 + (uint32_t)lane;
                 const bool live = it < total;
                 int t = 0;                                    // owner: smallest t with s_pref[t] > it (branchless, 6 fixed steps)
@@ -312,33 +233,127 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
                 const uint32_t i0 = p0 + (uint32_t)t + 1u + ((it - first) << 2);           // first candidate slot of the chunk
                 const uint32_t nin = live ? min(4u, s_rend[t] - i0) : 0u;
                 const uint32_t *ln = s_line[t];
+                // the four tests of the chunk first, then ONE compaction: four ballots and their popcounts give every lane its
+                // positions in the buffer, and no branch into the look-up sits between the slots
+                uint64_t cm[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     bool cand = false;
-                    int32_t c = 0;
                     if ((uint32_t)k < nin) {
-                        c = staged ? s_col[i0 + (uint32_t)k] : ocol[S0 + i0 + (uint32_t)k];
+                        const int32_t c = staged ? s_col[i0 + (uint32_t)k] : ocol[S0 + i0 + (uint32_t)k];
                         uint32_t blk; unsigned long long mask;
                         sig_slot(c, blk, mask);
                         const unsigned long long word = *reinterpret_cast<const unsigned long long *>(ln + 2 * blk);
                         cand = (word & mask) == mask;
                     }
-                    const uint64_t cm = __ballot(cand);
-                    if (cm) {
-                        if (cand) s_cand[n_cand + (uint32_t)__popcll(cm & lanemask_lt())] = make_uint2((uint32_t)t | ((i0 + (uint32_t)k) << 6), (uint32_t)c);
-                        n_cand += (uint32_t)__popcll(cm);
-                        if (n_cand >= (uint32_t)kWave) search_cands(p0);       // at most 63 are waiting when the next 64 arrive
+                    cm[k] = __ballot(cand);
+                }
+                const uint64_t below = lanemask_lt();
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if ((cm[k] >> lane) & 1ull) s_cand[n_cand + (uint32_t)__popcll(cm[k] & below)] = (uint32_t)t | ((i0 + (uint32_t)k) << 6);
+                    n_cand += (uint32_t)__popcll(cm[k]);
+                }
+                // at most 63 were waiting and at most 4 * 64 arrived.  The batch's last trip empties the buffer: the parked
+                // candidates name their edge by its lane in THIS batch
+                const bool last = it0 + (uint32_t)kWave >= n_it;
+                if (n_cand >= (uint32_t)kWave || last) {
+                    const uint32_t keep = last ? 0u : (n_cand & (uint32_t)(kWave - 1));
+                    __builtin_amdgcn_wave_barrier();
+                    if (ablate & 1) n_cand = keep;
+                    while (n_cand > keep) {
+                        const uint32_t b0 = n_cand > (uint32_t)kWave ? n_cand - (uint32_t)kWave : 0u;
+                        const uint32_t x = b0 + (uint32_t)lane;
+                        uint32_t ct = 0, i_rel = 0, l = 0, n = 0;
+                        int32_t c = 0;
+                        const bool have = x < n_cand;
+                        n_cand = b0;
+                        if (have) {
+                            const uint32_t cd = s_cand[x];
+                            ct = cd & 63u; i_rel = cd >> 6;
+                            c = staged ? s_col[i_rel] : ocol[S0 + i_rel];
+                        }
+                        // the pivots of the candidate's edge, from the registers of that edge's lane (all lanes take part in the shuffles)
+                        const int32_t p0v = __shfl(pv0, (int)ct), p1v = __shfl(pv1, (int)ct), p2v = __shfl(pv2, (int)ct);
+                        const int32_t p3v = __shfl(pv3, (int)ct), p4v = __shfl(pv4, (int)ct), p5v = __shfl(pv5, (int)ct);
+                        if (have) {
+                            const uint32_t *cl = s_line[ct];
+                            l = cl[8];
+                            const uint32_t len = cl[9], seg = (len + (uint32_t)kPivots) / (uint32_t)(kPivots + 1);
+                            // segment of c: the number of pivots <= c (the pivots are ascending; unused ones are INT32_MAX)
+                            uint32_t sidx;
+                            if (p3v <= c) sidx = p5v <= c ? 6u : (p4v <= c ? 5u : 4u);
+                            else sidx = p1v <= c ? (p2v <= c ? 3u : 2u) : (p0v <= c ? 1u : 0u);
+                            const uint32_t lo = sidx * seg;
+                            l += lo;
+                            n = lo < len ? min(seg, len - lo) : 0u;
+                        }
+                        // segments longer than 8 elements (rows longer than 56) are halved in global memory first
+                        while (__ballot(n > 8u)) {
+                            const bool on = n > 8u;
+                            const uint32_t half = n >> 1;
+                            const int32_t pvv = on ? ocol[l + half] : 0;
+                            const bool go = on && pvv <= c;                           // c, if present, is at or behind l + half
+                            l = go ? l + half : l;
+                            n = on ? (go ? n - half : half) : n;
+                        }
+                        // the segment: up to 8 consecutive elements, two 16-byte loads issued together
+                        uint32_t pos = 0xFFFFFFFFu;
+                        if (n) {
+                            const Int4U q0 = *reinterpret_cast<const Int4U *>(ocol + l);
+                            Int4U q1 = {0, 0, 0, 0};
+                            if (n > 4u) q1 = *reinterpret_cast<const Int4U *>(ocol + l + 4);
+                            pos = q0.x == c ? 0u : (n > 1u && q0.y == c) ? 1u : (n > 2u && q0.z == c) ? 2u : (n > 3u && q0.w == c) ? 3u :
+                                  (n > 4u && q1.x == c) ? 4u : (n > 5u && q1.y == c) ? 5u : (n > 6u && q1.z == c) ? 6u : (n > 7u && q1.w == c) ? 7u : 0xFFFFFFFFu;
+                        }
+                        const bool hit = pos != 0xFFFFFFFFu && !((ablate & 8) && c != -1);          // (ablate 8: the look-up's loads happen, no triangle is reported)
+                        l += hit ? pos : 0u;
+                        const uint64_t hm = __ballot(hit);
+                        if (!hm) continue;
+                        const uint32_t e_rel = p0 + ct;
+                        if (!staged) {
+                            if (hit) s_tri[n_buf + (uint32_t)__popcll(hm & lanemask_lt())] = make_uint3(e_rel, i_rel, l);
+                            n_buf += (uint32_t)__popcll(hm);
+                            if (n_buf >= (uint32_t)kTriBuf - kWave) { flush_tris(); n_buf = 0; }
+                            continue;
+                        }
+                        if (hit) {
+                            const uint32_t ce = atomicAdd(&s_cnt[e_rel], 1u), ci = atomicAdd(&s_cnt[i_rel], 1u);
+                            if (MODE == TRI_COUNT) atomicAdd(&other[l], 1u);
+                            else s_rec[n_buf + (uint32_t)__popcll(hm & lanemask_lt())] = make_uint2(e_rel | (i_rel << 8) | (ce << 16) | (ci << 24), l);
+                        }
+                        if (MODE == TRI_SINGLE) {
+                            n_buf += (uint32_t)__popcll(hm);
+                            const bool full = n_buf > (uint32_t)kTriRec - kWave;
+                            if (n_buf - n_done >= (uint32_t)kWave || full) {         // 64 or more are waiting (or the buffer is full): one dense pass over all of them
+                                drain(n_done, n_buf, true, spilled);
+                                n_done = n_buf;
+                            }
+                            if (full) {
+                                // the sub-range's records leave LDS: to the wavefront's scratch while that has room; without it the
+                                // sub-range gives up its dense block -- everything kept so far, and what follows, become records
+                                if (!spilled && scr && n_scr + n_buf <= kScratchRec) {
+                                    for (uint32_t y = (uint32_t)lane; y < n_buf; y += kWave) scr[n_scr + y] = s_rec[y];
+                                    n_scr += n_buf;
+                                    if (lane == 0) atomicAdd(dense_cursor + 1, 1ull);     // statistics
+                                } else if (!spilled) {
+                                    drain(0, n_buf, false, true);
+                                    spilled = true;
+                                }
+                                n_buf = 0; n_done = 0;
+                            }
+                        }
                     }
+                    __builtin_amdgcn_wave_barrier();
                 }
             }
-            search_cands(p0);                                  // (the parked candidates name their edge by its lane in THIS batch)
         }
         if (!staged) {
             flush_tris();
             if (MODE == TRI_SINGLE && part == 0u) for (uint32_t k = (uint32_t)lane; k < E; k += kWave) { own[S0 + k] = 0u; ownoff[S0 + k] = kOwnSpill; }
             continue;
         }
-        if (MODE == TRI_SINGLE) { drain(n_done, n_rec, true, spilled); n_done = n_rec; }
+        if (MODE == TRI_SINGLE) { drain(n_done, n_buf, true, spilled); n_done = n_buf; }
         bool to_dense = MODE == TRI_SINGLE && !spilled;              // wave-uniform
         unsigned long long base = 0;
         if (to_dense) {
@@ -373,10 +388,10 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
         if (to_dense) {
             __builtin_amdgcn_wave_barrier();
             for (uint32_t k = (uint32_t)lane; k < E; k += kWave) { own[S0 + k] = s_cnt[k]; ownoff[S0 + k] = base + (uint32_t)s_col[k]; }
-            for (uint32_t b0 = 0; b0 < n_rec + n_scr; b0 += kWave) {
+            for (uint32_t b0 = 0; b0 < n_buf + n_scr; b0 += kWave) {
                 const uint32_t x = b0 + (uint32_t)lane;
-                if (x < n_rec + n_scr) {
-                    const uint2 rc = x < n_rec ? s_rec[x] : scr[x - n_rec];
+                if (x < n_buf + n_scr) {
+                    const uint2 rc = x < n_buf ? s_rec[x] : scr[x - n_buf];
                     const uint32_t er = rc.x & 0xFFu, ir = (rc.x >> 8) & 0xFFu;
                     dense[base + (uint32_t)s_col[er] + ((rc.x >> 16) & 0xFFu)] = make_int2((int)(S0 + ir), (int)rc.y);
                     dense[base + (uint32_t)s_col[ir] + (rc.x >> 24)] = make_int2((int)(S0 + er), (int)rc.y);
@@ -384,14 +399,13 @@ __global__ __launch_bounds__(kBlock, KOMB_WEDGE_EU) void k_wedges(const uint32_t
             }
         } else {
             if (MODE == TRI_SINGLE && !spilled) {                // no room in the region: own-role entries of every record become records
-                drain(0, n_rec, false, true);
+                drain(0, n_buf, false, true);
                 for (uint32_t b0 = 0; b0 < n_scr; b0 += kWave) {
                     const uint32_t x = b0 + (uint32_t)lane;
                     const bool has = x < n_scr;
                     const uint2 rc = has ? scr[x] : make_uint2(0u, 0u);
                     const uint32_t e = S0 + (rc.x & 0xFFu), i = S0 + ((rc.x >> 8) & 0xFFu), jj = rc.y;
-                    rec_append(has, e, make_int2((int)i, (int)jj));
-                    rec_append(has, i, make_int2((int)e, (int)jj));
+                    emit(has, e, i, jj, false, true);
                 }
             }
             __builtin_amdgcn_wave_barrier();
