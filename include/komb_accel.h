@@ -120,7 +120,7 @@ int         komb_abi_version(void);
  * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
  * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), MAXIMAL_LDS,
  * MAXIMAL_PIVOT, MAXIMAL_LIST, MAXIMAL_DEBUG (komb_maximal_cliques_run, below), PERC_GROUP, PERC_DEBUG
- * (komb_clique_communities_run, below), BICONN_HEAVY (komb_biconnected_run, below), and the
+ * (komb_clique_communities_run, below), BICONN_HEAVY (komb_biconnected_run, below), GRAPHLET_SHORT, GRAPHLET_LDS, GRAPHLET_DEBUG (komb_graphlets_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -878,6 +878,46 @@ int komb_get_stats(komb_ctx *ctx, komb_stats *out);
  * inputs of the roofline model's algorithmic bytes; makes the k-truss preparation if absent).  No product path calls it
  * (until ABI version 7 every graph build ran this 2.2 ms kernel). */
 int komb_graph_moments(komb_ctx *ctx);
+
+/* ---- graphlet census: 3- and 4-vertex orbit counts --------------------- */
+/* The graphlet degree vector of Przulj ("Biological network comparison using graphlet degree distribution", Bioinformatics
+ * 2007), orbits 0-14 as ORCA and PGD number them, on the last COMPLETE k-truss result (whole graph or vmask).  d(v) is the
+ * number of result edges at v, t_e the support of canonical edge e (komb_truss_fetch_support).  Everything is an exact
+ * unsigned 64-bit count.
+ * Per canonical edge, [ne_sub] in canonical order (komb_graphlets_fetch_edges; either output may be NULL): cycles4[e] = the
+ * 4-cycles, induced or not, that contain e; cliques4[e] = the 4-cliques that contain e.  (The triangles through e are its support.)
+ * Per vertex (komb_graphlets_fetch_vertices): orbit[o * nv + v], orbit-major, o = 0 .. 14, the INDUCED subgraphs v lies in by
+ * the position it holds: 0 edge end | 1, 2 end and middle of a 2-path | 3 triangle | 4, 5 end and inner vertex of a 4-path |
+ * 6, 7 leaf and centre of a claw | 8 4-cycle | 9, 10, 11 the paw's pendant vertex, its two degree-2 triangle vertices, its
+ * degree-3 vertex | 12, 13 the diamond's degree-2 and degree-3 vertices | 14 4-clique.  A vertex outside the result has fifteen zeros.
+ * komb_graphlets_info: total[9] = the induced graphlets of the result -- edge, wedge, triangle, path4, claw, cycle4, paw,
+ * diamond, clique4 -- summed in 128 bits and reported saturating at 2^64 - 1 (flags has KOMB_GRAPHLET_SATURATED when one did);
+ * max_degree = the largest d(v); cycle_items = the entries the 4-cycle pass walked, sum over the vertices v, over their
+ * neighbours u below v in (d, id) order, of the neighbours of u below v; n_triangles, n_cliques4 = total[2], total[8]
+ * (saturating at 2^63 - 1); ms = the device time of the run on the context's HIP-event timer.  Any output may be NULL.
+ * No context or no graph loaded: KOMB_ERR_ARG, nothing is written.  Without a completed k-truss result on this graph, after
+ * komb_truss_run_slice / a sharded run that materialised only part of the canonical edges, after komb_truss_unprepare, fetch /
+ * info before a run: KOMB_ERR_STATE.  A largest degree of 2^20 or more: KOMB_ERR_LIMIT, before anything is counted (below
+ * it every count and every intermediate of the closed forms stays under 2^63: DESIGN.md section 4.6o).  A pool failure:
+ * KOMB_ERR_NOMEM.  A result without edges has zeros everywhere; the empty graph is not an error.  Canonical endpoints and
+ * supports of a whole-graph result that no fetch has asked for yet are made here as those fetches make them.
+ * The result lives in arrays of its own, installed when a run has succeeded: a refused or failed run (KOMB_ERR_LIMIT,
+ * KOMB_ERR_NOMEM, KOMB_ERR_DEVICE) leaves the PREVIOUS graphlet result readable and every other result as it was.  It indexes one k-truss
+ * result: whatever replaces or drops that result -- a new k-truss run of any kind, komb_truss_unprepare, a graph load --
+ * drops it too.  No other call changes or drops it; a run changes no other result, no komb_stats field and not the resident
+ * k-truss preparation, and needs no nucleus run.
+ * Options (none changes a result): GRAPHLET_SHORT=<n>: a root of the 4-cycle pass that walks up to n entries stays with one
+ * wavefront (default and at most 128); GRAPHLET_LDS=<n>: up to n entries its table lives in a workgroup's LDS, above in
+ * global scratch (default and at most 4096; 0 sends every root to global scratch); GRAPHLET_DEBUG: one stderr line with the
+ * per-pass counts and device times. */
+#define KOMB_GRAPHLET_ORBITS 15
+#define KOMB_GRAPHLET_TYPES  9
+#define KOMB_GRAPHLET_SATURATED 1
+int komb_graphlets_run(komb_ctx *ctx);
+int komb_graphlets_fetch_vertices(komb_ctx *ctx, uint64_t *orbit /*[15 * nv]*/);
+int komb_graphlets_fetch_edges(komb_ctx *ctx, uint64_t *cycles4, uint64_t *cliques4 /*[ne_sub] each, either may be NULL*/);
+int komb_graphlets_info(komb_ctx *ctx, uint64_t *total /*[9]*/, int32_t *flags, int32_t *max_degree,
+                        int64_t *cycle_items, int64_t *n_triangles, int64_t *n_cliques4, double *ms);   /* any may be NULL */
 
 /* ---- synthetic workload (host code, no device) ------------------------- */
 /* Power-law "hybrid unitig graph" generator of SURVEY.md section 8(d): a union

@@ -44,7 +44,7 @@ OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
                 "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "CENSUS_LDS", "CENSUS_PIVOT",
                 "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "PERC_GROUP", "PERC_DEBUG", "BICONN_HEAVY",
-                "POISON")
+                "GRAPHLET_LDS", "GRAPHLET_SHORT", "GRAPHLET_DEBUG", "POISON")
 
 # (ALLOC_FAIL_AT / ALLOC_TRIM_AT are one-shot triggers counted from the moment they are set: they are NOT forwarded -- forwarding
 # would re-arm them before every call; a test sets them with set_option)
@@ -539,6 +539,45 @@ class KombAccel:
         """(label, size, role, sim_deg) of the structural clustering of the last k-truss result."""
         self.structural_clusters_run(eps_num, eps_den, mu)
         return self.structural_clusters_fetch()
+
+    # ---- graphlet census: 3- and 4-vertex orbit counts of the last k-truss result (include/komb_accel.h)
+    GRAPHLET_TYPES = ("edge", "wedge", "triangle", "path4", "claw", "cycle4", "paw", "diamond", "clique4")
+
+    def graphlets_run(self):
+        """Needs a complete k-truss result on this graph."""
+        self._sync_env_options()
+        self._check(self._lib.komb_graphlets_run(self._ctx))
+
+    def graphlets_fetch_vertices(self):
+        """orbit uint64[15, nv]: orbit[o, v] = the induced 3- and 4-vertex subgraphs v lies in at orbit o (Przulj's 0-14)."""
+        orbit = _out_u64(_lib.KOMB_GRAPHLET_ORBITS * max(self.nv, 0))
+        self._check(self._lib.komb_graphlets_fetch_vertices(self._ctx, ptr(orbit)))
+        return orbit.reshape(_lib.KOMB_GRAPHLET_ORBITS, max(self.nv, 0))
+
+    def graphlets_fetch_edges(self):
+        """(cycles4, cliques4) uint64[ne_sub], in the canonical edge order of the k-truss result."""
+        self._check(self._lib.komb_graphlets_info(self._ctx, *([None] * 7)))    # (the census' own errors first)
+        n = ctypes.c_int64()
+        self._check(self._lib.komb_truss_count(self._ctx, ctypes.byref(n)))
+        cycles4, cliques4 = _out_u64(max(n.value, 0)), _out_u64(max(n.value, 0))
+        self._check(self._lib.komb_graphlets_fetch_edges(self._ctx, ptr(cycles4), ptr(cliques4)))
+        return cycles4, cliques4
+
+    def graphlets_info(self):
+        """{"total": {graphlet: count}, "flags", "max_degree", "cycle_items", "n_triangles", "n_cliques4", "ms"} of the last run."""
+        total = (ctypes.c_uint64 * _lib.KOMB_GRAPHLET_TYPES)()
+        flags, maxd = ctypes.c_int32(), ctypes.c_int32()
+        items, tri, clq, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        self._check(self._lib.komb_graphlets_info(self._ctx, total, ctypes.byref(flags), ctypes.byref(maxd), ctypes.byref(items),
+                                                  ctypes.byref(tri), ctypes.byref(clq), ctypes.byref(ms)))
+        return {"total": dict(zip(self.GRAPHLET_TYPES, (int(x) for x in total))), "flags": flags.value, "max_degree": maxd.value,
+                "cycle_items": items.value, "n_triangles": tri.value, "n_cliques4": clq.value, "ms": ms.value}
+
+    def run_graphlets(self):
+        """(orbit, cycles4, cliques4, info) of the graphlet census of the last k-truss result."""
+        self.graphlets_run()
+        cycles4, cliques4 = self.graphlets_fetch_edges()
+        return self.graphlets_fetch_vertices(), cycles4, cliques4, self.graphlets_info()
 
     # ---- (3,4)-nucleus decomposition: triangles of the last k-truss result peeled by their 4-cliques (include/komb_accel.h)
     NUCLEUS_FIELDS = ("a", "b", "c", "key0", "theta")

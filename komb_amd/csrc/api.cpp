@@ -90,6 +90,7 @@ static_assert(KOMB_COMM_K_MAX == KOMB_BICONN_K_MAX, "resolve_truss_k serves both
 #define NO_BC "no blocks of the current k-truss result"
 #define NO_DENS "komb_densest_subgraph_run has not completed on this graph"
 #define NO_SC "no structural clustering of the current k-truss result"
+#define NO_GL "no graphlet census of the current k-truss result"
 #define NO_NUC "no nucleus decomposition of the current k-truss result"
 #define NO_MC "no maximum-clique search of the current k-truss result"
 #define NO_CC "no clique census of the current k-truss result"
@@ -531,6 +532,43 @@ int komb_structural_clusters_info(komb_ctx *ctx, int32_t *eps_num, int32_t *eps_
     if (n_outliers) *n_outliers = r.n_outliers;
     if (n_clusters) *n_clusters = r.n_clusters;
     if (largest) *largest = r.largest;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
+int komb_graphlets_run(komb_ctx *ctx)
+{
+    KOMB_HIER_ENTER(ctx, "komb_graphlets_run");
+    KOMB_TRY(require_full_truss(ctx, "komb_graphlets_run"));
+    return graphlets_run(ctx);
+}
+
+int komb_graphlets_fetch_vertices(komb_ctx *ctx, uint64_t *orbit)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_graphlets_fetch_vertices", ctx->gl.done, NO_GL);
+    return fetch(ctx, orbit, ctx->gl.orbit, (size_t)KOMB_GRAPHLET_ORBITS * (size_t)ctx->nv);
+}
+
+int komb_graphlets_fetch_edges(komb_ctx *ctx, uint64_t *cycles4, uint64_t *cliques4)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_graphlets_fetch_edges", ctx->gl.done, NO_GL);
+    const size_t m = ctx->t_ne > 0 && ctx->nv > 0 ? (size_t)ctx->t_ne : 0;
+    KOMB_TRY(fetch(ctx, cycles4, ctx->gl.cycles4, m));
+    KOMB_TRY(fetch(ctx, cliques4, ctx->gl.cliques4, m));
+    return KOMB_OK;
+}
+
+int komb_graphlets_info(komb_ctx *ctx, uint64_t *total, int32_t *flags, int32_t *max_degree, int64_t *cycle_items,
+                        int64_t *n_triangles, int64_t *n_cliques4, double *ms)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_graphlets_info", ctx->gl.done, NO_GL);
+    const komb_ctx::Graphlets &r = ctx->gl;
+    if (total) memcpy(total, r.total, sizeof(r.total));
+    if (flags) *flags = r.flags;
+    if (max_degree) *max_degree = r.max_degree;
+    if (cycle_items) *cycle_items = r.cycle_items;
+    if (n_triangles) *n_triangles = r.n_triangles;
+    if (n_cliques4) *n_cliques4 = r.n_cliques4;
     if (ms) *ms = r.ms;
     return KOMB_OK;
 }

@@ -439,6 +439,20 @@ struct komb_ctx {
         bool done = false;
     } sc;
 
+    // ---- graphlet census (graphlets.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
+    // computed from and dropped with it (truss_free)
+    struct Graphlets {
+        DevArr<unsigned long long> orbit;    // [15 * nv] orbit-major: orbit[o * nv + v], ORIGINAL ids
+        DevArr<unsigned long long> cycles4;  // [t_ne] 4-cycles (induced or not) through the canonical edge
+        DevArr<unsigned long long> cliques4; // [t_ne] 4-cliques through the canonical edge
+        uint64_t total[KOMB_GRAPHLET_TYPES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // induced graphlet counts, saturating
+        int32_t flags = 0, max_degree = 0;
+        int64_t cycle_items = 0, n_triangles = 0, n_cliques4 = 0;
+        int64_t n_wave = 0, n_lds = 0, n_heavy = 0;      // roots of the 4-cycle pass by tier (option GRAPHLET_DEBUG prints them)
+        double ms = 0.0, ms_cycles = 0.0, ms_tri = 0.0, ms_vertex = 0.0;   // device time of the last run | of its passes (HIP events)
+        bool done = false;
+    } gl;
+
     // ---- (3,4)-nucleus decomposition (nucleus.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
     struct Nucleus {
@@ -736,6 +750,7 @@ int community_hierarchy_run(komb_ctx *ctx);                   // community_hiera
 int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null
 int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu);   // structural.hip: the parameters and the k-truss result it needs checked by the caller
 int structural_fetch_edges(komb_ctx *ctx, int32_t *similar);  // structural.hip: similar[] of the last run as 0 | 1 words (host output)
+int graphlets_run(komb_ctx *ctx);                             // graphlets.hip: the k-truss result it needs checked by the caller
 int nucleus_run(komb_ctx *ctx);                               // nucleus.hip: the k-truss result it needs checked by the caller
 int nucleus_hierarchy_run(komb_ctx *ctx);                     // nucleus_hierarchy.hip: the nucleus result it needs checked by the caller
 int nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null

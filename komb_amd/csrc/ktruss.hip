@@ -281,6 +281,7 @@ void truss_free(komb_ctx *ctx)
     ctx->ch = {};                            // (so do the community hierarchy's reps and node[])
     ctx->bc = {};                            // (and the blocks' reps and block[])
     ctx->sc = {};                            // (and the structural clustering's similar[]; its d and sim_deg are this result's)
+    ctx->gl = {};                            // (and the graphlet census' cycles4[] / cliques4[]; its orbits count this result's edges)
     nucleus_drop(ctx);                       // (and the nucleus decomposition's triangles and edge_theta[], with its hierarchy)
     ctx->mc = {};                            // (and the maximum cliques: they are this result's)
     ctx->cc = {};                            // (and the clique census)

@@ -33,10 +33,11 @@ __device__ __forceinline__ unsigned long long nuc_below(int lane) { return (1ull
 // row c.  [it, it + n) is the shortest and is walked; the other two are searched.
 struct NucTails { uint32_t it, n, lo1, hi1, lo2, hi2; };
 
-__device__ __forceinline__ NucTails nuc_tails(const NucTri &o, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t t)
+// the triangle given by value: its vertices and the positions of (a, c) and (b, c)
+__device__ __forceinline__ NucTails nuc_tails(int32_t a, int32_t b, int32_t c, uint32_t pac, uint32_t pbc, const uint32_t *__restrict__ rs,
+                                              const uint32_t *__restrict__ re)
 {
-    const int32_t a = o.a[t], b = o.b[t], c = o.c[t];
-    const uint32_t al = o.pac[t] + 1, ah = re[a], bl = o.pbc[t] + 1, bh = re[b], cl = rs[c], ch = re[c];
+    const uint32_t al = pac + 1, ah = re[a], bl = pbc + 1, bh = re[b], cl = rs[c], ch = re[c];
     const uint32_t na = ah - al, nb = bh - bl, nc = ch - cl;
     NucTails s;
     if (na <= nb && na <= nc) { s.it = al; s.n = na; s.lo1 = bl; s.hi1 = bh; s.lo2 = cl; s.hi2 = ch; }
@@ -45,11 +46,26 @@ __device__ __forceinline__ NucTails nuc_tails(const NucTri &o, const uint32_t *_
     return s;                                            // (the walked tail is the shortest: an empty tail gives n = 0)
 }
 
-// entry x of the walked tail: a 4-clique iff its vertex d is in the other two tails as well
-__device__ __forceinline__ bool nuc_clq_entry(const int32_t *__restrict__ ev, const NucTails &s, uint32_t x)
+__device__ __forceinline__ NucTails nuc_tails(const NucTri &o, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t t)
+{
+    return nuc_tails(o.a[t], o.b[t], o.c[t], o.pac[t], o.pbc[t], rs, re);
+}
+
+// entry x of the walked tail: a 4-clique iff its vertex d is in the other two tails as well; p1 / p2: where it is in them
+// (with x itself the positions of (a, d), (b, d), (c, d) in some order), valid only when it returns true
+__device__ __forceinline__ bool nuc_clq_entry(const int32_t *__restrict__ ev, const NucTails &s, uint32_t x, uint32_t *p1, uint32_t *p2)
 {
     const int32_t d = ev[x];
-    return nuc_find(ev, d, s.lo1, s.hi1) != kNucNone && nuc_find(ev, d, s.lo2, s.hi2) != kNucNone;
+    *p1 = nuc_find(ev, d, s.lo1, s.hi1);
+    if (*p1 == kNucNone) return false;
+    *p2 = nuc_find(ev, d, s.lo2, s.hi2);
+    return *p2 != kNucNone;
+}
+
+__device__ __forceinline__ bool nuc_clq_entry(const int32_t *__restrict__ ev, const NucTails &s, uint32_t x)
+{
+    uint32_t p1, p2;
+    return nuc_clq_entry(ev, s, x, &p1, &p2);
 }
 
 } // namespace komb

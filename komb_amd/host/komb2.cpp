@@ -77,6 +77,14 @@
 //                       cores, or - for a hub / an outlier; ClusterSize its number of unitigs (0 then);
 //                       SimilarNeighbours the unitig's number of similar edges.  VIDs depend on -t, so only the
 //                       partition by Name compares between runs.  Nothing else changes.
+//   KOMB_GRAPHLETS=1|edges  also write the graphlet census (komb_graphlets_run) of a whole-graph k-truss run of its own, made
+//                       before the KOMB_TRUSS stage, which then runs on the max core exactly as without it.
+//                       graphlet_orbits.tsv: #VID, Name, O0 .. O14 -- one row per unitig in VID order, the induced 3- and
+//                       4-vertex subgraphs it lies in by orbit (Przulj's numbering).  graphlet_census.tsv: #Graphlet, Count
+//                       -- edge, wedge, triangle, path4, claw, cycle4, paw, diamond, clique4.  With edges also
+//                       graphlet_edges.tsv: #U, V, Triangles, Cycles4, Cliques4 -- one row per edge in canonical order, the
+//                       unitigs by Name.  Any other value is a usage error.  VIDs depend on -t, so only the tables by Name
+//                       compare between runs.  Nothing else changes.
 //   KOMB_NUCLEUS=1      with KOMB_TRUSS=1: also write, after the truss stage, the (3,4)-nucleus decomposition of its result
 //                       (komb_nucleus_run: triangles peeled by the 4-cliques they lie in).  nucleus_triangles.tsv:
 //                       #Name_A, Name_B, Name_C, Cliques, Theta -- one row per triangle in triangle order (ascending VIDs),
@@ -711,6 +719,76 @@ void write_structural(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t m
         buf.push_back('\t');
         if (label[(size_t)i] >= 0) buf.append(names.name[(size_t)label[(size_t)i]]); else buf.push_back('-');
         len = snprintf(tmp, sizeof(tmp), "\t%d\t%d\n", (int)size[(size_t)i], (int)simdeg[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
+// KOMB_GRAPHLETS: a whole-graph k-truss run of its own and komb_graphlets_run on it: the orbits, one row per vertex in VID order,
+// the nine totals and, with with_edges, the three per-edge counts in canonical order
+void write_graphlets(komb_ctx *ctx, bool with_edges, const std::string &outdir, const Names &names, int64_t nv, int threads)
+{
+    static const char *const kType[KOMB_GRAPHLET_TYPES] = {"edge", "wedge", "triangle", "path4", "claw", "cycle4", "paw", "diamond", "clique4"};
+    std::vector<uint64_t> orbit((size_t)KOMB_GRAPHLET_ORBITS * (size_t)nv), cyc, clq;
+    std::vector<int32_t> eu, ev, sup;
+    uint64_t total[KOMB_GRAPHLET_TYPES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t ne = 0;
+    if (nv > 0) {
+        int rc = komb_truss_run(ctx, nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_truss_run", rc);
+        rc = komb_graphlets_run(ctx);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_graphlets_run", rc);
+        rc = komb_graphlets_fetch_vertices(ctx, orbit.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_graphlets_fetch_vertices", rc);
+        rc = komb_graphlets_info(ctx, total, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_graphlets_info", rc);
+        if (with_edges) {
+            komb_truss_count(ctx, &ne);
+            eu.resize((size_t)ne); ev.resize((size_t)ne); sup.resize((size_t)ne); cyc.resize((size_t)ne); clq.resize((size_t)ne);
+            rc = komb_truss_fetch(ctx, eu.data(), ev.data(), nullptr);
+            if (rc != KOMB_OK) die_accel(ctx, "komb_truss_fetch", rc);
+            rc = komb_truss_fetch_support(ctx, sup.data());
+            if (rc != KOMB_OK) die_accel(ctx, "komb_truss_fetch_support", rc);
+            rc = komb_graphlets_fetch_edges(ctx, cyc.data(), clq.data());
+            if (rc != KOMB_OK) die_accel(ctx, "komb_graphlets_fetch_edges", rc);
+        }
+    }
+    std::string path = outdir + "/graphlet_orbits.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName");
+    for (int o = 0; o < KOMB_GRAPHLET_ORBITS; ++o) fprintf(fp, "\tO%d", o);
+    fprintf(fp, "\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        char tmp[48];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        for (int o = 0; o < KOMB_GRAPHLET_ORBITS; ++o) {
+            len = snprintf(tmp, sizeof(tmp), "\t%llu", (unsigned long long)orbit[(size_t)o * (size_t)nv + (size_t)i]);
+            buf.append(tmp, (size_t)len);
+        }
+        buf.push_back('\n');
+    });
+    fclose(fp);
+    path = outdir + "/graphlet_census.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Graphlet\tCount\n");
+    for (int i = 0; i < KOMB_GRAPHLET_TYPES; ++i) fprintf(fp, "%s\t%llu\n", kType[i], (unsigned long long)total[i]);
+    fclose(fp);
+    if (!with_edges) return;
+    path = outdir + "/graphlet_edges.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#U\tV\tTriangles\tCycles4\tCliques4\n");
+    write_rows(fp, ne, threads, [&](int64_t i, std::string &buf) {
+        char tmp[96];
+        buf.append(names.name[(size_t)eu[(size_t)i]]);
+        buf.push_back('\t');
+        buf.append(names.name[(size_t)ev[(size_t)i]]);
+        const int len = snprintf(tmp, sizeof(tmp), "\t%d\t%llu\t%llu\n", (int)sup[(size_t)i], (unsigned long long)cyc[(size_t)i],
+                                 (unsigned long long)clq[(size_t)i]);
         buf.append(tmp, (size_t)len);
     });
     fclose(fp);
@@ -1657,6 +1735,18 @@ int main(int argc, const char **argv)
             leave(EXIT_FAILURE);
         }
         write_structural(ctx, (int32_t)num, (int32_t)den, (int32_t)mu, args.outdir, names, nv, args.threads);
+    }
+
+    // graphlet census of the whole graph (no counterpart in the reference; opt-in): KOMB_GRAPHLETS=1 | edges.  Like the
+    // structural clustering it makes a whole-graph k-truss run of its own before the truss stage below.
+    const char *gl_env = getenv("KOMB_GRAPHLETS");
+    if (gl_env && *gl_env) {
+        const bool gl_edges = !strcmp(gl_env, "edges");
+        if (!gl_edges && strcmp(gl_env, "1") != 0) {
+            fprintf(stderr, "komb2: KOMB_GRAPHLETS=%s: expected 1 or edges\n", gl_env);
+            leave(EXIT_FAILURE);
+        }
+        write_graphlets(ctx, gl_edges, args.outdir, names, nv, args.threads);
     }
 
     // runTruss (src/graph.cpp:486-563) -- disabled in the reference at :478, opt-in here
