@@ -23,7 +23,7 @@
 //     a complete run's outputs do not depend on the scheduling.  Both are read by the host after the launch.
 //   * nodes: as in the search, batches of at most 256 per wave to one counter that every node reads; a wave that finds the budget
 //     spent stops.  What was added by then is a lower bound: every leaf adds real cliques, none twice.
-// The launches of a run: k_clq_tmax, k_clq_rows; k_cc_census in count mode (the largest |P| at need k_lo, which sizes the scratch
+// The launches of a run: k_clq_tmax, k_rows; k_cc_census in count mode (the largest |P| at need k_lo, which sizes the scratch
 // slots and the LDS; above 4096 the run is refused) and in run mode; k_cc_saturated.  No workgroup waits for another.
 #include "clique_root_dev.h"
 

@@ -15,8 +15,7 @@
 // The walks are the analyses' own.  DESIGN.md sections 4.6j, 4.6k and 4.6l.
 #pragma once
 
-#include "common.h"
-#include "nucleus_search_dev.h"
+#include "oriented_search_dev.h"
 
 #include <algorithm>
 
@@ -38,15 +37,6 @@ struct ClqGraph {
     const uint32_t *rs, *re;
 };
 
-static __global__ void k_clq_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= m) return;
-    const int32_t u = eu[j];
-    if (j == 0 || eu[j - 1] != u) rs[u] = j;
-    if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
-}
-
 __device__ __forceinline__ unsigned long long clq_shfl64(unsigned long long x, int src)
 {
     const uint32_t lo = (uint32_t)__shfl((int32_t)(uint32_t)x, src), hi = (uint32_t)__shfl((int32_t)(uint32_t)(x >> 32), src);
@@ -64,16 +54,6 @@ __device__ __forceinline__ int clq_sum(int x)
 {
     for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off);
     return x;
-}
-
-// the first position of [lo, hi) whose entry is not below x
-__device__ __forceinline__ uint32_t clq_lower(const int32_t *__restrict__ a, int32_t x, uint32_t lo, uint32_t hi)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // |P| of the root rj = (a, b): the shorter of (row a behind rj, row b) is walked 64 entries at a time, the other bisected; both
@@ -155,7 +135,7 @@ __device__ __forceinline__ uint32_t clq_cut_x(const ClqGraph &G, const ClqLower 
 {
     const int32_t a = G.eu[rj], b = G.ev[rj];
     const uint32_t lb = L.ls[b], le = L.le[b];
-    const uint32_t ia = clq_lower(L.lu, a, lb, le);      // (a itself is in the lower row of b: the edge rj)
+    const uint32_t ia = row_lower(L.lu, a, lb, le);      // (a itself is in the lower row of b: the edge rj)
     const uint32_t behind = ia < le ? ia + 1 : le;
     uint32_t n = clq_meet(G.tr, ClqSpan{L.lu, L.lpos, L.ls[a], L.le[a]}, ClqSpan{L.lu, L.lpos, lb, ia}, need, X, 0u, cap_x, fill, lane);
     n = clq_meet(G.tr, ClqSpan{G.ev, nullptr, G.rs[a], rj}, ClqSpan{L.lu, L.lpos, behind, le}, need, X, n, cap_x, fill, lane);
@@ -180,7 +160,7 @@ __device__ __forceinline__ void clq_matrix(const ClqGraph &G, uint32_t need, con
     for (uint32_t i = 0; i + 1 < n; ++i) {
         const int32_t c = P[i];
         const uint32_t ce = G.re[c];
-        const uint32_t cs = clq_lower(ev, P[i + 1], G.rs[c], ce);   // (row c is above c; what is below P[i + 1] is not in P)
+        const uint32_t cs = row_lower(ev, P[i + 1], G.rs[c], ce);   // (row c is above c; what is below P[i + 1] is not in P)
         for (uint32_t x0 = cs; x0 < ce; x0 += kWave) {
             const uint32_t x = x0 + (uint32_t)lane;
             bool past = false;
@@ -188,7 +168,7 @@ __device__ __forceinline__ void clq_matrix(const ClqGraph &G, uint32_t need, con
                 const int32_t dd = ev[x];
                 if (dd > p_last) past = true;
                 else if ((uint32_t)tr[x] >= need) {
-                    const uint32_t pos = clq_lower(P, dd, i + 1, n);
+                    const uint32_t pos = row_lower(P, dd, i + 1, n);
                     if (pos < n && P[pos] == dd) {
                         atomicOr(m32 + ((size_t)i * W * 2 + (pos >> 5)), 1u << (pos & 31u));
                         atomicOr(m32 + ((size_t)pos * W * 2 + (i >> 5)), 1u << (i & 31u));
@@ -396,14 +376,8 @@ inline long long clq_opt(const komb_ctx *ctx, const char *name, long long dflt, 
 // the rows of the canonical list (m > 0 edges) of the last k-truss result
 inline int clq_rows(komb_ctx *ctx, DevBufs &bufs, ClqGraph *g)
 {
-    hipStream_t s = ctx->stream;
-    const size_t nv = (size_t)ctx->nv;
     uint32_t *d_rs = nullptr, *d_re = nullptr;
-    KOMB_HIP(ctx, bufs.alloc(&d_rs, nv));
-    KOMB_HIP(ctx, bufs.alloc(&d_re, nv));
-    KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, nv * sizeof(uint32_t), s));
-    KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, nv * sizeof(uint32_t), s));
-    k_clq_rows<<<(int)((ctx->t_ne + kBlock - 1) / kBlock), kBlock, 0, s>>>(ctx->d_t_eu, (uint32_t)ctx->t_ne, d_rs, d_re);
+    KOMB_TRY(oriented_rows(ctx, bufs, ctx->d_t_eu, ctx->t_ne, nullptr, &d_rs, &d_re));
     KOMB_HIP(ctx, hipGetLastError());
     *g = ClqGraph{ctx->d_t_eu, ctx->d_t_ev, ctx->d_t_truss, d_rs, d_re};
     return KOMB_OK;

@@ -586,6 +586,13 @@ inline bool ctx_flag(const komb_ctx *ctx, const char *name)
     const char *v = ctx_opt(ctx, name);
     return v && strcmp(v, "0") != 0;
 }
+inline uint32_t ctx_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)      // a count or a length: 1 .. 2^31 - 1
+{
+    const char *e = ctx_opt(ctx, name);
+    if (!e) return dflt;
+    const unsigned long v = strtoul(e, nullptr, 10);
+    return v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
+}
 namespace komb {
 inline FinishMode finish_mode(const komb_ctx *ctx, FinishMode dflt)
 {

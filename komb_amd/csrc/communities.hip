@@ -5,10 +5,10 @@
 // and vmask runs alike.  The MEMBER edges (trussness >= k) are compacted in that order: member j is canonical edge
 // kept[j], with endpoints (mu[j], mv[j]).  The compacted list is itself an oriented CSR of the k-truss: row a = the
 // members with mu == a, [rs[a], re[a]), their mv ascending.  A triangle a < b < c of three members is found exactly
-// once, from its edge (a, b) = member j: c is in the part of row a behind j and in row b.  The lane walks the SHORTER of
-// the two and bisects the longer (sum over the edges of min(d(a), d(b)) <= 2 x arboricity x |E|: no orientation by
-// degree is needed for the bound), and a hit gives the three member ids as positions, without any lookup:
-// link(j, x), link(j, y) with x the position of (a, c) and y the position of (b, c).
+// once, from its edge (a, b) = member j: c is in the part of row a behind j and in row b.  The search is
+// oriented_search_dev.h's: the lane walks the SHORTER of the two and bisects the longer (sum over the edges of
+// min(d(a), d(b)) <= 2 x arboricity x |E|: no orientation by degree is needed for the bound), and a hit gives the three
+// member ids as positions, without any lookup: link(j, x), link(j, y) with x the position of (a, c) and y that of (b, c).
 //
 // The union-find is components.hip's (unionfind_dev.h) over member ids: hooks hang the larger root under the smaller,
 // walks go through strictly decreasing ids, and the root of a finished class is its smallest member id -- kept[] is
@@ -16,7 +16,7 @@
 // that file's header says about stale reads holds word for word for this parent[].  As there, a compressing flatten
 // launch is followed by a read-only labelling launch.  No workgroup waits for another; a call is a constant number of
 // launches; the one queue (edges whose shorter side is long) has room for every member edge.
-#include "common.h"
+#include "oriented_search_dev.h"
 #include "unionfind_dev.h"
 
 namespace komb {
@@ -58,41 +58,11 @@ __global__ void k_comm_compact(const int32_t *__restrict__ eu, const int32_t *__
     parent[j] = (int32_t)j; cnt[j] = 0u;
 }
 
-// row bounds per original vertex (rs / re zeroed before: a vertex without a row has an empty one)
-__global__ void k_comm_rows(const int32_t *__restrict__ mu, const uint32_t *__restrict__ n_mem, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x, nm = *n_mem;
-    if (j >= nm) return;
-    const int32_t u = mu[j];
-    if (j == 0 || mu[j - 1] != u) rs[u] = j;
-    if (j + 1 == nm || mu[j + 1] != u) re[u] = j + 1;
-}
-
-// the two sides of member j = (a, b): [it, it + n) is walked, [lo, hi) is searched; n <= hi - lo
-struct CommSides { uint32_t it, n, lo, hi; };
-
-__device__ __forceinline__ CommSides comm_sides(const int32_t *__restrict__ mu, const int32_t *__restrict__ mv,
-                                                const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t j)
-{
-    const int32_t a = mu[j], b = mv[j];
-    const uint32_t ab = j + 1, ae = re[a], bb = rs[b], be = re[b];   // (row a holds j: ae > j)
-    const uint32_t la = ae - ab, lb = be - bb;
-    CommSides s;
-    if (la <= lb) { s.it = ab; s.n = la; s.lo = bb; s.hi = be; }
-    else { s.it = bb; s.n = lb; s.lo = ab; s.hi = ae; }
-    if (s.hi == s.lo) s.n = 0;
-    return s;
-}
-
 // entry x of the walked side against the searched one [lo, end): a common third vertex closes a triangle of three members
 __device__ __forceinline__ void comm_entry(const int32_t *__restrict__ mv, int32_t *parent, uint32_t j, uint32_t x, uint32_t lo, uint32_t end)
 {
     const int32_t c = mv[x];
-    uint32_t hi = end;
-    while (lo < hi) {                         // first position of [lo, end) whose target is >= c
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (mv[mid] < c) lo = mid + 1; else hi = mid;
-    }
+    lo = row_lower(mv, c, lo, end);
     if (lo >= end || mv[lo] != c) return;
     comp_link(parent, (int32_t)j, (int32_t)x);       // (both positions are behind j: the edges (a, c) and (b, c))
     comp_link(parent, (int32_t)j, (int32_t)lo);
@@ -106,8 +76,8 @@ __global__ void k_comm_tri(const int32_t *__restrict__ mu, const int32_t *__rest
 {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
-    CommSides s{0, 0, 0, 0};
-    if (j < *n_mem) s = comm_sides(mu, mv, rs, re, j);
+    EdgeSides s{0, 0, 0, 0, true};
+    if (j < *n_mem) s = edge_sides(mu, mv, rs, re, j);
     bool act = s.n > 0;
     if (act && s.n >= n_heavy) {
         const uint32_t slot = atomicAdd(&ctl->n_heavy, 1u);
@@ -117,14 +87,11 @@ __global__ void k_comm_tri(const int32_t *__restrict__ mu, const int32_t *__rest
     const bool mid = act && s.n > n_short;
     if (act && !mid)
         for (uint32_t x = s.it; x < s.it + s.n; ++x) comm_entry(mv, parent, j, x, s.lo, s.hi);
-    unsigned long long m = __ballot(mid);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const uint32_t rj = (uint32_t)__shfl((int32_t)j, src), rit = (uint32_t)__shfl((int32_t)s.it, src), rn = (uint32_t)__shfl((int32_t)s.n, src);
-        const uint32_t rlo = (uint32_t)__shfl((int32_t)s.lo, src), rhi = (uint32_t)__shfl((int32_t)s.hi, src);
-        for (uint32_t x = rit + (uint32_t)lane; x < rit + rn; x += kWave) comm_entry(mv, parent, rj, x, rlo, rhi);
-    }
+    wave_turns(mid, [&](int src) {
+        const uint32_t rj = from_lane(j, src);
+        const EdgeSides r = from_lane(s, src);
+        wave_walk(r.it, r.n, lane, [&](uint32_t x) { comm_entry(mv, parent, rj, x, r.lo, r.hi); });
+    });
 }
 
 // the queued edges: block (x, y) takes the edges x, x + gridDim.x, ... and of each the entries y * kBlock + lane, stepping gridDim.y * kBlock
@@ -136,7 +103,7 @@ __global__ void k_comm_heavy(const int32_t *__restrict__ mu, const int32_t *__re
     const uint32_t t = blockIdx.y * kBlock + threadIdx.x, stride = gridDim.y * kBlock;
     for (uint32_t h = blockIdx.x; h < n; h += gridDim.x) {
         const uint32_t j = (uint32_t)heavy[h];
-        const CommSides s = comm_sides(mu, mv, rs, re, j);
+        const EdgeSides s = edge_sides(mu, mv, rs, re, j);
         for (uint32_t x = s.it + t; x < s.it + s.n; x += stride) comm_entry(mv, parent, j, x, s.lo, s.hi);
     }
 }
@@ -270,21 +237,13 @@ __global__ void k_comm_runs(const uint64_t *__restrict__ uk, uint32_t n, int32_t
     if (threadIdx.x == 0 && s_multi) atomicAdd(&ctl->n_multi, s_multi);
 }
 
-inline uint32_t comm_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
-{
-    const char *e = ctx_opt(ctx, name);
-    if (!e) return dflt;
-    const unsigned long v = strtoul(e, nullptr, 10);
-    return v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
-}
-
 } // namespace
 
 // k is checked and resolved by the caller (api.cpp): >= 2
 int communities_run(komb_ctx *ctx, int32_t k)
 {
     hipStream_t s = ctx->stream;
-    const int64_t m = ctx->t_ne, nv = ctx->nv;
+    const int64_t m = ctx->t_ne;
     ctx->comm = {};                                  // a run that fails leaves no result (include/komb_accel.h)
     komb_ctx::Communities res;                       // goes back to the pool unless it is installed
     res.k = k;
@@ -307,10 +266,8 @@ int communities_run(komb_ctx *ctx, int32_t k)
     KOMB_HIP(ctx, bufs.alloc(&d_mv, (size_t)m));
     KOMB_HIP(ctx, bufs.alloc(&d_parent, (size_t)m));
     KOMB_HIP(ctx, bufs.alloc(&d_heavy, (size_t)heavy_cap));
-    KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
-    KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
-    const uint32_t n_short = comm_opt_u32(ctx, "COMM_SHORT", kCommShort);    // (tests: every edge through the wave / the queued path)
-    uint32_t n_heavy = comm_opt_u32(ctx, "COMM_HEAVY", kCommHeavy);
+    const uint32_t n_short = ctx_opt_u32(ctx, "COMM_SHORT", kCommShort);    // (tests: every edge through the wave / the queued path)
+    uint32_t n_heavy = ctx_opt_u32(ctx, "COMM_HEAVY", kCommHeavy);
     if (n_heavy <= n_short) n_heavy = n_short + 1;
 
     const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *truss = ctx->d_t_truss;
@@ -319,12 +276,10 @@ int communities_run(komb_ctx *ctx, int32_t k)
     const int grid = comm_grid(m), grid1 = comm_grid(m + 1);
     ctx->timer.start(s);
     KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(CommCtl), s));
-    KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
-    KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
     k_comm_flag<<<grid1, kBlock, 0, s>>>(truss, (uint32_t)m, k, d_flag);
     KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
     k_comm_compact<<<grid, kBlock, 0, s>>>(eu, ev, truss, (uint32_t)m, k, d_pos, d_kept, d_mu, d_mv, d_parent, d_cnt);
-    k_comm_rows<<<grid, kBlock, 0, s>>>(d_mu, d_nm, d_rs, d_re);
+    KOMB_TRY(oriented_rows(ctx, bufs, d_mu, m, d_nm, &d_rs, &d_re));
     k_comm_tri<<<grid, kBlock, 0, s>>>(d_mu, d_mv, d_rs, d_re, d_nm, d_parent, d_ctl, d_heavy, heavy_cap, n_short, n_heavy);
     k_comm_heavy<<<dim3(kCommHeavyGrid, kCommHeavyChunks), kBlock, 0, s>>>(d_mu, d_mv, d_rs, d_re, d_parent, d_ctl, d_heavy, heavy_cap);
     // two passes: the first compresses, the second labels -- read-only walks of a step or two

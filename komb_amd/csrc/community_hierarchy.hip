@@ -1,9 +1,9 @@
 // community_hierarchy.hip -- the nesting forest of the k-truss communities over all k (komb_community_hierarchy_run): which
 // community of C_k lies inside which community of C_(k-1).  DESIGN.md section 4.6e; the definition is in include/komb_accel.h.
 //
-// communities.hip's member list and triangle search (the edges of trussness >= 3 compacted in canonical order, an oriented
-// CSR of its own; walk the shorter side, bisect the longer; the same three length classes) joined to the forest builder
-// (forest.hip; its header comment has CLAIM, ADOPT, the tail and why they are right).  What is this file's: the ITEMS are the
+// communities.hip's member list (the edges of trussness >= 3 compacted in canonical order, an oriented CSR of its own) and its
+// triangle search (oriented_search_dev.h: walk the shorter side, bisect the longer; the same three length classes) joined to
+// the forest builder (forest.hip; its header comment has CLAIM, ADOPT, the tail and why they are right).  This file's: the ITEMS are the
 // member edges, by position in the member list (kept[] is monotone, so kept[root] is the smallest canonical index), bucketed
 // by their own trussness; the LINKS are triangle records (j, x) and (j, y) of weight w = the smallest trussness of the
 // triangle's three edges -- the level at which the triangle starts to bind.  The triangles are enumerated ONCE into a record
@@ -14,8 +14,8 @@
 //
 // Why every node has a hooked member: a member of trussness k lies in a triangle of the k-truss, so it has a record of weight
 // exactly k; it was alone before, so the tree it ends the level in holds a member hooked at this level.
-// Every ballot sits in a loop whose bounds are uniform over its wave.
 #include "forest_dev.h"
+#include "oriented_search_dev.h"
 
 namespace komb {
 
@@ -65,43 +65,13 @@ __global__ void k_ch_compact(const int32_t *__restrict__ eu, const int32_t *__re
     claimk[j] = 0x7FFFFFFF;                  // the level that node was made at
 }
 
-// row bounds per original vertex (rs / re zeroed before: a vertex without a row has an empty one)
-__global__ void k_ch_rows(const int32_t *__restrict__ mu, const uint32_t *__restrict__ n_mem, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x, nm = *n_mem;
-    if (j >= nm) return;
-    const int32_t u = mu[j];
-    if (j == 0 || mu[j - 1] != u) rs[u] = j;
-    if (j + 1 == nm || mu[j + 1] != u) re[u] = j + 1;
-}
-
-// ---- the triangle search of communities.hip, counting or writing records
-
-// the two sides of member j = (a, b): [it, it + n) is walked, [lo, hi) is searched; n <= hi - lo
-struct ChSides { uint32_t it, n, lo, hi; };
-
-__device__ __forceinline__ ChSides ch_sides(const int32_t *__restrict__ mu, const int32_t *__restrict__ mv,
-                                            const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t j)
-{
-    const int32_t a = mu[j], b = mv[j];
-    const uint32_t ab = j + 1, ae = re[a], bb = rs[b], be = re[b];   // (row a holds j: ae > j)
-    const uint32_t la = ae - ab, lb = be - bb;
-    ChSides s;
-    if (la <= lb) { s.it = ab; s.n = la; s.lo = bb; s.hi = be; }
-    else { s.it = bb; s.n = lb; s.lo = ab; s.hi = ae; }
-    if (s.hi == s.lo) s.n = 0;
-    return s;
-}
+// ---- the triangle search, counting or writing records
 
 // entry x of the walked side against the searched one [lo, end): the position of the common third vertex there, or false
 __device__ __forceinline__ bool ch_search(const int32_t *__restrict__ mv, uint32_t x, uint32_t lo, uint32_t end, uint32_t *y)
 {
     const int32_t c = mv[x];
-    uint32_t hi = end;
-    while (lo < hi) {                         // first position of [lo, end) whose target is >= c
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (mv[mid] < c) lo = mid + 1; else hi = mid;
-    }
+    lo = row_lower(mv, c, lo, end);
     if (lo >= end || mv[lo] != c) return false;
     *y = lo;
     return true;
@@ -129,7 +99,7 @@ __device__ __forceinline__ void ch_emit(bool hit, uint32_t j, uint32_t x, uint32
     st.keys[slot + 1] = (uint32_t)w; st.vals[slot + 1] = ((unsigned long long)j << 32) | y;
 }
 
-// n entries from `it` on, entry i belongs to the lane with valid set; called by whole waves with a uniform trip count
+// entry x of member j's walked side, for the lane with valid set; called by whole waves
 template <bool kEmit>
 __device__ __forceinline__ void ch_entry(bool valid, uint32_t j, uint32_t x, uint32_t lo, uint32_t hi, const int32_t *__restrict__ mv,
                                          const int32_t *__restrict__ mt, ChCtl *ctl, const ChStream &st, uint32_t &found)
@@ -149,8 +119,8 @@ __global__ void k_ch_tri(const int32_t *__restrict__ mu, const int32_t *__restri
 {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
-    ChSides s{0, 0, 0, 0};
-    if (j < *n_mem) s = ch_sides(mu, mv, rs, re, j);
+    EdgeSides s{0, 0, 0, 0, true};
+    if (j < *n_mem) s = edge_sides(mu, mv, rs, re, j);
     bool act = s.n > 0;
     if (act && s.n >= n_heavy) {
         if (!kEmit) {
@@ -162,17 +132,13 @@ __global__ void k_ch_tri(const int32_t *__restrict__ mu, const int32_t *__restri
     const bool mid = act && s.n > n_short;
     uint32_t found = 0;
     const uint32_t own = act && !mid ? s.n : 0u;
-    const uint32_t top = wave_max(own);                       // (uniform: the ballots of ch_emit see the whole wave)
+    const uint32_t top = wave_max(own);
     for (uint32_t i = 0; i < top; ++i) ch_entry<kEmit>(i < own, j, s.it + i, s.lo, s.hi, mv, mt, ctl, st, found);
-    unsigned long long m = __ballot(mid);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const uint32_t rj = (uint32_t)__shfl((int32_t)j, src), rit = (uint32_t)__shfl((int32_t)s.it, src), rn = (uint32_t)__shfl((int32_t)s.n, src);
-        const uint32_t rlo = (uint32_t)__shfl((int32_t)s.lo, src), rhi = (uint32_t)__shfl((int32_t)s.hi, src);
-        for (uint32_t base = 0; base < rn; base += kWave)
-            ch_entry<kEmit>(base + (uint32_t)lane < rn, rj, rit + base + (uint32_t)lane, rlo, rhi, mv, mt, ctl, st, found);
-    }
+    wave_turns(mid, [&](int src) {
+        const uint32_t rj = from_lane(j, src);
+        const EdgeSides r = from_lane(s, src);
+        wave_walk_all(r.it, r.n, lane, [&](uint32_t x, bool in) { ch_entry<kEmit>(in, rj, x, r.lo, r.hi, mv, mt, ctl, st, found); });
+    });
     if (!kEmit) {
         found = wave_sum(found);
         if (lane == 0 && found) atomicAdd(&ctl->n_tri, (unsigned long long)found);
@@ -192,7 +158,7 @@ __global__ void k_ch_heavy(const int32_t *__restrict__ mu, const int32_t *__rest
     uint32_t found = 0;
     for (uint32_t h = blockIdx.x; h < n; h += gridDim.x) {
         const uint32_t j = (uint32_t)heavy[h];
-        const ChSides s = ch_sides(mu, mv, rs, re, j);
+        const EdgeSides s = edge_sides(mu, mv, rs, re, j);
         for (uint32_t base = 0; base < s.n; base += stride)      // (uniform per workgroup)
             ch_entry<kEmit>(base + t < s.n, j, s.it + base + t, s.lo, s.hi, mv, mt, ctl, st, found);
     }
@@ -251,14 +217,6 @@ __global__ void k_ch_labels(uint32_t m, int32_t k, const int32_t *__restrict__ e
     label[i] = lab; lsize[i] = sz;
 }
 
-inline uint32_t ch_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
-{
-    const char *e = ctx_opt(ctx, name);
-    if (!e) return dflt;
-    const unsigned long v = strtoul(e, nullptr, 10);
-    return v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
-}
-
 } // namespace
 
 // the state it needs is checked by the caller (api.cpp).  The result is built in blocks of its own and replaces the
@@ -266,7 +224,7 @@ inline uint32_t ch_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
 int community_hierarchy_run(komb_ctx *ctx)
 {
     hipStream_t s = ctx->stream;
-    const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0, nv = ctx->nv;
+    const int64_t m = ctx->t_ne > 0 ? ctx->t_ne : 0;
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));             // (a whole-graph result whose endpoints no fetch has asked for yet)
 
     Range r_all("komb_community_hierarchy_run");
@@ -280,8 +238,8 @@ int community_hierarchy_run(komb_ctx *ctx)
         const uint32_t levels = (uint32_t)top + 1u;              // level numbers 0 .. levels - 1
         const int bits = forest_bits(levels);
         const uint32_t heavy_cap = (uint32_t)m;                  // every member could be queued
-        const uint32_t n_short = ch_opt_u32(ctx, "COMM_SHORT", kChShort);      // (tests: every edge through the wave / the queued path)
-        uint32_t n_heavy = ch_opt_u32(ctx, "COMM_HEAVY", kChHeavy);
+        const uint32_t n_short = ctx_opt_u32(ctx, "COMM_SHORT", kChShort);      // (tests: every edge through the wave / the queued path)
+        uint32_t n_heavy = ctx_opt_u32(ctx, "COMM_HEAVY", kChHeavy);
         if (n_heavy <= n_short) n_heavy = n_short + 1;
 
         ChCtl *d_ctl = nullptr;
@@ -302,8 +260,6 @@ int community_hierarchy_run(komb_ctx *ctx)
         KOMB_HIP(ctx, bufs.alloc(&cur, (size_t)m));
         KOMB_HIP(ctx, bufs.alloc(&claimk, (size_t)m));
         KOMB_HIP(ctx, bufs.alloc(&d_heavy, (size_t)heavy_cap));
-        KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
-        KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
 
         const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *truss = ctx->d_t_truss;
         const uint32_t *d_nm = d_pos + m;                        // the number of members, on the device
@@ -311,12 +267,10 @@ int community_hierarchy_run(komb_ctx *ctx)
         const int grid = forest_grid(m);
         ctx->timer.start(s);
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(ChCtl), s));
-        KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
-        KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
         k_ch_flag<<<forest_grid(m + 1), kBlock, 0, s>>>(truss, (uint32_t)m, d_flag);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
         k_ch_compact<<<grid, kBlock, 0, s>>>(eu, ev, truss, (uint32_t)m, levels, d_pos, kept, mu, mv, mt, mkeys, mvals, parent, cnt, cur, claimk);
-        k_ch_rows<<<grid, kBlock, 0, s>>>(mu, d_nm, d_rs, d_re);
+        KOMB_TRY(oriented_rows(ctx, bufs, mu, m, d_nm, &d_rs, &d_re));
         // the counting launch: the triangles of the result (an edge of a triangle has trussness >= 3: all of them are found here)
         const ChStream none{nullptr, nullptr, 0u};
         k_ch_tri<false><<<grid, kBlock, 0, s>>>(mu, mv, mt, d_rs, d_re, d_nm, d_ctl, d_heavy, heavy_cap, n_short, n_heavy, none);

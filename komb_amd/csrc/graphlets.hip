@@ -21,10 +21,10 @@
 //      A table holds at most as many keys as the root walks entries, and the thresholds are clamped to half the slots, so a
 //      probe sequence always ends.
 //   2. triangles (k_gl_tri): every triangle a < b < c once, from its edge (a, b) over the oriented canonical rows, the shorter
-//      side walked and the longer one bisected (nuc_find).  Per triangle D2[x] += sup(opposite edge) - 1 for its three
-//      vertices, and the 4-cliques with a fourth vertex above c (nuc_tails, nuc_clq_entry): each adds 1 to its six edges
-//      directly -- the three of the triangle summed up first -- so no triangle is stored and there is no triangle or clique
-//      limit (the nucleus decomposition numbers both and has one).
+//      side walked and the longer one bisected (oriented_search_dev.h: edge_sides, nuc_find).  Per triangle
+//      D2[x] += sup(opposite edge) - 1 for its three vertices, and the 4-cliques with a fourth vertex above c (nuc_tails,
+//      nuc_clq_entry): each adds 1 to its six edges directly -- the three of the triangle summed up first -- so no triangle
+//      is stored and there is no triangle or clique limit (the nucleus decomposition numbers both and has one).
 //   3. vertices: two sweeps over the edges that sum per-edge terms onto both ends (k_gl_edge1, k_gl_edge2: the eu end by a
 //      segmented sum inside the wave, the ev end by one atomic per edge and term), then the fifteen closed forms and the sums
 //      of the nine totals (k_gl_vertex).
@@ -32,8 +32,7 @@
 // Which word is written when: cycles4[] only by pass 1's atomics, cliques4[] and D2[] only by pass 2's, the sums of pass 3 by
 // its two sweeps, each read only by later launches.  All arithmetic is unsigned 64-bit; with every degree below 2^20 no
 // exact value reaches 2^63 (DESIGN.md has the derivation), so the wrap-around of an intermediate difference cancels.
-#include "common.h"
-#include "nucleus_search_dev.h"
+#include "oriented_search_dev.h"
 
 namespace komb {
 
@@ -144,16 +143,6 @@ __global__ void k_gl_split(const uint64_t *__restrict__ skey, uint32_t n2, uint3
     if (i < n2) col[i] = (uint32_t)skey[i];
 }
 
-// the first position of col[lo, hi) (ascending) with a rank >= x
-__device__ __forceinline__ uint32_t gl_lower(const uint32_t *__restrict__ col, uint32_t lo, uint32_t hi, uint32_t x)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (col[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // entry i = (r, u): with u below r, plen[i] = the entries of row u below r, added to items[r]; else 0
 __global__ void k_gl_plen(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ col, const uint32_t *__restrict__ rowptr, uint32_t n2,
                           uint32_t *__restrict__ plen, u64 *items)
@@ -162,7 +151,7 @@ __global__ void k_gl_plen(const uint64_t *__restrict__ skey, const uint32_t *__r
     if (i >= n2) return;
     const uint32_t r = (uint32_t)(skey[i] >> 32), u = col[i];
     uint32_t p = 0;
-    if (u < r) { const uint32_t b = rowptr[u]; p = gl_lower(col, b, rowptr[u + 1], r) - b; }
+    if (u < r) { const uint32_t b = rowptr[u]; p = row_lower(col, r, b, rowptr[u + 1]) - b; }
     plen[i] = p;
     if (p) atomicAdd(items + r, (u64)p);
 }
@@ -273,7 +262,7 @@ __global__ void __launch_bounds__(kBlock) k_gl_cyc_wave(GlCsr g, const uint32_t 
     const uint32_t nw = gridDim.x * (kBlock / kWave);
     for (uint32_t i = blockIdx.x * (kBlock / kWave) + (uint32_t)wave; i < nq; i += nw) {   // (uniform per wave)
         const uint32_t r = queue[i], row = g.rowptr[r];
-        const uint32_t pre = gl_lower(g.col, row, g.rowptr[r + 1], r) - row;
+        const uint32_t pre = row_lower(g.col, r, row, g.rowptr[r + 1]) - row;
         gl_walk_lanes<0>(g, row, pre, lane, tab, cyc);
         gl_wave_sync();
         gl_walk_lanes<1>(g, row, pre, lane, tab, cyc);
@@ -293,7 +282,7 @@ __global__ void __launch_bounds__(kBlock) k_gl_cyc_lds(GlCsr g, const uint32_t *
     __syncthreads();
     for (uint32_t i = blockIdx.x; i < nq; i += gridDim.x) {                 // (uniform per workgroup)
         const uint32_t r = queue[i], row = g.rowptr[r];
-        const uint32_t pre = gl_lower(g.col, row, g.rowptr[r + 1], r) - row;
+        const uint32_t pre = row_lower(g.col, r, row, g.rowptr[r + 1]) - row;
         gl_walk_waves<0>(g, row, pre, wave, kBlock / kWave, lane, tab, cyc);
         __syncthreads();
         gl_walk_waves<1>(g, row, pre, wave, kBlock / kWave, lane, tab, cyc);
@@ -312,22 +301,12 @@ __global__ void __launch_bounds__(kBlock) k_gl_cyc_heavy(GlCsr g, const uint32_t
     if (i >= nq) return;
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t r = queue[i], row = g.rowptr[r];
-    const uint32_t pre = gl_lower(g.col, row, g.rowptr[r + 1], r) - row;
+    const uint32_t pre = row_lower(g.col, r, row, g.rowptr[r + 1]) - row;
     const GlDense tab{dense + (size_t)blockIdx.y * nv};
     gl_walk_waves<kPhase>(g, row, pre, blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave, gridDim.x * (kBlock / kWave), lane, tab, cyc);
 }
 
 // ---- pass 2: triangles and the 4-cliques above them
-
-// row bounds per original vertex over the oriented canonical rows (rs / re zeroed before: a vertex without a row has an empty one)
-__global__ void k_gl_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= m) return;
-    const int32_t u = eu[j];
-    if (j == 0 || eu[j - 1] != u) rs[u] = j;
-    if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
-}
 
 // triangle a < b < c with (a, b) at j, (a, c) at pac, (b, c) at pbc
 __device__ __forceinline__ void gl_triangle(const int32_t *__restrict__ ev, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re,
@@ -356,39 +335,24 @@ __global__ void k_gl_tri(const int32_t *__restrict__ eu, const int32_t *__restri
 {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
-    uint32_t it = 0, n = 0, lo = 0, hi = 0;
+    EdgeSides s{0, 0, 0, 0, true};
     int32_t a = 0, b = 0;
-    bool walk_a = true;
-    if (j < m && sup[j] > 0) {
-        a = eu[j]; b = ev[j];
-        const uint32_t ab = j + 1, ae = re[a], bb = rs[b], be = re[b];      // (row a holds j: ae > j)
-        const uint32_t la = ae - ab, lb = be - bb;
-        walk_a = la <= lb;
-        if (walk_a) { it = ab; n = la; lo = bb; hi = be; }
-        else { it = bb; n = lb; lo = ab; hi = ae; }
-        if (hi == lo) n = 0;
-    }
-    const bool mid = n > n_short;
+    if (j < m && sup[j] > 0) { a = eu[j]; b = ev[j]; s = edge_sides(eu, ev, rs, re, j); }
+    // entry x of edge ej = (ea, eb) with the sides e
+    const auto entry = [&](uint32_t ej, int32_t ea, int32_t eb, const EdgeSides &e, uint32_t x) {
+        const int32_t c = ev[x];
+        const uint32_t hit = nuc_find(ev, c, e.lo, e.hi);
+        if (hit != kNucNone) gl_triangle(ev, rs, re, sup, ea, eb, c, ej, e.walk_a ? x : hit, e.walk_a ? hit : x, d2, clq);
+    };
+    const bool mid = s.n > n_short;
     if (!mid)
-        for (uint32_t x = it; x < it + n; ++x) {
-            const int32_t c = ev[x];
-            const uint32_t hit = nuc_find(ev, c, lo, hi);
-            if (hit != kNucNone) gl_triangle(ev, rs, re, sup, a, b, c, j, walk_a ? x : hit, walk_a ? hit : x, d2, clq);
-        }
-    unsigned long long todo = __ballot(mid);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const uint32_t rj = (uint32_t)__shfl((int32_t)j, src), rit = (uint32_t)__shfl((int32_t)it, src), rn = (uint32_t)__shfl((int32_t)n, src);
-        const uint32_t rlo = (uint32_t)__shfl((int32_t)lo, src), rhi = (uint32_t)__shfl((int32_t)hi, src);
-        const bool rwa = __shfl((int32_t)walk_a, src) != 0;
+        for (uint32_t x = s.it; x < s.it + s.n; ++x) entry(j, a, b, s, x);
+    wave_turns(mid, [&](int src) {
+        const uint32_t rj = from_lane(j, src);
         const int32_t ra = __shfl(a, src), rb = __shfl(b, src);
-        for (uint32_t x = rit + (uint32_t)lane; x < rit + rn; x += kWave) {
-            const int32_t c = ev[x];
-            const uint32_t hit = nuc_find(ev, c, rlo, rhi);
-            if (hit != kNucNone) gl_triangle(ev, rs, re, sup, ra, rb, c, rj, rwa ? x : hit, rwa ? hit : x, d2, clq);
-        }
-    }
+        const EdgeSides r = from_lane(s, src);
+        wave_walk(r.it, r.n, lane, [&](uint32_t x) { entry(rj, ra, rb, r, x); });
+    });
 }
 
 // ---- pass 3: the per-vertex sums and the closed forms
@@ -600,17 +564,13 @@ int graphlets_run(komb_ctx *ctx)
             // ---- pass 2: triangles, 4-cliques per edge, D2
             uint32_t *d_rs = nullptr, *d_re = nullptr;
             u64 *d_d2 = nullptr, *d_acc = nullptr, *d_acc2 = nullptr;
-            KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
-            KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
             KOMB_HIP(ctx, bufs.alloc(&d_d2, (size_t)nv));
             KOMB_HIP(ctx, bufs.alloc(&d_acc, (size_t)kGlSums * nv));
             KOMB_HIP(ctx, bufs.alloc(&d_acc2, (size_t)kGlSums2 * nv));
-            KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
-            KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
             KOMB_HIP(ctx, hipMemsetAsync(d_d2, 0, (size_t)nv * sizeof(u64), s));
             KOMB_HIP(ctx, hipMemsetAsync(d_acc, 0, (size_t)kGlSums * nv * sizeof(u64), s));
             KOMB_HIP(ctx, hipMemsetAsync(d_acc2, 0, (size_t)kGlSums2 * nv * sizeof(u64), s));
-            k_gl_rows<<<ge, kBlock, 0, s>>>(eu, um, d_rs, d_re);
+            KOMB_TRY(oriented_rows(ctx, bufs, eu, m, nullptr, &d_rs, &d_re));
             k_gl_tri<<<ge, kBlock, 0, s>>>(eu, ev, d_rs, d_re, sup, um, kGlTriShort, d_d2, res.cliques4);
             KOMB_HIP(ctx, hipGetLastError());
             (void)hipEventRecord(e2, s);

@@ -28,7 +28,7 @@
 //     host after the launch.  A stale best only costs nodes.
 //   * nodes: every wave adds its nodes to one counter in batches of at most 256 and reads the counter at every node; once it has
 //     reached the budget the wave stops.  The overshoot is at most 256 per wave (KOMB_MAXCLQ_OVERSHOOT in all).
-// The launches of a run: k_clq_rows, k_clq_tmax; then per phase (seed, search, enumeration) k_mc_search in count mode (the
+// The launches of a run: k_rows, k_clq_tmax; then per phase (seed, search, enumeration) k_mc_search in count mode (the
 // largest |P|, which sizes the scratch slots and the LDS) and in the phase's mode; k_mc_verify on the witness; k_mc_mark when
 // the counts are the witness' own.  No workgroup waits for another; every loop runs over a row part, a candidate set or a
 // stack that is bounded before it starts, and the node counter bounds the search as a whole.

@@ -25,7 +25,7 @@
 //     written there -- or, past the stream's end, nothing but the overflow word.  All are read by the host after the launch.
 //   * nodes: as in the search, batches of at most 256 per wave to one counter that every node reads; a wave that finds the budget
 //     spent stops.  What was reported by then is a lower bound: every reported clique is maximal, none is reported twice.
-// The launches of a run: k_clq_tmax; k_clq_rows, k_mx_keys, the sort, k_mx_lower; k_mx_walk in count mode (the largest |Q| at need
+// The launches of a run: k_clq_tmax; k_rows, k_mx_keys, the sort, k_mx_lower; k_mx_walk in count mode (the largest |Q| at need
 // k_min, which sizes the scratch slots and the LDS; above 4096 the run is refused) and in run mode.  No workgroup waits for another.
 #include "clique_root_dev.h"
 

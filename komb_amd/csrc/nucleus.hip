@@ -4,10 +4,10 @@
 //
 // Input: the canonical edges (eu[i] < ev[i], sorted by (eu, ev), original ids) of the last complete k-truss result, whole
 // graph and vmask runs alike.  As in communities.hip the list is an oriented CSR: row a = the positions [rs[a], re[a]) with
-// eu == a, their ev ascending.
+// eu == a, their ev ascending; the search over it (sides, tails, bisection, lane and wave tiers) is oriented_search_dev.h's.
 //
 // The launches of a run:
-//   k_nuc_rows                    row bounds
+//   k_rows                        row bounds
 //   k_nuc_tri<count>, <fill>      triangles a < b < c from edge j = (a, b): c is in row a behind j and in row b; the shorter
 //                                 side is walked, the longer one bisected.  A short side stays with the edge's lane, a medium
 //                                 one is walked by its wave, a long one is queued for k_nuc_tri_heavy (several workgroups,
@@ -35,8 +35,7 @@
 // that is launched retires at least one triangle, so there are at most n_triangles of them; a triangle enters a queue
 // once, so a queue of n_triangles words cannot overflow (appends are guarded all the same); the device loops run over row
 // parts, incidence lists and queue lengths that are fixed before the launch.
-#include "common.h"
-#include "nucleus_search_dev.h"
+#include "oriented_search_dev.h"
 
 namespace komb {
 
@@ -62,33 +61,6 @@ static_assert(sizeof(NucCtl) == 64, "NucCtl layout");
 inline int nuc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 inline int nuc_sweep(int64_t n) { const int g = nuc_grid(n); return g < 1 ? 1 : (g < kNucSweepGrid ? g : kNucSweepGrid); }
 
-// row bounds per original vertex (rs / re zeroed before: a vertex without a row has an empty one)
-__global__ void k_nuc_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= m) return;
-    const int32_t u = eu[j];
-    if (j == 0 || eu[j - 1] != u) rs[u] = j;
-    if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
-}
-
-// the two sides of edge j = (a, b): [it, it + n) is walked, [lo, hi) is searched; n <= hi - lo
-struct NucSides { uint32_t it, n, lo, hi; bool walk_a; };
-
-__device__ __forceinline__ NucSides nuc_sides(const int32_t *__restrict__ eu, const int32_t *__restrict__ ev,
-                                              const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, uint32_t j)
-{
-    const int32_t a = eu[j], b = ev[j];
-    const uint32_t ab = j + 1, ae = re[a], bb = rs[b], be = re[b];   // (row a holds j: ae > j)
-    const uint32_t la = ae - ab, lb = be - bb;
-    NucSides s;
-    s.walk_a = la <= lb;
-    if (s.walk_a) { s.it = ab; s.n = la; s.lo = bb; s.hi = be; }
-    else { s.it = bb; s.n = lb; s.lo = ab; s.hi = ae; }
-    if (s.hi == s.lo) s.n = 0;
-    return s;
-}
-
 __device__ __forceinline__ void nuc_emit(const NucTri &o, uint32_t t, uint32_t j, int32_t a, int32_t b, int32_t c, uint32_t x, uint32_t hit, bool walk_a)
 {
     o.a[t] = a; o.b[t] = b; o.c[t] = c;
@@ -105,8 +77,8 @@ __global__ void k_nuc_tri(const int32_t *__restrict__ eu, const int32_t *__restr
 {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
-    NucSides s{0, 0, 0, 0, true};
-    if (j < m) s = nuc_sides(eu, ev, rs, re, j);
+    EdgeSides s{0, 0, 0, 0, true};
+    if (j < m) s = edge_sides(eu, ev, rs, re, j);
     bool act = s.n > 0;
     if (act && s.n >= n_heavy) {
         if (!kFill) atomicAdd(&ctl->n_heavy, 1u);
@@ -125,27 +97,22 @@ __global__ void k_nuc_tri(const int32_t *__restrict__ eu, const int32_t *__restr
             ++mine;
         }
     }
-    unsigned long long todo = __ballot(mid);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const uint32_t rj = (uint32_t)__shfl((int32_t)j, src), rit = (uint32_t)__shfl((int32_t)s.it, src), rn = (uint32_t)__shfl((int32_t)s.n, src);
-        const uint32_t rlo = (uint32_t)__shfl((int32_t)s.lo, src), rhi = (uint32_t)__shfl((int32_t)s.hi, src);
-        const bool rwa = __shfl((int32_t)s.walk_a, src) != 0;
+    wave_turns(mid, [&](int src) {
+        const uint32_t rj = from_lane(j, src);
+        const EdgeSides r = from_lane(s, src);
         const int32_t a = eu[rj], b = ev[rj];
         const uint32_t base = kFill ? tri_ptr[rj] : 0u;
         uint32_t run = 0;
-        for (uint32_t x0 = rit; x0 < rit + rn; x0 += kWave) {              // (uniform per wave: the ballots see every lane)
-            const uint32_t x = x0 + (uint32_t)lane;
+        wave_walk_all(r.it, r.n, lane, [&](uint32_t x, bool in) {
             int32_t c = 0;
             uint32_t hit = kNucNone;
-            if (x < rit + rn) { c = ev[x]; hit = nuc_find(ev, c, rlo, rhi); }
+            if (in) { c = ev[x]; hit = nuc_find(ev, c, r.lo, r.hi); }
             const unsigned long long hits = __ballot(hit != kNucNone);
-            if (kFill && hit != kNucNone) nuc_emit(o, base + run + (uint32_t)__popcll(hits & nuc_below(lane)), rj, a, b, c, x, hit, rwa);
+            if (kFill && hit != kNucNone) nuc_emit(o, base + run + (uint32_t)__popcll(hits & nuc_below(lane)), rj, a, b, c, x, hit, r.walk_a);
             run += (uint32_t)__popcll(hits);
-        }
+        });
         if (lane == src) mine = run;
-    }
+    });
     if (!kFill) {
         if (j <= m) cnt[j] = j < m ? mine : 0u;
         unsigned long long sum = mine;
@@ -160,7 +127,7 @@ __global__ void k_nuc_queue(const int32_t *__restrict__ eu, const int32_t *__res
                             const uint32_t *__restrict__ re, uint32_t m, uint32_t n_heavy, NucCtl *ctl, uint32_t *__restrict__ heavy, uint32_t cap)
 {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= m || nuc_sides(eu, ev, rs, re, j).n < n_heavy) return;
+    if (j >= m || edge_sides(eu, ev, rs, re, j).n < n_heavy) return;
     const uint32_t slot = atomicAdd(&ctl->n_queued, 1u);
     if (slot < cap) heavy[slot] = j;                     // (the same edges the count pass counted: slot < cap)
 }
@@ -177,7 +144,7 @@ __global__ void k_nuc_tri_heavy(const int32_t *__restrict__ eu, const int32_t *_
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     for (uint32_t h = blockIdx.x; h < n_queued; h += gridDim.x) {
         const uint32_t j = heavy[h];
-        const NucSides s = nuc_sides(eu, ev, rs, re, j);
+        const EdgeSides s = edge_sides(eu, ev, rs, re, j);
         const uint32_t end = s.it + s.n, seg = (s.n + gridDim.y - 1) / gridDim.y;
         uint32_t x0 = s.it + blockIdx.y * seg, x1 = x0 + seg;
         if (x0 > end) x0 = end;
@@ -209,22 +176,6 @@ __global__ void k_nuc_tri_heavy(const int32_t *__restrict__ eu, const int32_t *_
     }
 }
 
-// the id of the triangle of the edge at position e whose third vertex is d: a bisection in e's ascending part of tc[]
-__device__ __forceinline__ uint32_t nuc_tri_id(const uint32_t *__restrict__ tri_ptr, const int32_t *__restrict__ tc, uint32_t e, int32_t d,
-                                               uint32_t fallback, NucCtl *ctl)
-{
-    uint32_t lo = tri_ptr[e];
-    const uint32_t end = tri_ptr[e + 1];
-    uint32_t hi = end;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (tc[mid] < d) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && tc[lo] == d) return lo;
-    ctl->bad = 1u;                                       // (three edges of the result that close a triangle the fill did not write)
-    return fallback;
-}
-
 // record q: triangle t and the three triangles its vertices make with d = ev[x].  They hang on t's own edges (a, b), (a, c),
 // (b, c), so the positions of (a, d), (b, d), (c, d) the searches found are not needed again.
 __device__ __forceinline__ void nuc_clq_write(const int32_t *__restrict__ ev, const NucTri &o, const uint32_t *__restrict__ tri_ptr,
@@ -233,9 +184,9 @@ __device__ __forceinline__ void nuc_clq_write(const int32_t *__restrict__ ev, co
     const int32_t d = ev[x];
     uint4 r;
     r.x = t;
-    r.y = nuc_tri_id(tri_ptr, o.c, o.j[t], d, t, ctl);       // (a, b, d)
-    r.z = nuc_tri_id(tri_ptr, o.c, o.pac[t], d, t, ctl);     // (a, c, d)
-    r.w = nuc_tri_id(tri_ptr, o.c, o.pbc[t], d, t, ctl);     // (b, c, d)
+    r.y = tri_id(tri_ptr, o.c, o.j[t], d, t, &ctl->bad);       // (a, b, d)
+    r.z = tri_id(tri_ptr, o.c, o.pac[t], d, t, &ctl->bad);     // (a, c, d)
+    r.w = tri_id(tri_ptr, o.c, o.pbc[t], d, t, &ctl->bad);     // (b, c, d)
     clq[q] = r;
     atomicAdd(key0 + r.y, 1u); atomicAdd(key0 + r.z, 1u); atomicAdd(key0 + r.w, 1u);
 }
@@ -262,26 +213,19 @@ __global__ void k_nuc_clq(const int32_t *__restrict__ ev, const uint32_t *__rest
             ++mine;
         }
     }
-    unsigned long long todo = __ballot(mid);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const uint32_t rt = (uint32_t)__shfl((int32_t)t, src);
-        NucTails r;
-        r.it = (uint32_t)__shfl((int32_t)s.it, src); r.n = (uint32_t)__shfl((int32_t)s.n, src);
-        r.lo1 = (uint32_t)__shfl((int32_t)s.lo1, src); r.hi1 = (uint32_t)__shfl((int32_t)s.hi1, src);
-        r.lo2 = (uint32_t)__shfl((int32_t)s.lo2, src); r.hi2 = (uint32_t)__shfl((int32_t)s.hi2, src);
+    wave_turns(mid, [&](int src) {
+        const uint32_t rt = from_lane(t, src);
+        const NucTails r = from_lane(s, src);
         const uint32_t base = kFill ? q_ptr[rt] : 0u;
         uint32_t run = 0;
-        for (uint32_t x0 = r.it; x0 < r.it + r.n; x0 += kWave) {          // (uniform per wave)
-            const uint32_t x = x0 + (uint32_t)lane;
-            const bool hit = x < r.it + r.n && nuc_clq_entry(ev, r, x);
+        wave_walk_all(r.it, r.n, lane, [&](uint32_t x, bool in) {
+            const bool hit = in && nuc_clq_entry(ev, r, x);
             const unsigned long long hits = __ballot(hit);
             if (kFill && hit) nuc_clq_write(ev, o, tri_ptr, rt, x, base + run + (uint32_t)__popcll(hits & nuc_below(lane)), clq, key0, ctl);
             run += (uint32_t)__popcll(hits);
-        }
+        });
         if (lane == src) mine = run;
-    }
+    });
     if (kFill) {
         if (mine) atomicAdd(key0 + t, mine);
     } else {
@@ -375,20 +319,17 @@ __global__ void k_nuc_walk(NucCtl *ctl, int sel, const uint32_t *__restrict__ qu
     uint32_t n = ctl->n_q[sel];
     if (n > n_tri) n = n_tri;
     const int32_t k = ctl->kmin;
-    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {        // (uniform per workgroup)
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {        // (uniform per workgroup: wave_turns)
         const uint32_t i = base + threadIdx.x;
         uint32_t t = 0, lo = 0, hi = 0;
         if (i < n) { t = queue[i]; lo = inc_ptr[t]; hi = inc_ptr[t + 1]; }
         const bool mid = hi - lo > n_short;
         if (!mid)
             for (uint32_t x = lo; x < hi; ++x) nuc_retire(inc[x], t, k, clq, dead, theta, key, ctl, sel ^ 1, next, n_tri);
-        unsigned long long todo = __ballot(mid);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const uint32_t rt = (uint32_t)__shfl((int32_t)t, src), rlo = (uint32_t)__shfl((int32_t)lo, src), rhi = (uint32_t)__shfl((int32_t)hi, src);
-            for (uint32_t x = rlo + (uint32_t)lane; x < rhi; x += kWave) nuc_retire(inc[x], rt, k, clq, dead, theta, key, ctl, sel ^ 1, next, n_tri);
-        }
+        wave_turns(mid, [&](int src) {
+            const uint32_t rt = from_lane(t, src), rlo = from_lane(lo, src), rhi = from_lane(hi, src);
+            wave_walk(rlo, rhi - rlo, lane, [&](uint32_t x) { nuc_retire(inc[x], rt, k, clq, dead, theta, key, ctl, sel ^ 1, next, n_tri); });
+        });
     }
 }
 
@@ -408,14 +349,6 @@ __global__ void k_nuc_out(uint32_t n_tri, NucTri o, const int32_t *__restrict__ 
     nuc_max(vertex_theta + o.a[t], th); nuc_max(vertex_theta + o.b[t], th); nuc_max(vertex_theta + o.c[t], th);
 }
 
-inline uint32_t nuc_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
-{
-    const char *e = ctx_opt(ctx, name);
-    if (!e) return dflt;
-    const unsigned long v = strtoul(e, nullptr, 10);
-    return v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
-}
-
 } // namespace
 
 // the k-truss result it needs is checked by the caller (api.cpp).  The result is built in blocks of its own and replaces the
@@ -427,8 +360,8 @@ int nucleus_run(komb_ctx *ctx)
     if (m > 0) KOMB_TRY(truss_edges_canonical(ctx));     // (a whole-graph result whose endpoints no fetch has asked for yet)
     Range r_all("komb_nucleus_run");
     komb_ctx::Nucleus res;                               // goes back to the pool unless it is installed
-    const uint32_t n_short = nuc_opt_u32(ctx, "NUC_SHORT", kNucShort);       // (tests: every unit through the wave / the queued path)
-    uint32_t n_heavy = nuc_opt_u32(ctx, "NUC_HEAVY", kNucHeavy);
+    const uint32_t n_short = ctx_opt_u32(ctx, "NUC_SHORT", kNucShort);       // (tests: every unit through the wave / the queued path)
+    uint32_t n_heavy = ctx_opt_u32(ctx, "NUC_HEAVY", kNucHeavy);
     if (n_heavy <= n_short) n_heavy = n_short + 1;
     int64_t cap = kNucMaxClq;                                                // NUC_CAP (tests): a smaller clique limit
     if (const char *e = ctx_opt(ctx, "NUC_CAP")) { const long long v = strtoll(e, nullptr, 10); if (v >= 0 && v < cap) cap = v; }
@@ -456,13 +389,9 @@ int nucleus_run(komb_ctx *ctx)
     if (m > 0) {
         // ---- triangles
         uint32_t *d_rs = nullptr, *d_re = nullptr, *d_cnt = nullptr, *d_heavy = nullptr, *d_part = nullptr;
-        KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
-        KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
         KOMB_HIP(ctx, bufs.alloc(&d_cnt, (size_t)m + 1));        // counts, then tri_ptr
-        KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
-        KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
         const NucTri none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        k_nuc_rows<<<nuc_grid(m), kBlock, 0, s>>>(eu, um, d_rs, d_re);
+        KOMB_TRY(oriented_rows(ctx, bufs, eu, m, nullptr, &d_rs, &d_re));
         k_nuc_tri<false><<<nuc_grid(m + 1), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, d_cnt, nullptr, d_ctl, n_short, n_heavy, none);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));

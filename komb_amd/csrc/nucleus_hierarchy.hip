@@ -7,7 +7,7 @@
 // (a, b, c) order: the root of a tree is its rep), bucketed by their own theta; the LINKS are 4-clique records of weight
 // w = the smallest theta of the clique's four triangles -- the level at which the clique starts to bind.  komb_nucleus_run
 // drops its clique records with its scratch, so the cliques are enumerated ONCE more here, by nucleus.hip's search
-// (nucleus_search_dev.h: the shortest of three tails walked, the other two bisected, the ids of the other three triangles by
+// (oriented_search_dev.h: the shortest of three tails walked, the other two bisected, the ids of the other three triangles by
 // bisection in c[] through a rebuilt tri_ptr), into a record stream whose length the stored result gives exactly
 // (n_cliques4): there is no counting pass, a wave takes its slots with one returning atomic, and a cursor that does not end
 // on n_cliques4 fails the run.  The stream is sorted by w (a sort of (w, slot) pairs; LINK reads its records through the
@@ -17,10 +17,10 @@
 // Why every node has a hooked triangle: a triangle of theta = k lies in at least k cliques whose other triangles all have
 // theta >= k, records of weight exactly k; it was alone before, so the tree it ends the level in holds a triangle hooked at
 // this level.  The levels run from theta_max down to 1.
-// Every ballot sits in a loop whose bounds are uniform over its wave; every device loop runs over a row part or a length
-// fixed before its launch; the labels are read by a later store-free launch (the header comment of components.hip says why).
+// Every device loop runs over a row part or a length fixed before its launch; the labels are read by a later store-free launch
+// (the header comment of components.hip says why).
 #include "forest_dev.h"
-#include "nucleus_search_dev.h"
+#include "oriented_search_dev.h"
 
 namespace komb {
 
@@ -40,16 +40,6 @@ static_assert(sizeof(NhCtl) == 64 && offsetof(NhCtl, f) == 0, "NhCtl layout");
 struct NhStream { uint32_t *keys, *idx; uint4 *recs; uint32_t cap; };  // record slot q: weight | q | the four triangle ids
 
 // ---- the search structures of nucleus.hip, rebuilt from the stored a, b, c and the canonical edge list
-
-// row bounds per original vertex (rs / re zeroed before: a vertex without a row has an empty one)
-__global__ void k_nh_rows(const int32_t *__restrict__ eu, uint32_t m, uint32_t *__restrict__ rs, uint32_t *__restrict__ re)
-{
-    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= m) return;
-    const int32_t u = eu[j];
-    if (j == 0 || eu[j - 1] != u) rs[u] = j;
-    if (j + 1 == m || eu[j + 1] != u) re[u] = j + 1;
-}
 
 // per triangle: the positions of its edges (three bisections), its membership flag for the scan (flag[n_tri] = 0), and its
 // union-find words -- a class of its own that stands for no node yet.  A triangle whose edges are not found takes no part
@@ -90,22 +80,6 @@ __global__ void k_nh_tri_ptr(uint32_t m, uint32_t n_tri, const uint32_t *__restr
     tri_ptr[e] = lo;
 }
 
-// the id of the triangle of the edge at position e whose third vertex is d: a bisection in e's ascending part of tc[]
-__device__ __forceinline__ uint32_t nh_tri_id(const uint32_t *__restrict__ tri_ptr, const int32_t *__restrict__ tc, uint32_t e, int32_t d,
-                                              uint32_t fallback, NhCtl *ctl)
-{
-    uint32_t lo = tri_ptr[e];
-    const uint32_t end = tri_ptr[e + 1];
-    uint32_t hi = end;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (tc[mid] < d) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && tc[lo] == d) return lo;
-    ctl->bad = 1u;                                       // (three edges of the result that close a triangle the result does not hold)
-    return fallback;
-}
-
 // the hits of a wave: one record each, triangle t and the three triangles its vertices make with d = ev[x], of weight
 // min(theta); the slots are taken once per wave.  Every lane of the wave calls it.
 __device__ __forceinline__ void nh_emit(bool hit, uint32_t t, uint32_t x, const int32_t *__restrict__ ev, const NucTri &o,
@@ -124,9 +98,9 @@ __device__ __forceinline__ void nh_emit(bool hit, uint32_t t, uint32_t x, const 
     const int32_t d = ev[x];
     uint4 r;
     r.x = t;
-    r.y = nh_tri_id(tri_ptr, o.c, o.j[t], d, t, ctl);        // (a, b, d)
-    r.z = nh_tri_id(tri_ptr, o.c, o.pac[t], d, t, ctl);      // (a, c, d)
-    r.w = nh_tri_id(tri_ptr, o.c, o.pbc[t], d, t, ctl);      // (b, c, d)
+    r.y = tri_id(tri_ptr, o.c, o.j[t], d, t, &ctl->bad);        // (a, b, d)
+    r.z = tri_id(tri_ptr, o.c, o.pac[t], d, t, &ctl->bad);      // (a, c, d)
+    r.w = tri_id(tri_ptr, o.c, o.pbc[t], d, t, &ctl->bad);      // (b, c, d)
     const int32_t w0 = theta[r.x], w1 = theta[r.y], w2 = theta[r.z], w3 = theta[r.w];
     const int32_t wa = w0 < w1 ? w0 : w1, wb = w2 < w3 ? w2 : w3;
     st.keys[slot] = (uint32_t)(wa < wb ? wa : wb);           // (a weight outside 1 .. theta_max shows in the level table; the host checks it)
@@ -146,26 +120,16 @@ __global__ void k_nh_clq(const int32_t *__restrict__ ev, const uint32_t *__restr
     if (t < n_tri && o.j[t] != kNucNone) s = nuc_tails(o, rs, re, t);
     const bool act = s.n > 0, mid = act && s.n > n_short;
     const uint32_t own = act && !mid ? s.n : 0u;
-    const uint32_t top = wave_max(own);                               // (uniform per wave)
+    const uint32_t top = wave_max(own);
     for (uint32_t i = 0; i < top; ++i) {
         const bool hit = i < own && nuc_clq_entry(ev, s, s.it + i);
         nh_emit(hit, t, s.it + i, ev, o, tri_ptr, theta, ctl, st);
     }
-    unsigned long long todo = __ballot(mid);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const uint32_t rt = (uint32_t)__shfl((int32_t)t, src);
-        NucTails r;
-        r.it = (uint32_t)__shfl((int32_t)s.it, src); r.n = (uint32_t)__shfl((int32_t)s.n, src);
-        r.lo1 = (uint32_t)__shfl((int32_t)s.lo1, src); r.hi1 = (uint32_t)__shfl((int32_t)s.hi1, src);
-        r.lo2 = (uint32_t)__shfl((int32_t)s.lo2, src); r.hi2 = (uint32_t)__shfl((int32_t)s.hi2, src);
-        for (uint32_t x0 = r.it; x0 < r.it + r.n; x0 += kWave) {         // (uniform per wave)
-            const uint32_t x = x0 + (uint32_t)lane;
-            const bool hit = x < r.it + r.n && nuc_clq_entry(ev, r, x);
-            nh_emit(hit, rt, x, ev, o, tri_ptr, theta, ctl, st);
-        }
-    }
+    wave_turns(mid, [&](int src) {
+        const uint32_t rt = from_lane(t, src);
+        const NucTails r = from_lane(s, src);
+        wave_walk_all(r.it, r.n, lane, [&](uint32_t x, bool in) { nh_emit(in && nuc_clq_entry(ev, r, x), rt, x, ev, o, tri_ptr, theta, ctl, st); });
+    });
     if (t == 0) ctl->n_members = *n_mem;
 }
 
@@ -306,14 +270,6 @@ __global__ void k_nh_nuclei_out(uint32_t n_tri, const int32_t *__restrict__ labe
     nedge[i] = (int32_t)nh_range(euniq, n_e, lo, hi);
 }
 
-inline uint32_t nh_opt_u32(const komb_ctx *ctx, const char *name, uint32_t dflt)
-{
-    const char *e = ctx_opt(ctx, name);
-    if (!e) return dflt;
-    const unsigned long v = strtoul(e, nullptr, 10);
-    return v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
-}
-
 // label[] / size[] of threshold k on the device (k resolved by the caller: >= 1)
 int nh_labels_dev(komb_ctx *ctx, int32_t k, int32_t *d_label, int32_t *d_size)
 {
@@ -351,7 +307,7 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         const uint32_t um = (uint32_t)m, uT = (uint32_t)T, uQ = (uint32_t)Q;
         const uint32_t levels = (uint32_t)res.theta_max + 1u;    // level numbers 0 .. levels - 1
         const int bits = forest_bits(levels);
-        const uint32_t n_short = nh_opt_u32(ctx, "NUC_SHORT", kNhShort);      // (tests: every triangle through the wave / its lane)
+        const uint32_t n_short = ctx_opt_u32(ctx, "NUC_SHORT", kNhShort);      // (tests: every triangle through the wave / its lane)
         const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *theta = ctx->nuc.theta;
 
         NhCtl *d_ctl = nullptr;
@@ -360,8 +316,6 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         NucTri o{ctx->nuc.a, ctx->nuc.b, ctx->nuc.c, nullptr, nullptr, nullptr};
         NhStream st{nullptr, nullptr, nullptr, uQ};
         KOMB_HIP(ctx, bufs.alloc(&d_ctl, 1));
-        KOMB_HIP(ctx, bufs.alloc(&d_rs, (size_t)nv));
-        KOMB_HIP(ctx, bufs.alloc(&d_re, (size_t)nv));
         KOMB_HIP(ctx, bufs.alloc(&tri_ptr, (size_t)m + 1));
         KOMB_HIP(ctx, bufs.alloc(&o.j, (size_t)T));
         KOMB_HIP(ctx, bufs.alloc(&o.pac, (size_t)T));
@@ -382,9 +336,7 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         // ---- the search structures, the members' flags, and the one clique enumeration
         const uint32_t *d_nm = d_pos + T;                        // the number of members, on the device
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(NhCtl), s));
-        KOMB_HIP(ctx, hipMemsetAsync(d_rs, 0, (size_t)nv * sizeof(uint32_t), s));
-        KOMB_HIP(ctx, hipMemsetAsync(d_re, 0, (size_t)nv * sizeof(uint32_t), s));
-        k_nh_rows<<<forest_grid(m), kBlock, 0, s>>>(eu, um, d_rs, d_re);
+        KOMB_TRY(oriented_rows(ctx, bufs, eu, m, nullptr, &d_rs, &d_re));
         k_nh_tri<<<forest_grid(T + 1), kBlock, 0, s>>>(uT, (uint32_t)nv, o, ev, d_rs, d_re, theta, d_flag, parent, cnt, cur, claimk, d_ctl);
         k_nh_tri_ptr<<<forest_grid(m + 1), kBlock, 0, s>>>(um, uT, o.j, tri_ptr);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, T + 1));

@@ -137,6 +137,19 @@ def test_closed_forms(K):
                                  "diamond": 0, "clique4": 0}
 
 
+@pytest.mark.parametrize("n", [18, 19])
+def test_triangle_pass_lane_wave_boundary(K, n):
+    """The triangle pass keeps a walked side of up to 16 entries with the edge's lane and hands longer ones to the wave; the
+    threshold has no option.  In K_n the longest walked side is that of edge (0, 1), n - 2 entries: K_18 is the largest clique
+    that stays with the lanes, K_19 the smallest with a wave unit."""
+    with _load(K, n, _clique(range(n))) as a:
+        orbit, cyc, clq, info = _check(a)[4:]
+        m = comb(n, 2)
+        assert clq.tolist() == [comb(n - 2, 2)] * m and cyc.tolist() == [2 * comb(n - 2, 2)] * m
+        assert orbit[3].tolist() == [comb(n - 1, 2)] * n and orbit[14].tolist() == [comb(n - 1, 3)] * n
+        assert info["total"]["triangle"] == comb(n, 3) and info["total"]["clique4"] == comb(n, 4)
+
+
 @pytest.mark.parametrize("centre", [0, 5000])
 def test_star(K, centre):
     """K_{1,5000}: the centre's claw count is above 2^32, and nothing is walked (a leaf has no neighbour below the centre)."""
