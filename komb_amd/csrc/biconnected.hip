@@ -34,8 +34,7 @@
 // arrays here, and as there a compressing flatten launch is followed by a store-free labelling launch.  A stale read of
 // level[] in the BFS can only show an unclaimed vertex that is claimed by now: the compare-and-swap then fails.  No
 // workgroup waits for another.  The number of launches is 4 per level of the forest plus a constant.
-#include "common.h"
-#include "unionfind_dev.h"
+#include "unionfind_dev.h"   // the union-find and its class tail; wave_dev.h: wave_append, wave_by_key
 
 namespace komb {
 
@@ -43,7 +42,6 @@ namespace {
 
 constexpr uint32_t kBiconnHeavy = 32;       // BFS rows longer than this: the vertex' wave (option BICONN_HEAVY)
 constexpr uint32_t kBiconnBlockRow = 2048;  // ... and from this length on: its workgroup
-constexpr int kBiconnTailGrid = 2048;       // the counting passes: at most this many workgroups, each over several tiles
 
 struct BiconnCtl {                          // 64 bytes, zeroed before every run
     uint32_t tail;                          // BFS: vertices appended to order[] so far
@@ -53,28 +51,6 @@ struct BiconnCtl {                          // 64 bytes, zeroed before every run
     uint32_t pad[8];
 };
 static_assert(sizeof(BiconnCtl) == 64, "BiconnCtl layout");
-
-inline int bc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-
-// a slot of a list for every lane that takes one: one atomic per wave.  Every lane that is here calls it.
-__device__ __forceinline__ uint32_t wave_append(bool take, uint32_t *counter)
-{
-    const unsigned long long m = __ballot(take);
-    if (!m) return 0u;
-    const int lane = threadIdx.x & (kWave - 1), lead = __ffsll((long long)m) - 1;
-    uint32_t base = 0u;
-    if (lane == lead) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int32_t)base, lead);
-    return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-
-// flag[i] = edge i is a member (flag[m] = 0: the scan's last entry is the number of members)
-__global__ void k_bc_flag(const int32_t *__restrict__ truss, uint32_t m, int32_t k, uint32_t *__restrict__ flag)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i > m) return;
-    flag[i] = i < m && truss[i] >= k ? 1u : 0u;
-}
 
 // per vertex: the three union-finds start as singletons, nobody has a level, every counter is empty (deg has nv + 1 entries)
 __global__ void k_bc_vinit(uint32_t nv, uint32_t *__restrict__ deg, uint32_t *__restrict__ fill, int32_t *__restrict__ cpar,
@@ -257,20 +233,18 @@ __global__ void k_bc_flatten(uint32_t nv, int32_t *parent)
 {
     const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
     if (v >= nv) return;
-    const int32_t r = kFinal ? comp_find_ro(parent, (int32_t)v) : comp_find(parent, (int32_t)v);
-    if (r != (int32_t)v) pstore(parent + v, r);
+    comp_flatten<kFinal>(parent, v);
 }
 
 // eblk[j] = the class of member edge j, read off ec[j] (the same words: every lane rewrites its own); per class the edges,
-// the tree edges and the smallest canonical index.  k_comp_count's scheme: lanes of a wave that share a class add once (the
-// lowest lane of them holds the smallest index: kept[] ascends), and what a workgroup adds to the class its first tile starts
-// with (the giant block's, nearly always) it sums in LDS first.
+// the tree edges and the smallest canonical index.  k_class_count's scheme with three accumulators: lanes of a wave that share
+// a class add once (the lowest lane of them holds the smallest index: kept[] ascends), and what a workgroup adds to the class
+// its first tile starts with (the giant block's, nearly always) it sums in LDS first.
 __global__ void k_bc_edge_blocks(const int32_t *__restrict__ kept, uint32_t nm, const int32_t *__restrict__ blabel, int32_t *eblk,
                                  int32_t *blockmin, uint32_t *edges, uint32_t *tree)
 {
     __shared__ int32_t s_first, s_min;
     __shared__ uint32_t s_sum, s_tree;
-    const int lane = threadIdx.x & (kWave - 1);
     if (threadIdx.x == 0) { s_first = -1; s_min = 0x7FFFFFFF; s_sum = 0u; s_tree = 0u; }
     __syncthreads();
     for (uint32_t base = blockIdx.x * kBlock; base < nm; base += gridDim.x * kBlock) {      // (uniform per workgroup: the ballots see whole waves)
@@ -289,18 +263,12 @@ __global__ void k_bc_edge_blocks(const int32_t *__restrict__ kept, uint32_t nm, 
         }
         const int32_t first = s_first;
         const bool act = lab >= 0;
-        unsigned long long m = __ballot(act);
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(lab, src);
-            const unsigned long long same = __ballot(act && lab == lead);
+        wave_by_key(act, lab, [&](int32_t lead, unsigned long long same, bool is_leader) {
             const uint32_t n_tree = (uint32_t)__popcll(__ballot(act && lab == lead && is_tree));
-            if (lane == src) {
-                if (lead == first) { atomicAdd(&s_sum, (uint32_t)__popcll(same)); atomicAdd(&s_tree, n_tree); atomicMin(&s_min, idx); }
-                else { atomicAdd(edges + lead, (uint32_t)__popcll(same)); if (n_tree) atomicAdd(tree + lead, n_tree); atomicMin(blockmin + lead, idx); }
-            }
-            m &= ~same;
-        }
+            if (!is_leader) return;
+            if (lead == first) { atomicAdd(&s_sum, (uint32_t)__popcll(same)); atomicAdd(&s_tree, n_tree); atomicMin(&s_min, idx); }
+            else { atomicAdd(edges + lead, (uint32_t)__popcll(same)); if (n_tree) atomicAdd(tree + lead, n_tree); atomicMin(blockmin + lead, idx); }
+        });
     }
     __syncthreads();
     if (threadIdx.x == 0 && s_sum) {
@@ -337,36 +305,6 @@ __global__ void k_bc_ecc_label(uint32_t nv, const int32_t *__restrict__ level, c
     const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
     if (v >= nv) return;
     label[v] = level[v] >= 0 ? comp_find_ro(epar, (int32_t)v) : -1;
-}
-
-// cnt[label] += vertices that carry it (k_comp_count)
-__global__ void k_bc_ecc_count(uint32_t nv, const int32_t *__restrict__ label, uint32_t *cnt)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t v0 = blockIdx.x * kBlock;
-    if (threadIdx.x == 0) { s_first = v0 < nv ? label[v0] : -1; s_sum = 0u; }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t base = v0; base < nv; base += gridDim.x * kBlock) {
-        const uint32_t v = base + threadIdx.x;
-        const int32_t lab = v < nv ? label[v] : -1;
-        const bool act = lab >= 0;
-        unsigned long long m = __ballot(act);
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(lab, src);
-            const unsigned long long same = __ballot(act && lab == lead);
-            if (lane == src) {
-                if (lead == first) atomicAdd(&s_sum, (uint32_t)__popcll(same));
-                else atomicAdd(cnt + lead, (uint32_t)__popcll(same));
-            }
-            m &= ~same;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(cnt + first, s_sum);
 }
 
 // ecc_size[v]; the 2-edge-connected components and the largest; the articulation points; the largest block
@@ -458,7 +396,7 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
     KOMB_HIP(ctx, ctx->pool.get((void **)res.ecc_size.slot(&ctx->pool), (size_t)nv * sizeof(int32_t)));
     int32_t *block = res.block, *size = res.size, *n_blocks = res.nblocks, *ecc_label = res.ecc_label;
     const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *truss = ctx->d_t_truss;
-    const int vgrid = bc_grid(nv), egrid = bc_grid(m);
+    const int vgrid = tiles_of(nv), egrid = tiles_of(m);
 
     DevBufs bufs(ctx);
     BiconnCtl *d_ctl = nullptr;
@@ -470,8 +408,7 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
     KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(BiconnCtl), s));
     uint32_t nm = 0;
     if (m > 0) {
-        k_bc_flag<<<bc_grid(m + 1), kBlock, 0, s>>>(truss, (uint32_t)m, k, d_flag);
-        KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
+        KOMB_TRY(prim_flag_ge_scan(ctx, truss, m, k, d_flag, d_pos));
         KOMB_HIP(ctx, d2h(ctx, &nm, d_pos + m, sizeof(uint32_t)));
     }
     if (nm == 0) {                                       // no member edge: nothing to traverse
@@ -501,15 +438,11 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
     for (uint32_t **p : {&d_fill, &d_nd, &d_cursor, &d_edges, &d_tree, &d_top, &d_ecnt}) KOMB_HIP(ctx, bufs.alloc(p, (size_t)nv));
     for (int32_t **p : {&d_cpar, &d_bpar, &d_epar, &d_level, &d_par, &d_order, &d_pre, &d_low, &d_high, &d_blockmin})
         KOMB_HIP(ctx, bufs.alloc(p, (size_t)nv));
-    uint32_t heavy = kBiconnHeavy;
-    if (const char *e = ctx_opt(ctx, "BICONN_HEAVY")) {  // (tests: every row through the wave)
-        const unsigned long v = strtoul(e, nullptr, 10);
-        heavy = v < 1 ? 1u : (v > 0x7FFFFFFFul ? 0x7FFFFFFFu : (uint32_t)v);
-    }
-    const int mgrid = bc_grid(nm);
+    const uint32_t heavy = ctx_opt_u32(ctx, "BICONN_HEAVY", kBiconnHeavy);      // (tests: every row through the wave)
+    const int mgrid = tiles_of(nm);
 
     Range r_part("biconnected: member graph");
-    k_bc_vinit<<<bc_grid(nv + 1), kBlock, 0, s>>>((uint32_t)nv, d_rowptr, d_fill, d_cpar, d_bpar, d_epar, d_level, d_nd, d_cursor, d_blockmin,
+    k_bc_vinit<<<tiles_of(nv + 1), kBlock, 0, s>>>((uint32_t)nv, d_rowptr, d_fill, d_cpar, d_bpar, d_epar, d_level, d_nd, d_cursor, d_blockmin,
                                                    d_edges, d_tree, d_top, d_ecnt);
     k_bc_compact<<<egrid, kBlock, 0, s>>>(eu, ev, truss, (uint32_t)m, k, d_pos, d_kept, d_mu, d_mv, d_rowptr, d_cpar);
     KOMB_TRY(prim_exclusive_sum_u32(ctx, d_rowptr, d_rowptr, nv + 1));
@@ -525,7 +458,7 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
         if (tail > (uint32_t)nv) KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_biconnected_run: the BFS queued %u of %lld vertices", tail, (long long)nv);
         const uint32_t lo = off.back();
         off.push_back(tail);
-        k_bc_bfs<<<bc_grid(tail - lo), kBlock, 0, s>>>(lo, tail, (int32_t)off.size() - 1, d_rowptr, d_adj, d_level, d_par, d_order, d_ctl, heavy);
+        k_bc_bfs<<<tiles_of(tail - lo), kBlock, 0, s>>>(lo, tail, (int32_t)off.size() - 1, d_rowptr, d_adj, d_level, d_par, d_order, d_ctl, heavy);
         KOMB_HIP(ctx, d2h(ctx, &tail, &d_ctl->tail, sizeof(uint32_t)));
     }
     const int depth = (int)off.size() - 1;               // levels 0 .. depth - 1 are order[off[L], off[L + 1])
@@ -534,31 +467,29 @@ int biconnected_run(komb_ctx *ctx, int32_t k)
     // ---- the three sweeps
     r_part.next("biconnected: sweeps");
     for (int L = depth - 1; L >= 1; --L)
-        k_bc_nd_up<<<bc_grid(off[L + 1] - off[L]), kBlock, 0, s>>>(off[L], off[L + 1], d_order, d_par, d_nd);
+        k_bc_nd_up<<<tiles_of(off[L + 1] - off[L]), kBlock, 0, s>>>(off[L], off[L + 1], d_order, d_par, d_nd);
     for (int L = 0; L < depth; ++L)
-        k_bc_pre_down<<<bc_grid(off[L + 1] - off[L]), kBlock, 0, s>>>(off[L], off[L + 1], L == 0, d_order, d_par, d_nd, d_cursor, d_pre, d_low, d_high, d_ctl);
+        k_bc_pre_down<<<tiles_of(off[L + 1] - off[L]), kBlock, 0, s>>>(off[L], off[L + 1], L == 0, d_order, d_par, d_nd, d_cursor, d_pre, d_low, d_high, d_ctl);
     k_bc_reach<<<mgrid, kBlock, 0, s>>>(d_mu, d_mv, nm, d_par, d_pre, d_nd, d_low, d_high, d_bpar, (uint32_t *)d_eblk);
     for (int L = depth - 1; L >= 1; --L)
-        k_bc_reach_up<<<bc_grid(off[L + 1] - off[L]), kBlock, 0, s>>>(off[L], off[L + 1], d_order, d_par, d_low, d_high);
+        k_bc_reach_up<<<tiles_of(off[L + 1] - off[L]), kBlock, 0, s>>>(off[L], off[L + 1], d_order, d_par, d_low, d_high);
 
     // ---- the blocks
     r_part.next("biconnected: blocks");
     k_bc_link_tree<<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_level, d_par, d_pre, d_nd, d_low, d_high, d_bpar, n_blocks);
     k_bc_flatten<false><<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_bpar);
     k_bc_flatten<true><<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_bpar);
-    const int tail_m = mgrid < kBiconnTailGrid ? mgrid : kBiconnTailGrid, tail_v = vgrid < kBiconnTailGrid ? vgrid : kBiconnTailGrid;
-    const int tail_e = bc_grid(m + 1) < kBiconnTailGrid ? bc_grid(m + 1) : kBiconnTailGrid;
-    k_bc_edge_blocks<<<tail_m, kBlock, 0, s>>>(d_kept, nm, d_bpar, d_eblk, d_blockmin, d_edges, d_tree);
+    k_bc_edge_blocks<<<class_tail_grid(nm), kBlock, 0, s>>>(d_kept, nm, d_bpar, d_eblk, d_blockmin, d_edges, d_tree);
     k_bc_tops<<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_level, d_par, d_bpar, d_top, n_blocks);
-    k_bc_efinish<<<tail_e, kBlock, 0, s>>>((uint32_t)m, truss, k, d_pos, d_eblk, d_blockmin, d_edges, block, size, d_flag, d_ctl);
+    k_bc_efinish<<<class_tail_grid(m + 1), kBlock, 0, s>>>((uint32_t)m, truss, k, d_pos, d_eblk, d_blockmin, d_edges, block, size, d_flag, d_ctl);
 
     // ---- the 2-edge-connected components
     r_part.next("biconnected: 2-edge-connected");
     k_bc_ecc_link<<<mgrid, kBlock, 0, s>>>(d_mu, d_mv, nm, d_eblk, d_edges, d_epar);
     k_bc_flatten<false><<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_epar);
     k_bc_ecc_label<<<vgrid, kBlock, 0, s>>>((uint32_t)nv, d_level, d_epar, ecc_label);
-    k_bc_ecc_count<<<tail_v, kBlock, 0, s>>>((uint32_t)nv, ecc_label, d_ecnt);
-    k_bc_vfinish<<<tail_v, kBlock, 0, s>>>((uint32_t)nv, ecc_label, d_ecnt, n_blocks, d_edges, res.ecc_size, d_ctl);
+    class_count(ctx, nv, nullptr, ecc_label, d_ecnt);
+    k_bc_vfinish<<<class_tail_grid(nv), kBlock, 0, s>>>((uint32_t)nv, ecc_label, d_ecnt, n_blocks, d_edges, res.ecc_size, d_ctl);
 
     // ---- the block list
     r_part.next("biconnected: block list");

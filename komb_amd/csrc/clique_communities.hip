@@ -292,8 +292,6 @@ __global__ void k_pc_vfix(const int32_t *__restrict__ v_comm, int32_t *__restric
     if (v < nv && v_comm[v] == 0) v_first[v] = -1;
 }
 
-inline int pc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-
 } // namespace
 
 // the held list (listed, k_min <= k), 2 <= k and the budget's sign are checked by the caller (api.cpp).  The result is built on the
@@ -359,13 +357,13 @@ int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
         KOMB_HIP(ctx, staged_copy(ctx, d_verts, mx.verts.data(), (size_t)words * sizeof(int32_t), true));
         for (uint32_t *p : {d_rs, d_re}) KOMB_HIP(ctx, hipMemsetAsync(p, 0, (size_t)nv * sizeof(uint32_t), s));
         // ---- the incidence: keys (vertex, clique) of the member cliques, sorted; a vertex' row is its member cliques, ascending
-        k_pc_flag<<<pc_grid(nc), kBlock, 0, s>>>(d_off, unc, (uint32_t)k, d_msize, d_parent);
+        k_pc_flag<<<tiles_of(nc), kBlock, 0, s>>>(d_off, unc, (uint32_t)k, d_msize, d_parent);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_msize, d_mpos, nc));
-        k_pc_keys<<<pc_grid(words), kBlock, 0, s>>>(d_off, d_verts, d_msize, d_mpos, unc, uw, unv, d_keys, A.ctl);
+        k_pc_keys<<<tiles_of(words), kBlock, 0, s>>>(d_off, d_verts, d_msize, d_mpos, unc, uw, unv, d_keys, A.ctl);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, entries, 32 + key_bits(nv), &d_sorted));
-        k_pc_rows<<<pc_grid(entries), kBlock, 0, s>>>(d_sorted, ue, unv, unc, d_row, d_rs, d_re, A.ctl);
+        k_pc_rows<<<tiles_of(entries), kBlock, 0, s>>>(d_sorted, ue, unv, unc, d_row, d_rs, d_re, A.ctl);
         KOMB_HIP(ctx, hipGetLastError());
         // ---- the pivots and pair_tests, before anything is linked
         A.off = d_off; A.verts = d_verts; A.msize = d_msize; A.rs = d_rs; A.re = d_re; A.row = d_row; A.pstart = d_pstart; A.parent = d_parent;
@@ -392,9 +390,9 @@ int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
         KOMB_HIP(ctx, bufs.alloc(&d_flag, (size_t)nc));
         KOMB_HIP(ctx, bufs.alloc(&d_cnum, (size_t)nc));
         KOMB_HIP(ctx, hipMemsetAsync(d_csize, 0, (size_t)nc * sizeof(uint32_t), s));
-        k_pc_label<<<pc_grid(nc), kBlock, 0, s>>>(d_parent, d_msize, unc, d_label, d_csize);
+        k_pc_label<<<tiles_of(nc), kBlock, 0, s>>>(d_parent, d_msize, unc, d_label, d_csize);
         KOMB_HIP(ctx, hipGetLastError());
-        k_pc_sizes<<<pc_grid(nc), kBlock, 0, s>>>(d_label, d_csize, unc, d_size, d_flag);
+        k_pc_sizes<<<tiles_of(nc), kBlock, 0, s>>>(d_label, d_csize, unc, d_size, d_flag);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_cnum, nc));
         uint32_t tail[2] = {0u, 0u};
@@ -408,10 +406,10 @@ int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
         KOMB_HIP(ctx, bufs.alloc(&d_coff, (size_t)n_comm));
         KOMB_HIP(ctx, bufs.alloc(&d_cverts, (size_t)entries));
         KOMB_HIP(ctx, bufs.alloc(&d_vc, (size_t)std::max<int64_t>(2 * nv, 1)));   // v_comm[nv] | v_first[nv]
-        k_pc_reps<<<pc_grid(nc), kBlock, 0, s>>>(d_flag, d_cnum, d_csize, unc, d_rep, d_ncl);
+        k_pc_reps<<<tiles_of(nc), kBlock, 0, s>>>(d_flag, d_cnum, d_csize, unc, d_rep, d_ncl);
         KOMB_HIP(ctx, hipGetLastError());
         // ---- the communities' vertices: keys (community, vertex) of every member clique's vertices, sorted, distinct
-        k_pc_ckeys<<<pc_grid(words), kBlock, 0, s>>>(d_off, d_verts, d_msize, d_mpos, d_label, d_cnum, unc, uw, d_keys);
+        k_pc_ckeys<<<tiles_of(words), kBlock, 0, s>>>(d_off, d_verts, d_msize, d_mpos, d_label, d_cnum, unc, uw, d_keys);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_TRY(prim_sort_u64(ctx, d_keys, d_keys_alt, entries, 32 + key_bits(n_comm), &d_sorted));
         uint64_t *d_uniq = d_sorted == d_keys ? d_keys_alt : d_keys;
@@ -422,9 +420,9 @@ int clique_communities_run(komb_ctx *ctx, int32_t k, int64_t budget)
         KOMB_HIP(ctx, hipMemsetAsync(d_coff, 0, (size_t)n_comm * sizeof(uint32_t), s));
         KOMB_HIP(ctx, hipMemsetAsync(d_vc, 0, (size_t)nv * sizeof(int32_t), s));
         KOMB_HIP(ctx, hipMemsetAsync(d_vc + nv, 0x7F, (size_t)nv * sizeof(int32_t), s));
-        k_pc_comm<<<pc_grid(n_uniq), kBlock, 0, s>>>(d_uniq, (uint32_t)n_uniq, (uint32_t)n_comm, unv, d_coff, d_cverts, d_vc, d_vc + nv, A.ctl);
+        k_pc_comm<<<tiles_of(n_uniq), kBlock, 0, s>>>(d_uniq, (uint32_t)n_uniq, (uint32_t)n_comm, unv, d_coff, d_cverts, d_vc, d_vc + nv, A.ctl);
         KOMB_HIP(ctx, hipGetLastError());
-        k_pc_vfix<<<pc_grid(nv), kBlock, 0, s>>>(d_vc, d_vc + nv, unv);
+        k_pc_vfix<<<tiles_of(nv), kBlock, 0, s>>>(d_vc, d_vc + nv, unv);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, A.ctl, sizeof(PcCtl)));
         if (h.bad)

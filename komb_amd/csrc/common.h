@@ -30,6 +30,7 @@ struct Range {
 
 constexpr int kBlock = 256;                 // 4 wave64 per workgroup
 constexpr int kWave = 64;
+inline int tiles_of(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }   // workgroups of kBlock lanes, one lane per item
 // stamp / core value of a live edge / vertex: kAlive - c, where c = 0 for a unit with a short slice
 // ("light") and c = its number of kChunk-item chunks otherwise.  Whoever reads the marker to test
 // liveness (the SCAN sweep, the item that decrements the unit) learns the unit's class for free,
@@ -703,6 +704,8 @@ inline int key_bits(int64_t n)                            // bits that hold ever
 int prim_unique_u64(komb_ctx *ctx, const uint64_t *in, uint64_t *out, int64_t n, int64_t *n_out);
 int prim_exclusive_sum_u32(komb_ctx *ctx, const uint32_t *in, uint32_t *out, int64_t n);   // out[n-1] valid; in/out may alias
 int prim_exclusive_sum_u32_u64(komb_ctx *ctx, const uint32_t *in, unsigned long long *out, int64_t n);
+// flag[i] = i < m && val[i] >= k for i <= m, pos[] = its exclusive sum over m + 1: pos[i] places member i, pos[m] is their number
+int prim_flag_ge_scan(komb_ctx *ctx, const int32_t *val, int64_t m, int32_t k, uint32_t *flag, uint32_t *pos);
 int prim_sort_pairs_desc_i64(komb_ctx *ctx, int64_t *keys, int64_t *keys_tmp, uint32_t *vals, uint32_t *vals_tmp,
                              int64_t n, int end_bit, int64_t **sorted_keys, uint32_t **sorted_vals);
 
@@ -732,7 +735,6 @@ struct ForestState {                         // the working arrays of a run, one
     uint32_t cap;                            // items = entries of the log = the most nodes there can be
 };
 constexpr int kForestStepGrid = 2048;        // CLAIM / ADOPT: at most this many workgroups, each striding
-inline int forest_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 inline int forest_bits(uint32_t levels) { int b = 1; while (b < 32 && (1u << b) < levels) ++b; return b; }
 // off[k] = the first position of the ascending keys[n] with a key >= k, for k = 0 .. levels (queued; reads nothing back)
 void forest_offsets(komb_ctx *ctx, uint32_t n, const uint32_t *keys, uint32_t levels, uint32_t *off);

@@ -26,7 +26,6 @@ namespace {
 constexpr uint32_t kCommShort = 16;         // shorter side up to this long: the edge's own lane
 constexpr uint32_t kCommHeavy = 2048;       // from this length on: several workgroups of k_comm_heavy (between: the edge's wave)
 constexpr int kCommHeavyGrid = 256, kCommHeavyChunks = 8;   // k_comm_heavy: edges side by side x workgroups along one
-constexpr int kCommTailGrid = 2048;         // k_comm_count / k_comm_finish: workgroups, each over several tiles
 
 struct CommCtl {                            // 64 bytes, zeroed before every run
     uint32_t n_heavy;                       // edges queued for k_comm_heavy
@@ -35,16 +34,6 @@ struct CommCtl {                            // 64 bytes, zeroed before every run
     uint32_t pad[11];
 };
 static_assert(sizeof(CommCtl) == 64, "CommCtl layout");
-
-inline int comm_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-
-// flag[i] = edge i is a member (flag[m] = 0: the scan's last entry is the number of members)
-__global__ void k_comm_flag(const int32_t *__restrict__ truss, uint32_t m, int32_t k, uint32_t *__restrict__ flag)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i > m) return;
-    flag[i] = i < m && truss[i] >= k ? 1u : 0u;
-}
 
 // the member list in canonical order; every member a class of its own
 __global__ void k_comm_compact(const int32_t *__restrict__ eu, const int32_t *__restrict__ ev, const int32_t *__restrict__ truss,
@@ -115,41 +104,7 @@ __global__ void k_comm_flatten(const uint32_t *__restrict__ n_mem, int32_t *pare
 {
     const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= *n_mem) return;
-    const int32_t r = kFinal ? comp_find_ro(parent, (int32_t)j) : comp_find(parent, (int32_t)j);
-    if (r != (int32_t)j) pstore(parent + j, r);
-}
-
-// cnt[root] += members under it (k_comp_count's scheme over edges).  Lanes of a wave that share a root add once; what a
-// workgroup adds to the root its first tile starts with (the giant community's, nearly always) it sums in LDS first:
-// one global atomic per workgroup.
-__global__ void k_comm_count(const uint32_t *__restrict__ n_mem, const int32_t *__restrict__ root, uint32_t *cnt)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const uint32_t nm = *n_mem;
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t j0 = blockIdx.x * kBlock;
-    if (threadIdx.x == 0) { s_first = j0 < nm ? root[j0] : -1; s_sum = 0u; }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t base = j0; base < nm; base += gridDim.x * kBlock) {      // (uniform per workgroup: the ballots see whole waves)
-        const uint32_t j = base + threadIdx.x;
-        const int32_t lab = j < nm ? root[j] : -1;
-        const bool act = lab >= 0;
-        unsigned long long m = __ballot(act);
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(lab, src);
-            const unsigned long long same = __ballot(act && lab == lead);
-            if (lane == src) {
-                if (lead == first) atomicAdd(&s_sum, (uint32_t)__popcll(same));
-                else atomicAdd(cnt + lead, (uint32_t)__popcll(same));
-            }
-            m &= ~same;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(cnt + first, s_sum);
+    comp_flatten<kFinal>(parent, j);
 }
 
 // canonical order again: label[i] = kept[root], size[i] = cnt[root] (-1 / 0 for a non-member); members, communities
@@ -158,10 +113,6 @@ __global__ void k_comm_finish(uint32_t m, const int32_t *__restrict__ truss, int
                               const int32_t *__restrict__ root, const int32_t *__restrict__ kept, const uint32_t *__restrict__ cnt,
                               int32_t *__restrict__ label, int32_t *__restrict__ size, CommCtl *ctl)
 {
-    __shared__ uint32_t s_mem, s_comm, s_max;
-    if (threadIdx.x == 0) { s_mem = 0u; s_comm = 0u; s_max = 0u; }
-    __syncthreads();
-    const int lane = threadIdx.x & (kWave - 1);
     uint32_t n_mem = 0, n_root = 0, mx = 0;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < m; i += gridDim.x * kBlock) {
         int32_t lab = -1; uint32_t sz = 0u;
@@ -174,18 +125,7 @@ __global__ void k_comm_finish(uint32_t m, const int32_t *__restrict__ truss, int
         }
         label[i] = lab; size[i] = (int32_t)sz;
     }
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        n_mem += (uint32_t)__shfl_xor((int32_t)n_mem, o);
-        n_root += (uint32_t)__shfl_xor((int32_t)n_root, o);
-        const uint32_t other = (uint32_t)__shfl_xor((int32_t)mx, o);
-        mx = other > mx ? other : mx;
-    }
-    if (lane == 0 && n_mem) { atomicAdd(&s_mem, n_mem); atomicAdd(&s_comm, n_root); atomicMax(&s_max, mx); }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_mem) {
-        atomicAdd(&ctl->n_members, s_mem);
-        if (s_comm) { atomicAdd(&ctl->n_communities, s_comm); atomicMax(&ctl->largest, s_max); }
-    }
+    class_totals(n_mem, n_root, mx, &ctl->n_members, &ctl->n_communities, &ctl->largest);
 }
 
 // ---- the vertex pass: n_comm[v] = distinct labels among the member edges at v
@@ -273,11 +213,10 @@ int communities_run(komb_ctx *ctx, int32_t k)
     const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *truss = ctx->d_t_truss;
     const uint32_t *d_nm = d_pos + m;                // the number of members, on the device
     uint32_t *d_cnt = d_flag;
-    const int grid = comm_grid(m), grid1 = comm_grid(m + 1);
+    const int grid = tiles_of(m);
     ctx->timer.start(s);
     KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(CommCtl), s));
-    k_comm_flag<<<grid1, kBlock, 0, s>>>(truss, (uint32_t)m, k, d_flag);
-    KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
+    KOMB_TRY(prim_flag_ge_scan(ctx, truss, m, k, d_flag, d_pos));
     k_comm_compact<<<grid, kBlock, 0, s>>>(eu, ev, truss, (uint32_t)m, k, d_pos, d_kept, d_mu, d_mv, d_parent, d_cnt);
     KOMB_TRY(oriented_rows(ctx, bufs, d_mu, m, d_nm, &d_rs, &d_re));
     k_comm_tri<<<grid, kBlock, 0, s>>>(d_mu, d_mv, d_rs, d_re, d_nm, d_parent, d_ctl, d_heavy, heavy_cap, n_short, n_heavy);
@@ -285,9 +224,8 @@ int communities_run(komb_ctx *ctx, int32_t k)
     // two passes: the first compresses, the second labels -- read-only walks of a step or two
     k_comm_flatten<false><<<grid, kBlock, 0, s>>>(d_nm, d_parent);
     k_comm_flatten<true><<<grid, kBlock, 0, s>>>(d_nm, d_parent);
-    const int tail_grid = grid < kCommTailGrid ? grid : kCommTailGrid;
-    k_comm_count<<<tail_grid, kBlock, 0, s>>>(d_nm, d_parent, d_cnt);
-    k_comm_finish<<<tail_grid, kBlock, 0, s>>>((uint32_t)m, truss, k, d_pos, d_parent, d_kept, d_cnt, res.label, res.size, d_ctl);
+    class_count(ctx, m, d_nm, d_parent, d_cnt);
+    k_comm_finish<<<class_tail_grid(m), kBlock, 0, s>>>((uint32_t)m, truss, k, d_pos, d_parent, d_kept, d_cnt, res.label, res.size, d_ctl);
     const double ms = ctx->timer.stop(s);
     KOMB_HIP(ctx, hipGetLastError());
     CommCtl h;
@@ -321,16 +259,16 @@ int communities_vertices(komb_ctx *ctx)
         KOMB_HIP(ctx, bufs.alloc(&d_keys, 2 * (size_t)nm));
         KOMB_HIP(ctx, bufs.alloc(&d_tmp, 2 * (size_t)nm));
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(CommCtl), s));
-        k_comm_vflag<<<comm_grid(m + 1), kBlock, 0, s>>>(ctx->comm.label, (uint32_t)m, d_flag);
+        k_comm_vflag<<<tiles_of(m + 1), kBlock, 0, s>>>(ctx->comm.label, (uint32_t)m, d_flag);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
-        k_comm_keys<<<comm_grid(m), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, ctx->comm.label, (uint32_t)m, d_pos, d_keys);
+        k_comm_keys<<<tiles_of(m), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, ctx->comm.label, (uint32_t)m, d_pos, d_keys);
         int vb = 1;
         while (vb < 31 && (1ll << vb) < nv) ++vb;
         KOMB_TRY(prim_sort_u64(ctx, d_keys, d_tmp, 2 * nm, 32 + vb, &sorted));
         uint64_t *uniq = sorted == d_keys ? d_tmp : d_keys;
         int64_t n_u = 0;
         KOMB_TRY(prim_unique_u64(ctx, sorted, uniq, 2 * nm, &n_u));
-        k_comm_runs<<<comm_grid(n_u), kBlock, 0, s>>>(uniq, (uint32_t)n_u, ctx->comm.ncomm, d_ctl);
+        k_comm_runs<<<tiles_of(n_u), kBlock, 0, s>>>(uniq, (uint32_t)n_u, ctx->comm.ncomm, d_ctl);
         KOMB_HIP(ctx, hipGetLastError());
         CommCtl h;
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(CommCtl)));

@@ -39,14 +39,6 @@ static_assert(sizeof(ChCtl) == 64 && offsetof(ChCtl, f) == 0, "ChCtl layout");
 
 // ---- members: the edges of trussness >= 3 in canonical order
 
-// flag[i] = edge i is a member (flag[m] = 0: the scan's last entry is the number of members)
-__global__ void k_ch_flag(const int32_t *__restrict__ truss, uint32_t m, uint32_t *__restrict__ flag)
-{
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i > m) return;
-    flag[i] = i < m && truss[i] >= 3 ? 1u : 0u;
-}
-
 // the member list; every member a class of its own that stands for no node yet
 __global__ void k_ch_compact(const int32_t *__restrict__ eu, const int32_t *__restrict__ ev, const int32_t *__restrict__ truss,
                              uint32_t m, uint32_t levels, const uint32_t *__restrict__ pos, int32_t *__restrict__ kept,
@@ -83,16 +75,8 @@ struct ChStream { uint32_t *keys; unsigned long long *vals; uint32_t cap; };   /
 // of the wave calls it.
 __device__ __forceinline__ void ch_emit(bool hit, uint32_t j, uint32_t x, uint32_t y, const int32_t *__restrict__ mt, ChCtl *ctl, const ChStream &st)
 {
-    const unsigned long long m = __ballot(hit);
-    if (!m) return;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lead = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == lead) base = atomicAdd(&ctl->rec_n, 2u * (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int32_t)base, lead);
-    if (!hit) return;
-    const uint32_t slot = base + 2u * (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (slot >= st.cap || st.cap - slot < 2u) return;       // (cannot happen: the counting launch found every hit; the host checks rec_n)
+    const uint32_t slot = wave_append(hit, &ctl->rec_n, 2u);
+    if (!hit || slot >= st.cap || st.cap - slot < 2u) return;       // (cannot happen: the counting launch found every hit; the host checks rec_n)
     const int32_t tj = mt[j], tx = mt[x], ty = mt[y];
     const int32_t w = tj < tx ? (tj < ty ? tj : ty) : (tx < ty ? tx : ty);
     st.keys[slot] = (uint32_t)w;     st.vals[slot] = ((unsigned long long)j << 32) | x;
@@ -264,11 +248,10 @@ int community_hierarchy_run(komb_ctx *ctx)
         const int32_t *eu = ctx->d_t_eu, *ev = ctx->d_t_ev, *truss = ctx->d_t_truss;
         const uint32_t *d_nm = d_pos + m;                        // the number of members, on the device
         uint32_t *cnt = d_flag;
-        const int grid = forest_grid(m);
+        const int grid = tiles_of(m);
         ctx->timer.start(s);
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(ChCtl), s));
-        k_ch_flag<<<forest_grid(m + 1), kBlock, 0, s>>>(truss, (uint32_t)m, d_flag);
-        KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, m + 1));
+        KOMB_TRY(prim_flag_ge_scan(ctx, truss, m, 3, d_flag, d_pos));
         k_ch_compact<<<grid, kBlock, 0, s>>>(eu, ev, truss, (uint32_t)m, levels, d_pos, kept, mu, mv, mt, mkeys, mvals, parent, cnt, cur, claimk);
         KOMB_TRY(oriented_rows(ctx, bufs, mu, m, d_nm, &d_rs, &d_re));
         // the counting launch: the triangles of the result (an edge of a triangle has trussness >= 3: all of them are found here)
@@ -310,7 +293,7 @@ int community_hierarchy_run(komb_ctx *ctx)
             uint32_t *d_moff = d_tab, *d_roff = d_tab + levels + 1;
             KOMB_HIP(ctx, hipMemsetAsync(d_tab, 0, tab_words * sizeof(uint32_t), s));
 
-            const int mgrid = forest_grid(nm);
+            const int mgrid = tiles_of(nm);
             k_ch_tri<true><<<mgrid, kBlock, 0, s>>>(mu, mv, mt, d_rs, d_re, d_nm, d_ctl, d_heavy, heavy_cap, n_short, n_heavy, st);
             if (h.n_heavy)
                 k_ch_heavy<true><<<dim3(kChHeavyGrid, kChHeavyChunks), kBlock, 0, s>>>(mu, mv, mt, d_rs, d_re, d_ctl, d_heavy, heavy_cap, st);
@@ -340,7 +323,7 @@ int community_hierarchy_run(komb_ctx *ctx)
                 const uint32_t r_b = roff[k], r_n = roff[k + 1] - roff[k];
                 if (!sh_n) continue;                                                    // (a record of weight k has an edge of trussness k)
                 if (li == 0) res.kmax = k;
-                if (r_n) k_ch_link<<<forest_grid(r_n), kBlock, 0, s>>>(recs, r_b, r_n, nm, parent, d_ctl, log, nm);
+                if (r_n) k_ch_link<<<tiles_of(r_n), kBlock, 0, s>>>(recs, r_b, r_n, nm, parent, d_ctl, log, nm);
                 forest_level(ctx, f, k, li, false, mord, sh_b, sh_n, r_n < nm ? r_n : nm);      // at most this many hooks at this level
                 ++li;
             }
@@ -387,7 +370,7 @@ int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t
     KOMB_HIP(ctx, bufs.alloc(&d_size, (size_t)m));
     const int32_t *nodes = ctx->ch.nodes;
     const size_t c = (size_t)ctx->ch.cap;
-    k_ch_labels<<<forest_grid(m), kBlock, 0, s>>>((uint32_t)m, k, ctx->ch.enode, (uint32_t)ctx->ch.n_nodes, nodes, nodes + c, nodes + 2 * c,
+    k_ch_labels<<<tiles_of(m), kBlock, 0, s>>>((uint32_t)m, k, ctx->ch.enode, (uint32_t)ctx->ch.n_nodes, nodes, nodes + c, nodes + 2 * c,
                                               nodes + 3 * c, d_label, d_size);
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, hipStreamSynchronize(s));

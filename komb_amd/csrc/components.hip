@@ -28,8 +28,7 @@
 //    runs in a launch before it.
 // Every access to parent[] inside the linking launches is a relaxed agent-scope atomic load / store (it bypasses the
 // L1, so a walk sees a hook soon, and no dirty line of parent[] waits in an L2 behind an atomic of another XCD).
-#include "common.h"
-#include "unionfind_dev.h"   // pload / pstore, comp_find, comp_find_ro, comp_link (shared with communities.hip)
+#include "unionfind_dev.h"   // pload / pstore, comp_find, comp_link, the class tail (shared with communities.hip); wave_dev.h
 
 namespace komb {
 
@@ -40,7 +39,6 @@ constexpr uint32_t kCompHeavy = 2048;       // rows from this length on: several
 constexpr uint32_t kCompWindow = 16;        // sampling pass: entries of a row it looks at for its two neighbours
 constexpr int kCompSamples = 1024;          // vertices whose roots vote for the giant component
 constexpr int kCompHeavyGrid = 256, kCompHeavyChunks = 8;   // k_comp_heavy: rows side by side x workgroups along a row
-constexpr int kCompTailGrid = 2048;        // k_comp_count / k_comp_finish: workgroups, each over several tiles
 
 struct CompCtl {                            // 64 bytes, zeroed before every run
     int32_t  giant;                         // root of the most frequent component of the sample (-1: none)
@@ -94,8 +92,7 @@ __global__ void k_comp_flatten(uint32_t nv, int32_t *parent, const int32_t *__re
     const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
     if (v >= nv) return;
     if (!flag[v]) { if (kFinal) pstore(parent + v, -1); return; }
-    const int32_t r = kFinal ? comp_find_ro(parent, (int32_t)v) : comp_find(parent, (int32_t)v);
-    if (r != (int32_t)v) pstore(parent + v, r);
+    comp_flatten<kFinal>(parent, v);
 }
 
 // the most frequent root among kCompSamples evenly spaced vertices (ties: the smaller id); one workgroup
@@ -148,14 +145,11 @@ __global__ void k_comp_rows(const uint32_t *__restrict__ rowptr, const int32_t *
     const bool mid = act && deg > kCompShort;
     if (act && !mid)
         for (uint32_t i = b; i < e; ++i) comp_entry<kAll, kBoth>(core, k, parent, (int32_t)v, col[i]);
-    unsigned long long m = __ballot(mid);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int32_t rv = __shfl((int32_t)v, src);
-        const uint32_t rb = (uint32_t)__shfl((int32_t)b, src), re = (uint32_t)__shfl((int32_t)e, src);
-        for (uint32_t i = rb + (uint32_t)lane; i < re; i += kWave) comp_entry<kAll, kBoth>(core, k, parent, rv, col[i]);
-    }
+    wave_turns(mid, [&](int src) {
+        const int32_t rv = (int32_t)from_lane(v, src);
+        const uint32_t rb = from_lane(b, src), rn = from_lane(deg, src);
+        wave_walk(rb, rn, lane, [&](uint32_t i) { comp_entry<kAll, kBoth>(core, k, parent, rv, col[i]); });
+    });
 }
 
 // the queued rows: block (x, y) takes the rows x, x + gridDim.x, ... and of each the entries y * kBlock + lane, stepping gridDim.y * kBlock
@@ -184,44 +178,9 @@ __global__ void k_comp_truss(const int32_t *__restrict__ eu, const int32_t *__re
     comp_link(parent, u, v);
 }
 
-// cnt[root] += members under it.  Lanes of a wave that share a label add once; what a workgroup adds to the label its
-// first tile starts with (the giant component's, nearly always) it sums in LDS first: one global atomic per workgroup.
-__global__ void k_comp_count(uint32_t nv, const int32_t *__restrict__ label, uint32_t *cnt)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t v0 = blockIdx.x * kBlock;
-    if (threadIdx.x == 0) { s_first = v0 < nv ? label[v0] : -1; s_sum = 0u; }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t base = v0; base < nv; base += gridDim.x * kBlock) {      // (uniform per workgroup: the ballots see whole waves)
-        const uint32_t v = base + threadIdx.x;
-        const int32_t lab = v < nv ? label[v] : -1;
-        const bool act = lab >= 0;
-        unsigned long long m = __ballot(act);
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(lab, src);
-            const unsigned long long same = __ballot(act && lab == lead);
-            if (lane == src) {
-                if (lead == first) atomicAdd(&s_sum, (uint32_t)__popcll(same));
-                else atomicAdd(cnt + lead, (uint32_t)__popcll(same));
-            }
-            m &= ~same;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(cnt + first, s_sum);
-}
-
 // size[v] = cnt[label[v]] (0 for a non-member); members, components (label[v] == v) and the largest size summed up per workgroup
 __global__ void k_comp_finish(uint32_t nv, const int32_t *__restrict__ label, const uint32_t *__restrict__ cnt, int32_t *__restrict__ size, CompCtl *ctl)
 {
-    __shared__ uint32_t s_mem, s_comp, s_max;
-    if (threadIdx.x == 0) { s_mem = 0u; s_comp = 0u; s_max = 0u; }
-    __syncthreads();
-    const int lane = threadIdx.x & (kWave - 1);
     uint32_t n_mem = 0, n_root = 0, mx = 0;
     for (uint32_t v = blockIdx.x * kBlock + threadIdx.x; v < nv; v += gridDim.x * kBlock) {
         const int32_t lab = label[v];
@@ -230,21 +189,8 @@ __global__ void k_comp_finish(uint32_t nv, const int32_t *__restrict__ label, co
         n_mem += lab >= 0 ? 1u : 0u;
         if (lab == (int32_t)v) { ++n_root; mx = sz > mx ? sz : mx; }
     }
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        n_mem += (uint32_t)__shfl_xor((int32_t)n_mem, o);
-        n_root += (uint32_t)__shfl_xor((int32_t)n_root, o);
-        const uint32_t other = (uint32_t)__shfl_xor((int32_t)mx, o);
-        mx = other > mx ? other : mx;
-    }
-    if (lane == 0 && n_mem) { atomicAdd(&s_mem, n_mem); atomicAdd(&s_comp, n_root); atomicMax(&s_max, mx); }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_mem) {
-        atomicAdd(&ctl->n_members, s_mem);
-        if (s_comp) { atomicAdd(&ctl->n_components, s_comp); atomicMax(&ctl->largest, s_max); }
-    }
+    class_totals(n_mem, n_root, mx, &ctl->n_members, &ctl->n_components, &ctl->largest);
 }
-
-inline int comp_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
 // the linking launches of the core kind (kAll: k == 0, no coreness is read)
 template <bool kAll>
@@ -252,7 +198,7 @@ void comp_link_rows(komb_ctx *ctx, bool sample, int32_t k, int32_t *parent, cons
 {
     hipStream_t s = ctx->stream;
     const uint32_t nv = (uint32_t)ctx->nv;
-    const int grid = comp_grid(nv);
+    const int grid = tiles_of(nv);
     const uint32_t *rp = ctx->d_o_rowptr; const int32_t *col = ctx->d_o_col, *core = ctx->core.core;
     if (sample) {
         k_comp_sample<kAll><<<grid, kBlock, 0, s>>>(rp, col, core, k, nv, parent, flag);
@@ -297,7 +243,7 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k)
     const bool sample = so ? strcmp(so, "0") != 0 : true;
 
     int32_t *parent = ctx->comp.label, *flag = ctx->comp.size;
-    const int grid = comp_grid(nv);
+    const int grid = tiles_of(nv);
     const bool all = !truss && k == 0;
     // (core kind above the largest coreness: nobody is a member, and nothing is linked)
     const bool none = truss || (k > 0 && k > ctx->stats.max_coreness);
@@ -305,7 +251,7 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k)
     KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(CompCtl), s));
     k_comp_init<<<grid, kBlock, 0, s>>>((uint32_t)nv, ctx->core.core, k, all, none, parent, flag, d_cnt);
     if (truss) {
-        if (m > 0) k_comp_truss<<<comp_grid(m), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, ctx->d_t_truss, (uint32_t)m, k, parent, flag);
+        if (m > 0) k_comp_truss<<<tiles_of(m), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, ctx->d_t_truss, (uint32_t)m, k, parent, flag);
     } else if (!none && ctx->ne > 0) {
         if (all) comp_link_rows<true>(ctx, sample, k, parent, flag, d_ctl, d_heavy, heavy_cap);
         else comp_link_rows<false>(ctx, sample, k, parent, flag, d_ctl, d_heavy, heavy_cap);
@@ -314,9 +260,8 @@ int components_run(komb_ctx *ctx, int32_t kind, int32_t k)
     // passes), the second labels -- read-only walks of a step or two
     k_comp_flatten<false><<<grid, kBlock, 0, s>>>((uint32_t)nv, parent, flag);
     k_comp_flatten<true><<<grid, kBlock, 0, s>>>((uint32_t)nv, parent, flag);
-    const int tail_grid = grid < kCompTailGrid ? grid : kCompTailGrid;
-    k_comp_count<<<tail_grid, kBlock, 0, s>>>((uint32_t)nv, parent, d_cnt);
-    k_comp_finish<<<tail_grid, kBlock, 0, s>>>((uint32_t)nv, parent, d_cnt, ctx->comp.size, d_ctl);
+    class_count(ctx, nv, nullptr, parent, d_cnt);
+    k_comp_finish<<<class_tail_grid(nv), kBlock, 0, s>>>((uint32_t)nv, parent, d_cnt, ctx->comp.size, d_ctl);
     const double ms = ctx->timer.stop(s);
     KOMB_HIP(ctx, hipGetLastError());
     CompCtl h;

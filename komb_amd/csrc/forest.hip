@@ -36,7 +36,7 @@
 // - Every ballot sits in a loop whose bounds are uniform over its workgroup, so all lanes of a wave take part in it.
 // - The hot word.  Nearly all items end in one giant class, whose cnt / shell word would take one atomic per wave.  What
 //   goes to the root (CLAIM) or node (ADOPT) of the workgroup's first entry is summed in LDS and added once per workgroup
-//   (k_comm_count's scheme).
+//   (k_class_count's scheme).
 // Every access to parent[] is a relaxed agent-scope atomic (the header comment of components.hip says why that suffices).
 #include "forest_dev.h"
 
@@ -57,19 +57,11 @@ __global__ void k_forest_offsets(uint32_t n, const uint32_t *__restrict__ keys, 
 // summed in *s_sum (LDS) for the workgroup's one global atomic.  Every lane of the wave calls it.
 __device__ __forceinline__ void forest_group_add(uint32_t *arr, int32_t key, int32_t first, uint32_t *s_sum)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const bool act = key >= 0;
-    unsigned long long m = __ballot(act);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        const int32_t lead = __shfl(key, src);
-        const unsigned long long same = __ballot(act && key == lead);
-        if (lane == src) {
-            if (lead == first) atomicAdd(s_sum, (uint32_t)__popcll(same));
-            else atomicAdd(arr + lead, (uint32_t)__popcll(same));
-        }
-        m &= ~same;
-    }
+    wave_by_key(key >= 0, key, [&](int32_t lead, unsigned long long same, bool is_leader) {
+        if (!is_leader) return;
+        if (lead == first) atomicAdd(s_sum, (uint32_t)__popcll(same));
+        else atomicAdd(arr + lead, (uint32_t)__popcll(same));
+    });
 }
 
 // the node (k, r) of root r, made by the first lane that asks for it at this level
@@ -97,7 +89,6 @@ __global__ void k_forest_claim(int32_t k, uint32_t li, bool isolated, const uint
     if (le > cap) le = cap;
     const uint32_t b0 = blockIdx.x * kBlock, stride = gridDim.x * kBlock;
     if (b0 + threadIdx.x == 0) seg[li + 1] = le;                 // (read by later launches only)
-    const int lane = threadIdx.x & (kWave - 1);
     if (threadIdx.x == 0) {                                      // the root this workgroup's first entry has
         s_first = lb + b0 < le ? comp_find(parent, log[lb + b0]) : (b0 < sh_n ? comp_find(parent, (int32_t)order[sh_b + b0]) : -1);
         s_sum = 0u;
@@ -116,15 +107,10 @@ __global__ void k_forest_claim(int32_t k, uint32_t li, bool isolated, const uint
             else if (c) atomicAdd(cnt + r, c);
         }
         mine = wave_sum(mine);
-        if (lane == 0 && mine) atomicAdd(&s_sum, mine);
-        unsigned long long m = __ballot(r >= 0);                 // one lane per distinct root of the wave asks for its node
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(r, src);
-            const unsigned long long same = __ballot(r == lead);
-            if (lane == src) forest_claim(lead, k, ctl, claimk, cur, t, cap);
-            m &= ~same;
-        }
+        if ((threadIdx.x & (kWave - 1)) == 0 && mine) atomicAdd(&s_sum, mine);
+        wave_by_key(r >= 0, r, [&](int32_t lead, unsigned long long, bool is_leader) {   // one lane per distinct root asks for its node
+            if (is_leader) forest_claim(lead, k, ctl, claimk, cur, t, cap);
+        });
     }
     for (uint32_t base = b0; base < sh_n; base += stride) {      // (uniform per workgroup)
         const uint32_t j = base + threadIdx.x;
@@ -223,7 +209,7 @@ __global__ void k_forest_depth(uint32_t n, const int32_t *__restrict__ par, Fore
 
 void forest_offsets(komb_ctx *ctx, uint32_t n, const uint32_t *keys, uint32_t levels, uint32_t *off)
 {
-    k_forest_offsets<<<forest_grid((int64_t)n + 1), kBlock, 0, ctx->stream>>>(n, keys, levels, off);
+    k_forest_offsets<<<tiles_of((int64_t)n + 1), kBlock, 0, ctx->stream>>>(n, keys, levels, off);
 }
 
 void forest_level(komb_ctx *ctx, const ForestState &f, int32_t k, uint32_t li, bool isolated, const uint32_t *order, uint32_t sh_b,
@@ -244,7 +230,7 @@ int forest_tail(komb_ctx *ctx, DevBufs &bufs, const ForestState &f, uint32_t n, 
     uint32_t *order = nullptr;
     KOMB_HIP(ctx, bufs.alloc(&nkeys, (size_t)n));
     KOMB_HIP(ctx, bufs.alloc(&nkeys2, (size_t)n));
-    const int grid = forest_grid(n);
+    const int grid = tiles_of(n);
     k_forest_node_keys<<<grid, kBlock, 0, s>>>(n, f.made, nkeys, vals);
     KOMB_TRY(prim_sort_pairs_u64_u32(ctx, nkeys, nkeys2, vals, vals_alt, n, 32 + bits, &nsorted, &order));
     k_forest_ranks<<<grid, kBlock, 0, s>>>(n, order, rank);

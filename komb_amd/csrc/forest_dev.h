@@ -3,25 +3,16 @@
 // forest.  The structures and the host side are in common.h.
 #pragma once
 
-#include "common.h"
 #include "unionfind_dev.h"
 
 namespace komb {
 
-// a wave's hooks (hooked >= 0) into the log, its slots taken with one atomic.  Every lane of the wave calls it: a LINK
-// kernel whose lanes diverge around the call (row loops of different lengths) appends per lane instead.
+// a wave's hooks (hooked >= 0) into the log, its slots taken with one atomic (wave_append).  Every lane of the wave calls
+// it: a LINK kernel whose lanes diverge around the call (row loops of different lengths) appends per lane instead.
 __device__ __forceinline__ void forest_log_wave(int32_t hooked, ForestCtl *ctl, int32_t *__restrict__ log, uint32_t cap)
 {
-    const unsigned long long m = __ballot(hooked >= 0);
-    if (!m) return;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lead = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == lead) base = atomicAdd(&ctl->log_n, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int32_t)base, lead);
-    if (hooked < 0) return;
-    const uint32_t slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (slot < cap) log[slot] = hooked;      // (cannot overflow: an item is hooked once)
+    const uint32_t slot = wave_append(hooked >= 0, &ctl->log_n);
+    if (hooked >= 0 && slot < cap) log[slot] = hooked;      // (cannot overflow: an item is hooked once)
 }
 
 // from node c (0 <= c < the number of nodes, level nk[c] >= k) up while the parent's level is still >= k: the node of c's

@@ -229,7 +229,7 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
     KOMB_HIP(ctx, bufs.alloc(&d_tab, tab_words));
     uint32_t *d_voff = d_tab, *d_second = d_tab + levels + 1;
 
-    const int grid = forest_grid(nv);
+    const int grid = tiles_of(nv);
     const int bits = forest_bits(levels);
     ctx->timer.start(s);
     KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(HierCtl), s));
@@ -237,7 +237,7 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
     k_hier_init<<<grid, kBlock, 0, s>>>((uint32_t)nv, parent, cur, claimk, cnt, vnode, lvl);
     uint32_t *vord = nullptr, *eord = nullptr, *sorted_keys = nullptr;
     if (truss) {
-        if (m > 0) k_hier_keys_edges<<<forest_grid(m), kBlock, 0, s>>>((uint32_t)m, ctx->d_t_eu, ctx->d_t_ev, ctx->d_t_truss, levels, ekeys, evals, lvl);
+        if (m > 0) k_hier_keys_edges<<<tiles_of(m), kBlock, 0, s>>>((uint32_t)m, ctx->d_t_eu, ctx->d_t_ev, ctx->d_t_truss, levels, ekeys, evals, lvl);
         KOMB_TRY(prim_sort_pairs_u32_u32(ctx, ekeys, ekeys2, evals, evals2, m, bits, &sorted_keys, &eord));
         forest_offsets(ctx, (uint32_t)m, sorted_keys, levels, d_second);
         k_hier_keys_lvl<<<grid, kBlock, 0, s>>>((uint32_t)nv, lvl, vkeys, vvals);
@@ -270,11 +270,11 @@ int hierarchy_run(komb_ctx *ctx, int32_t kind)
         if (li == 0) k_top = k;
         uint64_t hooks;                                      // at most this many hooks at this level
         if (truss) {
-            k_hier_edges<<<forest_grid(e_n), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, eord, second[k], e_n, parent, d_ctl, log, (uint32_t)nv);
+            k_hier_edges<<<tiles_of(e_n), kBlock, 0, s>>>(ctx->d_t_eu, ctx->d_t_ev, eord, second[k], e_n, parent, d_ctl, log, (uint32_t)nv);
             hooks = e_n < (uint64_t)nv ? e_n : (uint64_t)nv;
         } else {
             if (k > 0) {                                     // (coreness 0: no row has an entry)
-                k_hier_rows<<<forest_grid(sh_n), kBlock, 0, s>>>(ctx->d_o_rowptr, ctx->d_o_col, ctx->core.core, k, vord, sh_b, sh_n, parent, d_ctl,
+                k_hier_rows<<<tiles_of(sh_n), kBlock, 0, s>>>(ctx->d_o_rowptr, ctx->d_o_col, ctx->core.core, k, vord, sh_b, sh_n, parent, d_ctl,
                                                                d_heavy, heavy_cap, log, (uint32_t)nv);
                 if (second[k])
                     k_hier_heavy<<<dim3(second[k] < (uint32_t)kHierHeavyGrid ? second[k] : kHierHeavyGrid, kHierHeavyChunks), kBlock, 0, s>>>(

@@ -58,8 +58,7 @@ struct NucCtl {                             // 64 bytes, zeroed before every run
 };
 static_assert(sizeof(NucCtl) == 64, "NucCtl layout");
 
-inline int nuc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-inline int nuc_sweep(int64_t n) { const int g = nuc_grid(n); return g < 1 ? 1 : (g < kNucSweepGrid ? g : kNucSweepGrid); }
+inline int nuc_sweep(int64_t n) { const int g = tiles_of(n); return g < 1 ? 1 : (g < kNucSweepGrid ? g : kNucSweepGrid); }
 
 __device__ __forceinline__ void nuc_emit(const NucTri &o, uint32_t t, uint32_t j, int32_t a, int32_t b, int32_t c, uint32_t x, uint32_t hit, bool walk_a)
 {
@@ -392,7 +391,7 @@ int nucleus_run(komb_ctx *ctx)
         KOMB_HIP(ctx, bufs.alloc(&d_cnt, (size_t)m + 1));        // counts, then tri_ptr
         const NucTri none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         KOMB_TRY(oriented_rows(ctx, bufs, eu, m, nullptr, &d_rs, &d_re));
-        k_nuc_tri<false><<<nuc_grid(m + 1), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, d_cnt, nullptr, d_ctl, n_short, n_heavy, none);
+        k_nuc_tri<false><<<tiles_of(m + 1), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, d_cnt, nullptr, d_ctl, n_short, n_heavy, none);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));
         const uint32_t n_queued = h.n_heavy < um ? h.n_heavy : um;
@@ -400,7 +399,7 @@ int nucleus_run(komb_ctx *ctx)
         if (n_queued) {
             KOMB_HIP(ctx, bufs.alloc(&d_heavy, (size_t)n_queued));          // (sized from the count, as the clique storage is)
             KOMB_HIP(ctx, bufs.alloc(&d_part, (size_t)n_queued * kNucHeavyChunks));
-            k_nuc_queue<<<nuc_grid(m), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, n_heavy, d_ctl, d_heavy, n_queued);
+            k_nuc_queue<<<tiles_of(m), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, n_heavy, d_ctl, d_heavy, n_queued);
             k_nuc_tri_heavy<false><<<hgrid, kBlock, 0, s>>>(eu, ev, d_rs, d_re, d_cnt, nullptr, d_ctl, d_heavy, n_queued, d_part, none);
             KOMB_HIP(ctx, hipGetLastError());
             KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));
@@ -422,7 +421,7 @@ int nucleus_run(komb_ctx *ctx)
             KOMB_HIP(ctx, bufs.alloc(&o.j, (size_t)T));
             KOMB_HIP(ctx, bufs.alloc(&o.pac, (size_t)T));
             KOMB_HIP(ctx, bufs.alloc(&o.pbc, (size_t)T));
-            k_nuc_tri<true><<<nuc_grid(m), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, nullptr, tri_ptr, d_ctl, n_short, n_heavy, o);
+            k_nuc_tri<true><<<tiles_of(m), kBlock, 0, s>>>(eu, ev, d_rs, d_re, um, nullptr, tri_ptr, d_ctl, n_short, n_heavy, o);
             if (n_queued) k_nuc_tri_heavy<true><<<hgrid, kBlock, 0, s>>>(eu, ev, d_rs, d_re, nullptr, tri_ptr, d_ctl, d_heavy, n_queued, d_part, o);
             KOMB_HIP(ctx, hipGetLastError());
             (void)hipEventRecord(e_t1, s);
@@ -434,7 +433,7 @@ int nucleus_run(komb_ctx *ctx)
             uint32_t *key0 = (uint32_t *)res.key0.get();
             KOMB_HIP(ctx, bufs.alloc(&d_qcnt, (size_t)T + 1));   // counts, then q_ptr
             (void)hipEventRecord(e_q0, s);
-            k_nuc_clq<false><<<nuc_grid(T + 1), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, d_qcnt, nullptr, nullptr, nullptr, d_ctl, n_short);
+            k_nuc_clq<false><<<tiles_of(T + 1), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, d_qcnt, nullptr, nullptr, nullptr, d_ctl, n_short);
             KOMB_HIP(ctx, hipGetLastError());
             KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NucCtl)));
             if (h.n_clq > (unsigned long long)cap)
@@ -454,10 +453,10 @@ int nucleus_run(komb_ctx *ctx)
             KOMB_HIP(ctx, hipMemsetAsync(d_cur, 0, (size_t)T * sizeof(uint32_t), s));
             if (Q > 0) {
                 KOMB_HIP(ctx, hipMemsetAsync(d_dead, 0, (size_t)Q * sizeof(uint32_t), s));
-                k_nuc_clq<true><<<nuc_grid(T), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, nullptr, d_qcnt, d_clq, key0, d_ctl, n_short);
+                k_nuc_clq<true><<<tiles_of(T), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, nullptr, d_qcnt, d_clq, key0, d_ctl, n_short);
             }
             KOMB_TRY(prim_exclusive_sum_u32(ctx, key0, d_inc_ptr, T + 1));
-            if (Q > 0) k_nuc_inc<<<nuc_grid(Q), kBlock, 0, s>>>(d_clq, uQ, d_inc_ptr, d_cur, d_inc);
+            if (Q > 0) k_nuc_inc<<<tiles_of(Q), kBlock, 0, s>>>(d_clq, uQ, d_inc_ptr, d_cur, d_inc);
             KOMB_HIP(ctx, hipGetLastError());
             (void)hipEventRecord(e_q1, s);
             timed_clq = true;
@@ -492,7 +491,7 @@ int nucleus_run(komb_ctx *ctx)
                 }
             }
             (void)hipEventRecord(e_p1, s);
-            k_nuc_out<<<nuc_grid(T), kBlock, 0, s>>>(uT, o, res.theta, res.edge, res.vertex);
+            k_nuc_out<<<tiles_of(T), kBlock, 0, s>>>(uT, o, res.theta, res.edge, res.vertex);
             KOMB_HIP(ctx, hipGetLastError());
         }
     }

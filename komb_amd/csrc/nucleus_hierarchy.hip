@@ -276,7 +276,7 @@ int nh_labels_dev(komb_ctx *ctx, int32_t k, int32_t *d_label, int32_t *d_size)
     const int64_t T = ctx->nuc.n_tri;
     const int32_t *nodes = ctx->nh.nodes;
     const size_t c = (size_t)ctx->nh.cap;
-    k_nh_labels<<<forest_grid(T), kBlock, 0, ctx->stream>>>((uint32_t)T, k, ctx->nh.tnode, (uint32_t)ctx->nh.n_nodes, nodes, nodes + c, nodes + 2 * c,
+    k_nh_labels<<<tiles_of(T), kBlock, 0, ctx->stream>>>((uint32_t)T, k, ctx->nh.tnode, (uint32_t)ctx->nh.n_nodes, nodes, nodes + c, nodes + 2 * c,
                                                         nodes + 3 * c, d_label, d_size);
     KOMB_HIP(ctx, hipGetLastError());
     return KOMB_OK;
@@ -337,10 +337,10 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         const uint32_t *d_nm = d_pos + T;                        // the number of members, on the device
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(NhCtl), s));
         KOMB_TRY(oriented_rows(ctx, bufs, eu, m, nullptr, &d_rs, &d_re));
-        k_nh_tri<<<forest_grid(T + 1), kBlock, 0, s>>>(uT, (uint32_t)nv, o, ev, d_rs, d_re, theta, d_flag, parent, cnt, cur, claimk, d_ctl);
-        k_nh_tri_ptr<<<forest_grid(m + 1), kBlock, 0, s>>>(um, uT, o.j, tri_ptr);
+        k_nh_tri<<<tiles_of(T + 1), kBlock, 0, s>>>(uT, (uint32_t)nv, o, ev, d_rs, d_re, theta, d_flag, parent, cnt, cur, claimk, d_ctl);
+        k_nh_tri_ptr<<<tiles_of(m + 1), kBlock, 0, s>>>(um, uT, o.j, tri_ptr);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, T + 1));
-        k_nh_clq<<<forest_grid(T), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, theta, d_nm, d_ctl, n_short, st);
+        k_nh_clq<<<tiles_of(T), kBlock, 0, s>>>(ev, d_rs, d_re, o, uT, tri_ptr, theta, d_nm, d_ctl, n_short, st);
         KOMB_HIP(ctx, hipGetLastError());
         NhCtl h;
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NhCtl)));       // the cursor, read once: it ends on the stored count or the run fails
@@ -368,7 +368,7 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         KOMB_HIP(ctx, bufs.alloc(&d_tab, tab_words));
         uint32_t *d_moff = d_tab, *d_roff = d_tab + levels + 1;
         KOMB_HIP(ctx, hipMemsetAsync(d_tab, 0, tab_words * sizeof(uint32_t), s));
-        k_nh_compact<<<forest_grid(T), kBlock, 0, s>>>(uT, theta, levels, d_pos, nm, mkeys, mvals);
+        k_nh_compact<<<tiles_of(T), kBlock, 0, s>>>(uT, theta, levels, d_pos, nm, mkeys, mvals);
         uint32_t *rsorted = nullptr, *order = nullptr, *msorted = nullptr, *mord = nullptr;
         KOMB_TRY(prim_sort_pairs_u32_u32(ctx, st.keys, rkeys2, st.idx, ridx2, Q, bits, &rsorted, &order));
         forest_offsets(ctx, uQ, rsorted, levels, d_roff);
@@ -396,7 +396,7 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
             const uint32_t sh_b = moff[k], sh_n = moff[k + 1] - moff[k];
             const uint32_t r_b = roff[k], r_n = roff[k + 1] - roff[k];
             if (!sh_n) continue;                                                    // (a record of weight k has a triangle of theta k)
-            if (r_n) k_nh_link<<<forest_grid(r_n), kBlock, 0, s>>>(st.recs, order, r_b, r_n, uQ, uT, parent, d_ctl, log, nm);
+            if (r_n) k_nh_link<<<tiles_of(r_n), kBlock, 0, s>>>(st.recs, order, r_b, r_n, uQ, uT, parent, d_ctl, log, nm);
             forest_level(ctx, f, k, li, false, mord, sh_b, sh_n, 3ull * r_n < nm ? 3ull * r_n : nm);      // at most this many hooks at this level
             ++li;
         }
@@ -414,7 +414,7 @@ int nucleus_hierarchy_run(komb_ctx *ctx)
         ForestNodes out{res.nodes, res.nodes + cap_nodes, res.nodes + 2 * cap_nodes,
                         (uint32_t *)res.nodes.get() + 3 * cap_nodes, (uint32_t *)res.nodes.get() + 4 * cap_nodes};
         KOMB_TRY(forest_tail(ctx, bufs, f, n, bits, out, rank, nullptr, mvals, mvals2));   // (the members' sort has served: n <= nm)
-        k_nh_tri_out<<<forest_grid(T), kBlock, 0, s>>>(uT, theta, mnode, rank, n, res.tnode);
+        k_nh_tri_out<<<tiles_of(T), kBlock, 0, s>>>(uT, theta, mnode, rank, n, res.tnode);
         res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, d2h(ctx, &h, d_ctl, sizeof(NhCtl)));
@@ -467,7 +467,7 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
         KOMB_HIP(ctx, bufs.alloc(&d_flag, (size_t)T + 1));
         KOMB_HIP(ctx, bufs.alloc(&d_pos, (size_t)T + 1));
         KOMB_TRY(nh_labels_dev(ctx, k, d_label, d_size));
-        k_nh_rep_flag<<<forest_grid(T + 1), kBlock, 0, s>>>((uint32_t)T, d_label, d_flag);
+        k_nh_rep_flag<<<tiles_of(T + 1), kBlock, 0, s>>>((uint32_t)T, d_label, d_flag);
         KOMB_TRY(prim_exclusive_sum_u32(ctx, d_flag, d_pos, T + 1));
         KOMB_HIP(ctx, hipGetLastError());
         uint32_t total = 0;
@@ -488,7 +488,7 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
         KOMB_HIP(ctx, bufs.alloc(&vuniq, n_keys));
         KOMB_HIP(ctx, bufs.alloc(&euniq, n_keys));
         KOMB_HIP(ctx, bufs.alloc(&d_out, 4 * (size_t)n_nuc));
-        k_nh_keys<<<forest_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, ctx->nuc.a, ctx->nuc.b, ctx->nuc.c, ctx->d_t_eu, ctx->d_t_ev,
+        k_nh_keys<<<tiles_of(T), kBlock, 0, s>>>((uint32_t)T, d_label, ctx->nuc.a, ctx->nuc.b, ctx->nuc.c, ctx->d_t_eu, ctx->d_t_ev,
                                                 (uint32_t)m, vkeys, ekeys);
         KOMB_HIP(ctx, hipGetLastError());
         int64_t n_v = 0, n_e = 0;
@@ -500,7 +500,7 @@ int nucleus_hierarchy_nuclei(komb_ctx *ctx, int32_t k, int64_t cap, int64_t *n_n
             KOMB_FAIL(ctx, KOMB_ERR_DEVICE, "komb_nucleus_hierarchy_nuclei: inconsistent key counts (%lld vertices, %lld edges of %zu keys)",
                       (long long)n_v, (long long)n_e, n_keys);
         int32_t *o_rep = d_out, *o_tri = d_out + n_nuc, *o_edge = d_out + 2 * n_nuc, *o_vert = d_out + 3 * n_nuc;
-        k_nh_nuclei_out<<<forest_grid(T), kBlock, 0, s>>>((uint32_t)T, d_label, d_size, d_pos, (uint32_t)n_nuc, vuniq, (uint32_t)n_v, euniq, (uint32_t)n_e,
+        k_nh_nuclei_out<<<tiles_of(T), kBlock, 0, s>>>((uint32_t)T, d_label, d_size, d_pos, (uint32_t)n_nuc, vuniq, (uint32_t)n_v, euniq, (uint32_t)n_e,
                                                       o_rep, o_tri, o_edge, o_vert);
         KOMB_HIP(ctx, hipGetLastError());
         KOMB_HIP(ctx, hipStreamSynchronize(s));

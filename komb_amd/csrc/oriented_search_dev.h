@@ -1,17 +1,12 @@
 // oriented_search_dev.h -- the one triangle and 4-clique search over the oriented canonical edge list: row a = the positions
 // [rs[a], re[a]) with eu == a, their ev ascending.  Its users: communities.hip and community_hierarchy.hip (over their member
 // lists), nucleus.hip, nucleus_hierarchy.hip, graphlets.hip and, through clique_root_dev.h, the three clique walks.  Here are
-// the row bounds, the two sides of an edge, the three tails of a triangle, the one bisection, the triangle id, and the
-// lane / wave tiers.  What a hit does is each user's own.  DESIGN.md sections 4.6c, 4.6e, 4.6h.
-//
-// THE WAVE RULE, for everything below that ballots or shuffles (wave_turns, from_lane, wave_walk_all) and for every functor
-// that does: all 64 lanes of the wave get there together.  So it is called from straight-line kernel code or from loops whose
-// bounds are uniform over the wave, never under a condition that differs between lanes; a lane with nothing to do comes
-// along with mid = false, n = 0 or in = false.  wave_walk is the one exception: its lanes leave when their entries run out,
-// so its functor must neither ballot nor shuffle.
+// the row bounds, the two sides of an edge, the three tails of a triangle, the one bisection and the triangle id.  What a hit
+// does is each user's own.  DESIGN.md sections 4.6c, 4.6e, 4.6h.  The lane / wave tiers (wave_turns, from_lane, wave_walk,
+// wave_walk_all) and THE WAVE RULE they come with are wave_dev.h's; here are from_lane's overloads for the two units.
 #pragma once
 
-#include "common.h"
+#include "wave_dev.h"
 
 namespace komb {
 
@@ -139,22 +134,7 @@ __device__ __forceinline__ bool nuc_clq_entry(const int32_t *__restrict__ ev, co
     return nuc_clq_entry(ev, s, x, &p1, &p2);
 }
 
-// ---- the tiers.  One lane per unit (an edge and its sides, a triangle and its tails).  A unit whose walked part is short stays
-// with its lane; the longer ones (mid) are walked by the whole wave, one after the other: unit(src) is called once for every
-// lane src with mid set, in ascending lane order, and fetches that lane's unit with from_lane.
-template <class F>
-__device__ __forceinline__ void wave_turns(bool mid, F unit)
-{
-    unsigned long long todo = __ballot(mid);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        unit(src);
-    }
-}
-
-__device__ __forceinline__ uint32_t from_lane(uint32_t v, int src) { return (uint32_t)__shfl((int32_t)v, src); }
-
+// ---- a lane's unit handed to the whole wave (wave_turns)
 __device__ __forceinline__ EdgeSides from_lane(const EdgeSides &s, int src)
 {
     EdgeSides r;
@@ -167,23 +147,6 @@ __device__ __forceinline__ NucTails from_lane(const NucTails &s, int src)
 {
     return NucTails{from_lane(s.it, src), from_lane(s.n, src), from_lane(s.lo1, src), from_lane(s.hi1, src), from_lane(s.lo2, src),
                     from_lane(s.hi2, src)};
-}
-
-// the wave over the entries [it, it + n) of one unit, free form: entry(x) by the lane that x falls to, its hits its own affair
-template <class F>
-__device__ __forceinline__ void wave_walk(uint32_t it, uint32_t n, int lane, F entry)
-{
-    for (uint32_t x = it + (uint32_t)lane; x < it + n; x += kWave) entry(x);
-}
-
-// ... uniform form, for an entry that ballots: every lane calls entry(x, in) on every trip, in = x is an entry of the unit
-template <class F>
-__device__ __forceinline__ void wave_walk_all(uint32_t it, uint32_t n, int lane, F entry)
-{
-    for (uint32_t x0 = it; x0 < it + n; x0 += kWave) {
-        const uint32_t x = x0 + (uint32_t)lane;
-        entry(x, x < it + n);
-    }
 }
 
 } // namespace komb

@@ -62,6 +62,20 @@ int prim_exclusive_sum_u32(komb_ctx *ctx, const uint32_t *in, uint32_t *out, int
     return KOMB_OK;                              // asynchronous on the context's stream (the scratch goes back to the pool, which the same stream uses)
 }
 
+// the members of a list by a threshold: flag[i] = val[i] >= k (flag[m] = 0: the scan's last entry is the number of members)
+static __global__ void k_flag_ge(const int32_t *__restrict__ val, uint32_t m, int32_t k, uint32_t *__restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i > m) return;
+    flag[i] = i < m && val[i] >= k ? 1u : 0u;
+}
+
+int prim_flag_ge_scan(komb_ctx *ctx, const int32_t *val, int64_t m, int32_t k, uint32_t *flag, uint32_t *pos)
+{
+    k_flag_ge<<<tiles_of(m + 1), kBlock, 0, ctx->stream>>>(val, (uint32_t)m, k, flag);
+    return prim_exclusive_sum_u32(ctx, flag, pos, m + 1);
+}
+
 // exclusive sum of 32-bit counts into 64-bit offsets (totals beyond 2^32)
 struct WidenU32 { __host__ __device__ unsigned long long operator()(uint32_t x) const { return (unsigned long long)x; } };
 int prim_exclusive_sum_u32_u64(komb_ctx *ctx, const uint32_t *in, unsigned long long *out, int64_t n)

@@ -16,7 +16,7 @@
 //   k_sc_flatten   x 2: a compressing pass, then a store-free labelling pass (components.hip's header says why)
 //   k_sc_border    similar edges between a core and a non-core: atomicMin of the core's label onto the non-core
 //   k_sc_hub       every edge: an unlabelled end takes the min and the max of the other end's label
-//   k_sc_count, k_sc_finish   sizes, roles, the counts of the control block
+//   k_class_count (unionfind_dev.h), k_sc_finish   sizes, roles, the counts of the control block
 //
 // Canonical order puts the edges with the same eu next to each other, so what an edge pass adds to its eu end is a
 // segmented reduction inside the wave: a ballot of the run heads, a ballot of the contributing lanes and one add per run
@@ -26,7 +26,6 @@
 // k_sc_hub reads label[] and writes lo[] / hi[] only; k_sc_finish writes label[v] from v's own lane.  An atomicMin /
 // atomicMax is skipped when a relaxed read of its word shows it cannot change it: such a word only ever moves one way, so
 // a stale read errs on the side of issuing the atomic.
-#include "common.h"
 #include "unionfind_dev.h"
 
 namespace komb {
@@ -36,15 +35,12 @@ namespace {
 typedef unsigned __int128 u128;
 
 constexpr int32_t kScNone = 0x7FFFFFFF;     // label word of a vertex without a label (until k_sc_finish writes -1); empty lo[]
-constexpr int kScTailGrid = 2048;           // k_sc_count / k_sc_finish: workgroups, each over several tiles
 
 struct ScCtl {                              // 64 bytes, zeroed before every run, read by the host once after it
     uint32_t n_similar, n_cores, n_borders, n_hubs, n_outliers, n_clusters, largest;
     uint32_t pad[9];
 };
 static_assert(sizeof(ScCtl) == 64, "ScCtl layout");
-
-inline int sc_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
 __global__ void k_sc_init(uint32_t nv, const uint32_t *__restrict__ rowptr, uint32_t *__restrict__ deg, uint32_t *__restrict__ simdeg,
                           int32_t *__restrict__ parent, int32_t *__restrict__ lo, int32_t *__restrict__ hi, uint32_t *__restrict__ cnt)
@@ -140,8 +136,7 @@ __global__ void k_sc_flatten(uint32_t nv, const uint32_t *__restrict__ simdeg, u
     const bool core = sc_core(simdeg, (int32_t)v, mu);
     if (kFinal) { label[v] = core ? comp_find_ro(parent, (int32_t)v) : kScNone; return; }
     if (!core) return;
-    const int32_t r = comp_find(parent, (int32_t)v);
-    if (r != (int32_t)v) pstore(parent + v, r);
+    comp_flatten<false>(parent, v);
 }
 
 __device__ __forceinline__ void sc_min(int32_t *p, int32_t x) { if (x < pload(p)) atomicMin(p, x); }
@@ -174,37 +169,6 @@ __global__ void k_sc_hub(const int32_t *__restrict__ eu, const int32_t *__restri
     sc_max(hi + x, l);
 }
 
-// cnt[label] += the vertices that carry it.  Lanes of a wave that share a label add once; what a workgroup adds to the
-// label its first tile starts with it sums in LDS first (components.hip: k_comp_count).
-__global__ void k_sc_count(uint32_t nv, const int32_t *__restrict__ label, uint32_t *cnt)
-{
-    __shared__ int32_t s_first;
-    __shared__ uint32_t s_sum;
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t v0 = blockIdx.x * kBlock;
-    if (threadIdx.x == 0) { s_first = v0 < nv ? label[v0] : kScNone; s_sum = 0u; }
-    __syncthreads();
-    const int32_t first = s_first;
-    for (uint32_t base = v0; base < nv; base += gridDim.x * kBlock) {      // (uniform per workgroup: the ballots see whole waves)
-        const uint32_t v = base + threadIdx.x;
-        const int32_t lab = v < nv ? label[v] : kScNone;
-        const bool act = lab != kScNone;
-        unsigned long long m = __ballot(act);
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            const int32_t lead = __shfl(lab, src);
-            const unsigned long long same = __ballot(act && lab == lead);
-            if (lane == src) {
-                if (lead == first) atomicAdd(&s_sum, (uint32_t)__popcll(same));
-                else atomicAdd(cnt + lead, (uint32_t)__popcll(same));
-            }
-            m &= ~same;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(cnt + first, s_sum);
-}
-
 // label (-1 without one), size, role and sim_deg of every vertex; the counts of the control block summed up per workgroup
 __global__ void k_sc_finish(uint32_t nv, const uint32_t *__restrict__ simdeg, uint32_t mu, const int32_t *__restrict__ lo,
                             const int32_t *__restrict__ hi, const uint32_t *__restrict__ cnt, int32_t *label, int32_t *__restrict__ size,
@@ -233,11 +197,8 @@ __global__ void k_sc_finish(uint32_t nv, const uint32_t *__restrict__ simdeg, ui
         role[v] = r;
         for (int j = 0; j < 4; ++j) n[j] += r == j ? 1u : 0u;
     }
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        for (int j = 0; j < 5; ++j) n[j] += (uint32_t)__shfl_xor((int32_t)n[j], o);
-        const uint32_t other = (uint32_t)__shfl_xor((int32_t)mx, o);
-        mx = other > mx ? other : mx;
-    }
+    for (int j = 0; j < 5; ++j) n[j] = wave_sum(n[j]);
+    mx = wave_max(mx);
     if (lane == 0) {
         for (int j = 0; j < 5; ++j) if (n[j]) atomicAdd(&s_n[j], n[j]);
         if (mx) atomicMax(&s_max, mx);
@@ -300,7 +261,7 @@ int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu)
         uint32_t *simdeg = (uint32_t *)res.simdeg.get();
         const uint32_t un = (uint32_t)nv, um = (uint32_t)m, umu = (uint32_t)mu;
         const uint64_t num2 = (uint64_t)eps_num * (uint64_t)eps_num, den2 = (uint64_t)eps_den * (uint64_t)eps_den;
-        const int gv = sc_grid(nv), ge = sc_grid(m);
+        const int gv = tiles_of(nv), ge = tiles_of(m);
         ctx->timer.start(s);
         KOMB_HIP(ctx, hipMemsetAsync(d_ctl, 0, sizeof(ScCtl), s));
         k_sc_init<<<gv, kBlock, 0, s>>>(un, whole ? ctx->d_o_rowptr : nullptr, d_deg, simdeg, d_parent, d_lo, d_hi, d_cnt);
@@ -317,9 +278,8 @@ int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu)
             k_sc_border<<<ge, kBlock, 0, s>>>(eu, ev, res.similar, um, simdeg, umu, res.label);
             k_sc_hub<<<ge, kBlock, 0, s>>>(eu, ev, um, res.label, d_lo, d_hi);
         }
-        const int tail_grid = gv < kScTailGrid ? gv : kScTailGrid;
-        k_sc_count<<<tail_grid, kBlock, 0, s>>>(un, res.label, d_cnt);
-        k_sc_finish<<<tail_grid, kBlock, 0, s>>>(un, simdeg, umu, d_lo, d_hi, d_cnt, res.label, res.size, res.role, d_ctl);
+        class_count(ctx, nv, nullptr, res.label, d_cnt);
+        k_sc_finish<<<class_tail_grid(nv), kBlock, 0, s>>>(un, simdeg, umu, d_lo, d_hi, d_cnt, res.label, res.size, res.role, d_ctl);
         res.ms = ctx->timer.stop(s);
         KOMB_HIP(ctx, hipGetLastError());
         ScCtl h;
@@ -348,7 +308,7 @@ int structural_fetch_edges(komb_ctx *ctx, int32_t *similar)
     DevBufs bufs(ctx);
     int32_t *d_out = nullptr;
     KOMB_HIP(ctx, bufs.alloc(&d_out, (size_t)m));
-    k_sc_widen<<<sc_grid(m), kBlock, 0, ctx->stream>>>(ctx->sc.similar, (uint32_t)m, d_out);
+    k_sc_widen<<<tiles_of(m), kBlock, 0, ctx->stream>>>(ctx->sc.similar, (uint32_t)m, d_out);
     KOMB_HIP(ctx, hipGetLastError());
     KOMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     KOMB_HIP(ctx, staged_copy(ctx, similar, d_out, (size_t)m * sizeof(int32_t), false));

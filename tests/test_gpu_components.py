@@ -117,7 +117,33 @@ def _two_k40(bridge_vertex):
     return 2 * n + (1 if bridge_vertex else 0), np.concatenate([iu, iu + n, np.asarray(link)])
 
 
+def _count_tiles():
+    """577 vertices, ids as given: three tiles of 256 for the counting kernel.  Tile 0 starts with a vertex without a label
+    (0 is isolated), has two waves of 64 different labels each (the pairs 64+i -- 128+i) and one alternating between two
+    labels that are not the tile's first (192.., step 2).  Tile 1 alternates between its first label, 256, and label 1, which
+    tile 0 owns (the even and the odd chain of 256..511; 1 -- 257 joins the odd one to the path 1..63).  Tile 2 is one
+    label, 512, and its last wave has one active lane (576)."""
+    r = np.arange
+    path = lambda a, b: np.stack([r(a, b), r(a + 1, b + 1)], 1)          # a - a+1 - ... - b
+    step2 = lambda a, b: np.stack([r(a, b), r(a + 2, b + 2)], 1)         # (i, i + 2) for a <= i < b
+    return 577, np.concatenate([path(1, 63), np.stack([64 + r(64), 128 + r(64)], 1), step2(192, 254), step2(256, 510),
+                                [[1, 257]], path(512, 576)])
+
+
 def test_edge_cases(K):
+    # what the counting kernel meets in three tiles, both kinds
+    nv, uv = _count_tiles()
+    with K.KombAccel() as a:
+        a.from_edges(nv, uv)
+        rowptr, col = a.get_csr()
+        _, core = a.run_core()
+        want = R.core_components(rowptr, col, core, 1)
+        assert R.summary(want) == (576, 69, 191)
+        for sample in ("0", "1"):
+            a.set_option("COMP_SAMPLE", sample)
+            _expect(a, "core", 1, want, k_used=1)
+        eu, ev, tr = a.run_truss()
+        _expect(a, "truss", 2, R.truss_components(nv, eu, ev, tr, 2), k_used=2)
     with K.KombAccel() as a:
         # the empty graph
         a.from_edges(0, np.zeros((0, 2)))
