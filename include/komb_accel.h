@@ -120,7 +120,7 @@ int         komb_abi_version(void);
  * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
  * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), MAXIMAL_LDS,
  * MAXIMAL_PIVOT, MAXIMAL_LIST, MAXIMAL_DEBUG (komb_maximal_cliques_run, below), PERC_GROUP, PERC_DEBUG
- * (komb_clique_communities_run, below), BICONN_HEAVY (komb_biconnected_run, below), GRAPHLET_SHORT, GRAPHLET_LDS, GRAPHLET_DEBUG (komb_graphlets_run, below), and the
+ * (komb_clique_communities_run, below), BICONN_HEAVY (komb_biconnected_run, below), GRAPHLET_SHORT, GRAPHLET_LDS, GRAPHLET_DEBUG (komb_graphlets_run, below), BTW_GRID, BTW_DEBUG (komb_betweenness_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -918,6 +918,52 @@ int komb_graphlets_fetch_vertices(komb_ctx *ctx, uint64_t *orbit /*[15 * nv]*/);
 int komb_graphlets_fetch_edges(komb_ctx *ctx, uint64_t *cycles4, uint64_t *cliques4 /*[ne_sub] each, either may be NULL*/);
 int komb_graphlets_info(komb_ctx *ctx, uint64_t *total /*[9]*/, int32_t *flags, int32_t *max_degree,
                         int64_t *cycle_items, int64_t *n_triangles, int64_t *n_cliques4, double *ms);   /* any may be NULL */
+
+/* ---- betweenness centrality from chosen sources ------------------------ */
+/* Brandes' algorithm ("A faster algorithm for betweenness centrality", J. Math. Sociol. 2001) from a list of source vertices
+ * (all of them, or a sample: Brandes & Pich 2007) on the RESIDENT graph: ORIGINAL ids, the symmetric CSR with ascending rows
+ * that komb_graph_get_csr returns, every edge of length 1.  It needs no other result.  The values are IEEE-754 binary64, and
+ * the ORDER OF EVERY ROUNDING OPERATION IS PART OF THE DEFINITION, so a result is a function of the graph and the source list
+ * alone and compares bit for bit with any implementation that follows this text:
+ * sources[n_sources] are vertex ids; sources == NULL means every vertex 0 .. nv-1 in ascending order (n_sources is then
+ * ignored).  Duplicates are allowed and count as often as they are given.  An id outside [0, nv) or n_sources < 0:
+ * KOMB_ERR_ARG.  n_sources == 0 is a valid run with zeros everywhere.
+ * Per source s, in exactly these operations, none of them fused (no fused multiply-add):
+ *   dist_s = the BFS distance from s (unreached: none); sigma_s[s] = 1.0.
+ *   A vertex w at distance L >= 1:  acc = 0.0; for v in the row of w, in ascending id, with dist_s[v] == L-1:
+ *     acc = acc + sigma_s[v];  then sigma_s[w] = acc.
+ *   A reached vertex v at distance L, levels descending:  acc = 0.0; for w in the row of v, in ascending id, with
+ *     dist_s[w] == L+1:  c = (1.0 + delta_s[w]) / sigma_s[w];  p = sigma_s[v] * c;  acc = acc + p;  then delta_s[v] = acc.
+ *   An unreached vertex has delta_s = 0.0.
+ * bc[v]:  acc = 0.0; for i = 0 .. n_sources-1 in the order given: if sources[i] != v: acc = acc + delta_{sources[i]}[v].
+ * The value is RAW: neither halved nor normalised.  With every vertex as a source it is exactly twice igraph's / networkx's
+ * undirected unnormalised betweenness (every pair counts from both ends); from a sample it is the sum over the sampled sources.
+ * Per source, in the order given (komb_betweenness_fetch_sources; any output may be NULL): source[i] = the id; n_reached[i] =
+ * the vertices reached, s itself included; sum_dist[i] = the exact sum of their distances; ecc[i] = the largest distance --
+ * the integers of closeness, harmonic reach and an eccentricity / diameter lower bound, at no extra cost.
+ * komb_betweenness_info (any output may be NULL): n_sources; flags has KOMB_BETWEENNESS_ROUNDED when some sigma reached 2^53
+ * or more (the result is still the defined one, but sigma no longer counts the shortest paths exactly); depth_max = the largest
+ * ecc; n_batches = the batches of up to 64 consecutive sources the run was made in, ceil(n_sources / 64); n_level_steps = the
+ * level sweeps of the run, the sum over the batches of (E + 1) + max(E - 1, 0) where E is the batch's largest ecc -- the cost
+ * of a run is a few kernel launches per step, so it grows with the depth; ms = the device time of the run on the context's
+ * HIP-event timer.
+ * A sigma that reaches +inf: KOMB_ERR_LIMIT, nothing is installed.  A pool failure: KOMB_ERR_NOMEM.  No context or no graph
+ * loaded: KOMB_ERR_ARG.  Fetch or info before a run on this graph: KOMB_ERR_STATE.  A failing call writes nothing to its outputs.
+ * The result lives in arrays of its own and is installed only when a run has succeeded: a refused or failed run (KOMB_ERR_ARG,
+ * KOMB_ERR_NOMEM, KOMB_ERR_LIMIT, KOMB_ERR_DEVICE) leaves the PREVIOUS betweenness result readable.  It belongs to the graph: a
+ * graph load drops it.  No k-core, k-truss or other analysis call changes or drops it, and a run changes none of their results,
+ * no komb_stats field and not the resident k-truss preparation.
+ * Memory: dist, sigma and delta of one batch are [nv][64] arrays from the context's pool, about 1.3 KB per vertex, given back
+ * when the run ends.
+ * Options (none changes a result): BTW_GRID=<n>: at most n workgroups per level sweep (default and at most 2048; tests lower
+ * it to make every wave take several vertices); BTW_DEBUG: one stderr line with the per-batch level counts and times and the
+ * share of row entries the frontier masks skipped. */
+#define KOMB_BETWEENNESS_ROUNDED 1
+int komb_betweenness_run(komb_ctx *ctx, int64_t n_sources, const int32_t *sources /* NULL: all */);
+int komb_betweenness_fetch(komb_ctx *ctx, double *bc /*[nv], may be NULL*/);
+int komb_betweenness_fetch_sources(komb_ctx *ctx, int32_t *source, int64_t *n_reached, int64_t *sum_dist, int32_t *ecc /*[n_sources] each, any may be NULL*/);
+int komb_betweenness_info(komb_ctx *ctx, int64_t *n_sources, int32_t *flags, int32_t *depth_max, int64_t *n_batches,
+                          int64_t *n_level_steps, double *ms);   /* any may be NULL */
 
 /* ---- synthetic workload (host code, no device) ------------------------- */
 /* Power-law "hybrid unitig graph" generator of SURVEY.md section 8(d): a union

@@ -44,7 +44,7 @@ OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
                 "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "CENSUS_LDS", "CENSUS_PIVOT",
                 "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "PERC_GROUP", "PERC_DEBUG", "BICONN_HEAVY",
-                "GRAPHLET_LDS", "GRAPHLET_SHORT", "GRAPHLET_DEBUG", "POISON")
+                "GRAPHLET_LDS", "GRAPHLET_SHORT", "GRAPHLET_DEBUG", "BTW_GRID", "BTW_DEBUG", "POISON")
 
 # (ALLOC_FAIL_AT / ALLOC_TRIM_AT are one-shot triggers counted from the moment they are set: they are NOT forwarded -- forwarding
 # would re-arm them before every call; a test sets them with set_option)
@@ -578,6 +578,46 @@ class KombAccel:
         self.graphlets_run()
         cycles4, cliques4 = self.graphlets_fetch_edges()
         return self.graphlets_fetch_vertices(), cycles4, cliques4, self.graphlets_info()
+
+    # ---- betweenness centrality from chosen sources on the resident graph (include/komb_accel.h)
+    def betweenness_run(self, sources=None):
+        """sources: vertex ids in the order they count (duplicates allowed); None = every vertex in ascending order."""
+        self._sync_env_options()
+        if sources is None:
+            self._check(self._lib.komb_betweenness_run(self._ctx, 0, None))
+            return
+        src = as_c(np.asarray(sources).reshape(-1), np.int32)
+        self._check(self._lib.komb_betweenness_run(self._ctx, len(src), ptr(src) if len(src) else ptr(np.zeros(1, np.int32))))
+
+    def betweenness_fetch(self):
+        """bc float64[nv]: the raw betweenness, neither halved nor normalised."""
+        bc = _out_f64(max(self.nv, 0))
+        self._check(self._lib.komb_betweenness_fetch(self._ctx, ptr(bc)))
+        return bc
+
+    def betweenness_fetch_sources(self):
+        """{"source", "n_reached", "sum_dist", "ecc"}: one entry per source of the last run, in the order given."""
+        n = self.betweenness_info()["n_sources"]
+        source, ecc = _out_i32(n), _out_i32(n)
+        reached, sumd = np.full(n, SENTINEL_I32, dtype=np.int64), np.full(n, SENTINEL_I32, dtype=np.int64)
+        self._check(self._lib.komb_betweenness_fetch_sources(self._ctx, ptr(source), ptr(reached), ptr(sumd), ptr(ecc)))
+        return {"source": source, "n_reached": reached, "sum_dist": sumd, "ecc": ecc}
+
+    def betweenness_info(self):
+        """{"n_sources", "flags", "depth_max", "n_batches", "n_level_steps", "ms"} of the last run."""
+        n, nb, steps = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        flags, depth, ms = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        self._check(self._lib.komb_betweenness_info(self._ctx, ctypes.byref(n), ctypes.byref(flags), ctypes.byref(depth), ctypes.byref(nb),
+                                                    ctypes.byref(steps), ctypes.byref(ms)))
+        return {"n_sources": n.value, "flags": flags.value, "depth_max": depth.value, "n_batches": nb.value,
+                "n_level_steps": steps.value, "ms": ms.value}
+
+    def run_betweenness(self, sources=None, halve=False):
+        """(bc, per-source dict, info).  halve: bc / 2, which with every vertex as a source is igraph's / networkx's undirected
+        unnormalised betweenness (exact: a division by two rounds nothing)."""
+        self.betweenness_run(sources)
+        bc = self.betweenness_fetch()
+        return (bc / 2 if halve else bc), self.betweenness_fetch_sources(), self.betweenness_info()
 
     # ---- (3,4)-nucleus decomposition: triangles of the last k-truss result peeled by their 4-cliques (include/komb_accel.h)
     NUCLEUS_FIELDS = ("a", "b", "c", "key0", "theta")

@@ -91,6 +91,7 @@ static_assert(KOMB_COMM_K_MAX == KOMB_BICONN_K_MAX, "resolve_truss_k serves both
 #define NO_DENS "komb_densest_subgraph_run has not completed on this graph"
 #define NO_SC "no structural clustering of the current k-truss result"
 #define NO_GL "no graphlet census of the current k-truss result"
+#define NO_BTW "komb_betweenness_run has not completed on this graph"
 #define NO_NUC "no nucleus decomposition of the current k-truss result"
 #define NO_MC "no maximum-clique search of the current k-truss result"
 #define NO_CC "no clique census of the current k-truss result"
@@ -569,6 +570,44 @@ int komb_graphlets_info(komb_ctx *ctx, uint64_t *total, int32_t *flags, int32_t 
     if (cycle_items) *cycle_items = r.cycle_items;
     if (n_triangles) *n_triangles = r.n_triangles;
     if (n_cliques4) *n_cliques4 = r.n_cliques4;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
+int komb_betweenness_run(komb_ctx *ctx, int64_t n_sources, const int32_t *sources)
+{
+    KOMB_HIER_ENTER(ctx, "komb_betweenness_run");
+    return betweenness_run(ctx, n_sources, sources);
+}
+
+int komb_betweenness_fetch(komb_ctx *ctx, double *bc)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_betweenness_fetch", ctx->btw.done, NO_BTW);
+    return fetch(ctx, bc, ctx->btw.bc, (size_t)ctx->nv);
+}
+
+int komb_betweenness_fetch_sources(komb_ctx *ctx, int32_t *source, int64_t *n_reached, int64_t *sum_dist, int32_t *ecc)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_betweenness_fetch_sources", ctx->btw.done, NO_BTW);
+    const komb_ctx::Betweenness &r = ctx->btw;
+    const size_t n = r.source.size();
+    if (source && n) memcpy(source, r.source.data(), n * sizeof(int32_t));
+    if (n_reached && n) memcpy(n_reached, r.n_reached.data(), n * sizeof(int64_t));
+    if (sum_dist && n) memcpy(sum_dist, r.sum_dist.data(), n * sizeof(int64_t));
+    if (ecc && n) memcpy(ecc, r.ecc.data(), n * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_betweenness_info(komb_ctx *ctx, int64_t *n_sources, int32_t *flags, int32_t *depth_max, int64_t *n_batches,
+                          int64_t *n_level_steps, double *ms)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_betweenness_info", ctx->btw.done, NO_BTW);
+    const komb_ctx::Betweenness &r = ctx->btw;
+    if (n_sources) *n_sources = (int64_t)r.source.size();
+    if (flags) *flags = r.flags;
+    if (depth_max) *depth_max = r.depth_max;
+    if (n_batches) *n_batches = r.n_batches;
+    if (n_level_steps) *n_level_steps = r.n_level_steps;
     if (ms) *ms = r.ms;
     return KOMB_OK;
 }

@@ -454,6 +454,20 @@ struct komb_ctx {
         bool done = false;
     } gl;
 
+    // ---- betweenness centrality from chosen sources (betweenness.hip): a snapshot in arrays of its own, dropped with the graph
+    // (graph_free) and by nothing else
+    struct Betweenness {
+        DevArr<double> bc;                   // [nv] raw betweenness, ORIGINAL ids (pool block)
+        std::vector<int32_t> source;         // [n_sources] the sources of the last run, in the order given
+        std::vector<int64_t> n_reached, sum_dist;   // [n_sources] vertices reached (the source included) | sum of their distances
+        std::vector<int32_t> ecc;            // [n_sources] the largest distance
+        int32_t flags = 0, depth_max = 0;    // KOMB_BETWEENNESS_ROUNDED | the largest ecc
+        int64_t n_batches = 0, n_level_steps = 0;
+        int64_t visits = 0, needed = 0;      // row entries the sweeps looked at | those some lane needed (option BTW_DEBUG prints them)
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
+    } btw;
+
     // ---- (3,4)-nucleus decomposition (nucleus.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
     struct Nucleus {
@@ -760,6 +774,7 @@ int community_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t
 int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu);   // structural.hip: the parameters and the k-truss result it needs checked by the caller
 int structural_fetch_edges(komb_ctx *ctx, int32_t *similar);  // structural.hip: similar[] of the last run as 0 | 1 words (host output)
 int graphlets_run(komb_ctx *ctx);                             // graphlets.hip: the k-truss result it needs checked by the caller
+int betweenness_run(komb_ctx *ctx, int64_t n_sources, const int32_t *sources);   // betweenness.hip: sources null = every vertex; checks its arguments itself
 int nucleus_run(komb_ctx *ctx);                               // nucleus.hip: the k-truss result it needs checked by the caller
 int nucleus_hierarchy_run(komb_ctx *ctx);                     // nucleus_hierarchy.hip: the nucleus result it needs checked by the caller
 int nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null

@@ -85,6 +85,14 @@
 //                       graphlet_edges.tsv: #U, V, Triangles, Cycles4, Cliques4 -- one row per edge in canonical order, the
 //                       unitigs by Name.  Any other value is a usage error.  VIDs depend on -t, so only the tables by Name
 //                       compare between runs.  Nothing else changes.
+//   KOMB_BETWEENNESS=all|<n>[:<seed>]  also write the betweenness centrality (komb_betweenness_run, Brandes' algorithm) of the
+//                       whole graph from every unitig, or from a sample: the n unitigs with the smallest
+//                       splitmix64(seed ^ VID), ties by VID, passed in ascending VID (seed defaults to 1; n >= the number of
+//                       unitigs is all).  betweenness.tsv: #VID, Name, Betweenness -- one row per unitig in VID order, the raw
+//                       value (neither halved nor normalised; from every unitig it is twice igraph's) printed with %.17g, which
+//                       reads back to the same binary64.  betweenness_sources.tsv: #VID, Name, Reached, SumDist, Ecc -- one
+//                       row per source in the order passed: the unitigs it reaches (itself included), the sum of their
+//                       distances and the largest.  Any other value is a usage error.  Nothing else changes.
 //   KOMB_NUCLEUS=1      with KOMB_TRUSS=1: also write, after the truss stage, the (3,4)-nucleus decomposition of its result
 //                       (komb_nucleus_run: triangles peeled by the 4-cliques they lie in).  nucleus_triangles.tsv:
 //                       #Name_A, Name_B, Name_C, Cliques, Theta -- one row per triangle in triangle order (ascending VIDs),
@@ -789,6 +797,71 @@ void write_graphlets(komb_ctx *ctx, bool with_edges, const std::string &outdir, 
         buf.append(names.name[(size_t)ev[(size_t)i]]);
         const int len = snprintf(tmp, sizeof(tmp), "\t%d\t%llu\t%llu\n", (int)sup[(size_t)i], (unsigned long long)cyc[(size_t)i],
                                  (unsigned long long)clq[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
+// KOMB_BETWEENNESS: komb_betweenness_run on the resident graph from every vertex (n < 0 or n >= nv) or from the n vertices with
+// the smallest splitmix64(seed ^ vid), as two tables: one row per vertex in VID order, one row per source in the order passed
+uint64_t splitmix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+void write_betweenness(komb_ctx *ctx, int64_t n, uint64_t seed, const std::string &outdir, const Names &names, int64_t nv, int threads)
+{
+    std::vector<int32_t> src;
+    const bool all = n < 0 || n >= nv;
+    if (!all) {
+        std::vector<std::pair<uint64_t, int32_t>> key((size_t)nv);
+        for (int64_t v = 0; v < nv; ++v) key[(size_t)v] = {splitmix64(seed ^ (uint64_t)v), (int32_t)v};
+        std::partial_sort(key.begin(), key.begin() + n, key.end());
+        for (int64_t i = 0; i < n; ++i) src.push_back(key[(size_t)i].second);
+        std::sort(src.begin(), src.end());
+    }
+    int64_t n_src = 0;
+    std::vector<double> bc((size_t)nv);
+    std::vector<int32_t> source, ecc;
+    std::vector<int64_t> reached, sumd;
+    if (nv > 0) {
+        int32_t none = 0;
+        int rc = komb_betweenness_run(ctx, all ? 0 : n, all ? nullptr : (src.empty() ? &none : src.data()));
+        if (rc != KOMB_OK) die_accel(ctx, "komb_betweenness_run", rc);
+        rc = komb_betweenness_info(ctx, &n_src, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_betweenness_info", rc);
+        source.resize((size_t)n_src); ecc.resize((size_t)n_src); reached.resize((size_t)n_src); sumd.resize((size_t)n_src);
+        rc = komb_betweenness_fetch(ctx, bc.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_betweenness_fetch", rc);
+        rc = komb_betweenness_fetch_sources(ctx, source.data(), reached.data(), sumd.data(), ecc.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_betweenness_fetch_sources", rc);
+    }
+    std::string path = outdir + "/betweenness.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tBetweenness\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        char tmp[64];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%.17g\n", bc[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+    path = outdir + "/betweenness_sources.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tReached\tSumDist\tEcc\n");
+    write_rows(fp, n_src, threads, [&](int64_t i, std::string &buf) {
+        char tmp[96];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)source[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)source[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%lld\t%lld\t%d\n", (long long)reached[(size_t)i], (long long)sumd[(size_t)i], (int)ecc[(size_t)i]);
         buf.append(tmp, (size_t)len);
     });
     fclose(fp);
@@ -1747,6 +1820,30 @@ int main(int argc, const char **argv)
             leave(EXIT_FAILURE);
         }
         write_graphlets(ctx, gl_edges, args.outdir, names, nv, args.threads);
+    }
+
+    // betweenness centrality of the whole graph (no counterpart in the reference; opt-in): KOMB_BETWEENNESS=all | <n>[:<seed>]
+    const char *btw_env = getenv("KOMB_BETWEENNESS");
+    if (btw_env && *btw_env) {
+        long long btw_n = -1;
+        unsigned long long btw_seed = 1;
+        bool ok = !strcmp(btw_env, "all");
+        if (!ok && *btw_env >= '0' && *btw_env <= '9') {
+            char *end = nullptr;
+            errno = 0;
+            btw_n = strtoll(btw_env, &end, 10);
+            ok = errno == 0 && btw_n >= 0;
+            if (ok && *end == ':' && end[1] >= '0' && end[1] <= '9') {
+                btw_seed = strtoull(end + 1, &end, 10);
+                ok = errno == 0;
+            }
+            ok = ok && *end == 0;
+        }
+        if (!ok) {
+            fprintf(stderr, "komb2: KOMB_BETWEENNESS=%s: expected all or <n>[:<seed>]\n", btw_env);
+            leave(EXIT_FAILURE);
+        }
+        write_betweenness(ctx, (int64_t)btw_n, (uint64_t)btw_seed, args.outdir, names, nv, args.threads);
     }
 
     // runTruss (src/graph.cpp:486-563) -- disabled in the reference at :478, opt-in here
