@@ -120,7 +120,7 @@ int         komb_abi_version(void);
  * NUC_SHORT, NUC_HEAVY, NUC_CAP (komb_nucleus_run, below), MAXCLQ_SEED, MAXCLQ_LDS, MAXCLQ_LIST, MAXCLQ_DEBUG
  * (komb_max_clique_run, below), CENSUS_LDS, CENSUS_PIVOT, CENSUS_DEBUG (komb_clique_census_run, below), MAXIMAL_LDS,
  * MAXIMAL_PIVOT, MAXIMAL_LIST, MAXIMAL_DEBUG (komb_maximal_cliques_run, below), PERC_GROUP, PERC_DEBUG
- * (komb_clique_communities_run, below), BICONN_HEAVY (komb_biconnected_run, below), GRAPHLET_SHORT, GRAPHLET_LDS, GRAPHLET_DEBUG (komb_graphlets_run, below), BTW_GRID, BTW_DEBUG (komb_betweenness_run, below), and the
+ * (komb_clique_communities_run, below), BICONN_HEAVY (komb_biconnected_run, below), GRAPHLET_SHORT, GRAPHLET_LDS, GRAPHLET_DEBUG (komb_graphlets_run, below), BTW_GRID, BTW_DEBUG (komb_betweenness_run, below), DIST_WORDS, DIST_GRID, DIST_DEBUG (komb_distances_run, below), and the
  * stderr traces TRI_DEBUG, POOL_DEBUG, BUILD_DEBUG, LOCAL_DEBUG, TAIL_DEBUG, STRUCT_DEBUG, NUC_DEBUG, COMP_SAMPLE (0 | 1:
  * komb_components_run's core kind in one pass over the rows, or skipping the giant component's), DENSEST_LOCAL (0 | 1:
  * komb_densest_subgraph_run's rounds never / whenever they fit in the single-workgroup LDS kernel), and POISON ("0xWWWWWWWW": every device
@@ -964,6 +964,57 @@ int komb_betweenness_fetch(komb_ctx *ctx, double *bc /*[nv], may be NULL*/);
 int komb_betweenness_fetch_sources(komb_ctx *ctx, int32_t *source, int64_t *n_reached, int64_t *sum_dist, int32_t *ecc /*[n_sources] each, any may be NULL*/);
 int komb_betweenness_info(komb_ctx *ctx, int64_t *n_sources, int32_t *flags, int32_t *depth_max, int64_t *n_batches,
                           int64_t *n_level_steps, double *ms);   /* any may be NULL */
+
+/* ---- distance analysis from chosen sources ----------------------------- */
+/* Closeness and harmonic sums, eccentricities and the neighbourhood function (hop plot) from a list of source vertices (all of
+ * them, or a sample: Eppstein & Wang 2004) on the RESIDENT graph, as for komb_betweenness_run: ORIGINAL ids, the symmetric CSR
+ * that komb_graph_get_csr returns, every edge of length 1.  It needs no other result.  Let d(i, v) be the distance from
+ * sources[i] to v where v can be reached; a source reaches itself at distance 0; a vertex that appears k times in the list
+ * counts k times, once per entry.  sources == NULL means every vertex in ascending order (n_sources is ignored).
+ * Per vertex v (komb_distances_fetch; any output may be NULL):
+ *   n_reached[v] = #{i : d(i, v) exists};  sum_dist[v] = the sum of those d(i, v);  ecc[v] = the largest of them, -1 when no
+ *   source reaches v.  harmonic[v] is an IEEE-754 binary64 whose ROUNDING ORDER IS PART OF THE DEFINITION:
+ *     cut the list into blocks of 64 consecutive entries.  For block b: h_b = 0.0; for L = 1, 2, ... ascending: c = #{i in b :
+ *     d(i, v) = L}; if c > 0: h_b = h_b + (double)c / (double)L (the division rounds once, then the addition rounds once).
+ *     Then harmonic[v] = 0.0; for b ascending: harmonic[v] = harmonic[v] + h_b.
+ *   It is a function of the graph and the list only, whatever DIST_WORDS and DIST_GRID are.  (Closeness in igraph's sense is
+ *   (n_reached[v] - 1) / sum_dist[v] after a run from every vertex; the harmonic centrality of networkx is harmonic[v].)
+ * Per source, in the order given (komb_distances_fetch_sources; any output may be NULL): the integers that
+ * komb_betweenness_fetch_sources defines, with the same meaning: source[i] = the id; n_reached[i] = the vertices reached, the
+ * source included; sum_dist[i] = the sum of their distances; ecc[i] = the largest.  With sources == NULL the two views agree
+ * by symmetry.
+ * komb_distances_histogram: pairs[L] = #{(i, v) : d(i, v) = L} for L = 0 .. depth_max.  cap = the room at pairs in entries:
+ * cap < depth_max + 1 is KOMB_ERR_ARG and nothing is written.
+ * komb_distances_info (any output may be NULL): n_sources; flags has KOMB_DISTANCES_ALL when the run had sources == NULL: ecc[]
+ * are then the exact eccentricities, depth_max the diameter of the component with the largest one (otherwise a lower bound),
+ * depth_min, the smallest per-source ecc, the radius in igraph's sense (0 when a vertex is isolated; 0 without a source), and
+ * sum_all twice the Wiener index.  n_pairs = the sum of pairs[]; sum_all = the sum of L * pairs[L].  n_batches = the batches
+ * of 64 W consecutive sources the run was made in, ceil(n_sources / (64 W)), W = DIST_WORDS; n_level_steps = the level steps
+ * of the run, the sum over the batches of E + 1 where E is the batch's largest ecc (the last step of a batch finds nothing);
+ * both are 0 on a graph without a vertex.  ms = the device time.
+ * Every count fits 63 bits: n_sources and the number of vertices nv are below 2^31, so n_reached[], pairs[] and n_pairs are
+ * at most n_sources * nv < 2^62, and a sum_dist[] is at most 2^31 distances below 2^31 each, < 2^62.  sum_all is n_pairs
+ * times the mean distance: it fits unless that reaches 2^63, which takes more than 2^30 sources on more than 2^30 vertices
+ * at a mean distance above 8 -- a run out of reach of the level-by-level traversal; the value would wrap.
+ * n_sources < 0, or an id outside [0, nv): KOMB_ERR_ARG.  A pool failure: KOMB_ERR_NOMEM.  No context or no graph loaded:
+ * KOMB_ERR_ARG.  Fetch, histogram or info before a run on this graph: KOMB_ERR_STATE.  A failing call writes nothing to its
+ * outputs.  The result lives in arrays of its own and is installed only when a run has succeeded: a refused or failed run
+ * leaves the PREVIOUS distance result readable.  It belongs to the graph: a graph load drops it.  No k-core, k-truss,
+ * betweenness or other analysis call changes or drops it, and a run changes none of their results, no komb_stats field and not
+ * the resident k-truss preparation.
+ * Memory: three masks and a partial sum of W 64-bit words each and 28 bytes of result per vertex, about 60 to 160 bytes per
+ * vertex, the masks given back when the run ends.
+ * Options (none changes a result): DIST_WORDS=1|2|4: W, the 64-bit words per vertex and mask, so 64 W sources share one pass
+ * over the rows (default 4; other values round down to one of the three); DIST_GRID=<n>: at most n workgroups per level step
+ * (default and at most 2048; tests lower it to make every wave take several turns); DIST_DEBUG: one stderr line with the batch
+ * and level counts and the share of row entries the early exit skipped. */
+#define KOMB_DISTANCES_ALL 1
+int komb_distances_run(komb_ctx *ctx, int64_t n_sources, const int32_t *sources /* NULL: all */);
+int komb_distances_fetch(komb_ctx *ctx, int64_t *n_reached, int64_t *sum_dist, int32_t *ecc, double *harmonic /*[nv] each, any may be NULL*/);
+int komb_distances_fetch_sources(komb_ctx *ctx, int32_t *source, int64_t *n_reached, int64_t *sum_dist, int32_t *ecc /*[n_sources] each, any may be NULL*/);
+int komb_distances_histogram(komb_ctx *ctx, int64_t *pairs /*[depth_max + 1]*/, int64_t cap);
+int komb_distances_info(komb_ctx *ctx, int64_t *n_sources, int32_t *flags, int32_t *depth_max, int32_t *depth_min,
+                        int64_t *n_pairs, int64_t *sum_all, int64_t *n_batches, int64_t *n_level_steps, double *ms);   /* any may be NULL */
 
 /* ---- synthetic workload (host code, no device) ------------------------- */
 /* Power-law "hybrid unitig graph" generator of SURVEY.md section 8(d): a union

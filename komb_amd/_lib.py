@@ -57,6 +57,7 @@ KOMB_DENSEST_CORE, KOMB_DENSEST_PREFIX = 0, 1
 KOMB_SC_OUTLIER, KOMB_SC_HUB, KOMB_SC_BORDER, KOMB_SC_CORE = 0, 1, 2, 3
 KOMB_GRAPHLET_ORBITS, KOMB_GRAPHLET_TYPES, KOMB_GRAPHLET_SATURATED = 15, 9, 1
 KOMB_BETWEENNESS_ROUNDED = 1
+KOMB_DISTANCES_ALL = 1
 KOMB_MAXCLQ_EXACT, KOMB_MAXCLQ_ENUMERATED, KOMB_MAXCLQ_LISTED = 1, 2, 4
 KOMB_MAXCLQ_OVERSHOOT = 262144
 KOMB_CENSUS_COMPLETE, KOMB_CENSUS_SATURATED = 1, 2
@@ -141,6 +142,13 @@ SIGNATURES = {
     "komb_betweenness_fetch_sources": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "komb_betweenness_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                      ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
+    "komb_distances_run": (_i32, [_vp, _i64, _vp]),
+    "komb_distances_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "komb_distances_fetch_sources": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "komb_distances_histogram": (_i32, [_vp, _vp, _i64]),
+    "komb_distances_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                   ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
     "komb_nucleus_run": (_i32, [_vp]),
     "komb_nucleus_count": (_i32, [_vp, ctypes.POINTER(_i64)]),
     "komb_nucleus_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),

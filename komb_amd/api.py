@@ -44,7 +44,8 @@ OPTION_NAMES = ("FINISH", "LOCAL_LIMIT", "LOCAL_ITEMS", "LOCAL_DENSITY", "LOCAL_
                 "TRI_DEBUG", "POOL_DEBUG", "BUILD_DEBUG", "LOCAL_DEBUG", "TAIL_DEBUG", "COMP_SAMPLE", "COMM_SHORT", "COMM_HEAVY", "DENSEST_LOCAL", "STRUCT_DEBUG",
                 "NUC_SHORT", "NUC_HEAVY", "NUC_CAP", "NUC_DEBUG", "MAXCLQ_SEED", "MAXCLQ_LDS", "MAXCLQ_LIST", "MAXCLQ_DEBUG", "CENSUS_LDS", "CENSUS_PIVOT",
                 "CENSUS_DEBUG", "MAXIMAL_LDS", "MAXIMAL_PIVOT", "MAXIMAL_LIST", "MAXIMAL_DEBUG", "PERC_GROUP", "PERC_DEBUG", "BICONN_HEAVY",
-                "GRAPHLET_LDS", "GRAPHLET_SHORT", "GRAPHLET_DEBUG", "BTW_GRID", "BTW_DEBUG", "POISON")
+                "GRAPHLET_LDS", "GRAPHLET_SHORT", "GRAPHLET_DEBUG", "BTW_GRID", "BTW_DEBUG", "DIST_WORDS", "DIST_GRID",
+                "DIST_DEBUG", "POISON")
 
 # (ALLOC_FAIL_AT / ALLOC_TRIM_AT are one-shot triggers counted from the moment they are set: they are NOT forwarded -- forwarding
 # would re-arm them before every call; a test sets them with set_option)
@@ -618,6 +619,53 @@ class KombAccel:
         self.betweenness_run(sources)
         bc = self.betweenness_fetch()
         return (bc / 2 if halve else bc), self.betweenness_fetch_sources(), self.betweenness_info()
+
+    # ---- distance analysis from chosen sources on the resident graph (include/komb_accel.h)
+    def distances_run(self, sources=None):
+        """sources: vertex ids in the order they count (duplicates allowed); None = every vertex in ascending order."""
+        self._sync_env_options()
+        if sources is None:
+            self._check(self._lib.komb_distances_run(self._ctx, 0, None))
+            return
+        src = as_c(np.asarray(sources).reshape(-1), np.int32)
+        self._check(self._lib.komb_distances_run(self._ctx, len(src), ptr(src) if len(src) else ptr(np.zeros(1, np.int32))))
+
+    def distances_fetch(self):
+        """{"n_reached", "sum_dist", "ecc", "harmonic"}: one entry per vertex."""
+        n = max(self.nv, 0)
+        ecc, harmonic = _out_i32(n), _out_f64(n)
+        reached, sumd = np.full(n, SENTINEL_I32, dtype=np.int64), np.full(n, SENTINEL_I32, dtype=np.int64)
+        self._check(self._lib.komb_distances_fetch(self._ctx, ptr(reached), ptr(sumd), ptr(ecc), ptr(harmonic)))
+        return {"n_reached": reached, "sum_dist": sumd, "ecc": ecc, "harmonic": harmonic}
+
+    def distances_fetch_sources(self):
+        """{"source", "n_reached", "sum_dist", "ecc"}: one entry per source of the last run, in the order given."""
+        n = self.distances_info()["n_sources"]
+        source, ecc = _out_i32(n), _out_i32(n)
+        reached, sumd = np.full(n, SENTINEL_I32, dtype=np.int64), np.full(n, SENTINEL_I32, dtype=np.int64)
+        self._check(self._lib.komb_distances_fetch_sources(self._ctx, ptr(source), ptr(reached), ptr(sumd), ptr(ecc)))
+        return {"source": source, "n_reached": reached, "sum_dist": sumd, "ecc": ecc}
+
+    def distances_histogram(self):
+        """pairs int64[depth_max + 1]: the (source, vertex) pairs at every distance."""
+        pairs = np.full(self.distances_info()["depth_max"] + 1, SENTINEL_I32, dtype=np.int64)
+        self._check(self._lib.komb_distances_histogram(self._ctx, ptr(pairs), len(pairs)))
+        return pairs
+
+    def distances_info(self):
+        """{"n_sources", "flags", "depth_max", "depth_min", "n_pairs", "sum_all", "n_batches", "n_level_steps", "ms"} of the last run."""
+        n, npairs, total, nb, steps = (ctypes.c_int64() for _ in range(5))
+        flags, dmax, dmin, ms = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        self._check(self._lib.komb_distances_info(self._ctx, ctypes.byref(n), ctypes.byref(flags), ctypes.byref(dmax), ctypes.byref(dmin),
+                                                  ctypes.byref(npairs), ctypes.byref(total), ctypes.byref(nb), ctypes.byref(steps),
+                                                  ctypes.byref(ms)))
+        return {"n_sources": n.value, "flags": flags.value, "depth_max": dmax.value, "depth_min": dmin.value, "n_pairs": npairs.value,
+                "sum_all": total.value, "n_batches": nb.value, "n_level_steps": steps.value, "ms": ms.value}
+
+    def run_distances(self, sources=None):
+        """(per-vertex dict, per-source dict, pairs, info)."""
+        self.distances_run(sources)
+        return self.distances_fetch(), self.distances_fetch_sources(), self.distances_histogram(), self.distances_info()
 
     # ---- (3,4)-nucleus decomposition: triangles of the last k-truss result peeled by their 4-cliques (include/komb_accel.h)
     NUCLEUS_FIELDS = ("a", "b", "c", "key0", "theta")

@@ -92,6 +92,7 @@ static_assert(KOMB_COMM_K_MAX == KOMB_BICONN_K_MAX, "resolve_truss_k serves both
 #define NO_SC "no structural clustering of the current k-truss result"
 #define NO_GL "no graphlet census of the current k-truss result"
 #define NO_BTW "komb_betweenness_run has not completed on this graph"
+#define NO_DIST "komb_distances_run has not completed on this graph"
 #define NO_NUC "no nucleus decomposition of the current k-truss result"
 #define NO_MC "no maximum-clique search of the current k-truss result"
 #define NO_CC "no clique census of the current k-truss result"
@@ -606,6 +607,62 @@ int komb_betweenness_info(komb_ctx *ctx, int64_t *n_sources, int32_t *flags, int
     if (n_sources) *n_sources = (int64_t)r.source.size();
     if (flags) *flags = r.flags;
     if (depth_max) *depth_max = r.depth_max;
+    if (n_batches) *n_batches = r.n_batches;
+    if (n_level_steps) *n_level_steps = r.n_level_steps;
+    if (ms) *ms = r.ms;
+    return KOMB_OK;
+}
+
+int komb_distances_run(komb_ctx *ctx, int64_t n_sources, const int32_t *sources)
+{
+    KOMB_HIER_ENTER(ctx, "komb_distances_run");
+    return distances_run(ctx, n_sources, sources);
+}
+
+int komb_distances_fetch(komb_ctx *ctx, int64_t *n_reached, int64_t *sum_dist, int32_t *ecc, double *harmonic)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_distances_fetch", ctx->dist.done, NO_DIST);
+    const komb_ctx::Distances &r = ctx->dist;
+    KOMB_TRY(fetch(ctx, n_reached, r.n_reached, (size_t)ctx->nv));
+    KOMB_TRY(fetch(ctx, sum_dist, r.sum_dist, (size_t)ctx->nv));
+    KOMB_TRY(fetch(ctx, ecc, r.ecc, (size_t)ctx->nv));
+    return fetch(ctx, harmonic, r.harmonic, (size_t)ctx->nv);
+}
+
+int komb_distances_fetch_sources(komb_ctx *ctx, int32_t *source, int64_t *n_reached, int64_t *sum_dist, int32_t *ecc)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_distances_fetch_sources", ctx->dist.done, NO_DIST);
+    const komb_ctx::Distances &r = ctx->dist;
+    const size_t n = r.source.size();
+    if (source && n) memcpy(source, r.source.data(), n * sizeof(int32_t));
+    if (n_reached && n) memcpy(n_reached, r.s_reached.data(), n * sizeof(int64_t));
+    if (sum_dist && n) memcpy(sum_dist, r.s_sum_dist.data(), n * sizeof(int64_t));
+    if (ecc && n) memcpy(ecc, r.s_ecc.data(), n * sizeof(int32_t));
+    return KOMB_OK;
+}
+
+int komb_distances_histogram(komb_ctx *ctx, int64_t *pairs, int64_t cap)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_distances_histogram", ctx->dist.done, NO_DIST);
+    const komb_ctx::Distances &r = ctx->dist;
+    if (cap < (int64_t)r.pairs.size())
+        KOMB_FAIL(ctx, KOMB_ERR_ARG, "komb_distances_histogram: room for %lld distances, the run has %lld", (long long)cap,
+                  (long long)r.pairs.size());
+    if (pairs) memcpy(pairs, r.pairs.data(), r.pairs.size() * sizeof(int64_t));
+    return KOMB_OK;
+}
+
+int komb_distances_info(komb_ctx *ctx, int64_t *n_sources, int32_t *flags, int32_t *depth_max, int32_t *depth_min, int64_t *n_pairs,
+                        int64_t *sum_all, int64_t *n_batches, int64_t *n_level_steps, double *ms)
+{
+    KOMB_HIER_ENTER_DONE(ctx, "komb_distances_info", ctx->dist.done, NO_DIST);
+    const komb_ctx::Distances &r = ctx->dist;
+    if (n_sources) *n_sources = (int64_t)r.source.size();
+    if (flags) *flags = r.flags;
+    if (depth_max) *depth_max = r.depth_max;
+    if (depth_min) *depth_min = r.depth_min;
+    if (n_pairs) *n_pairs = r.n_pairs;
+    if (sum_all) *sum_all = r.sum_all;
     if (n_batches) *n_batches = r.n_batches;
     if (n_level_steps) *n_level_steps = r.n_level_steps;
     if (ms) *ms = r.ms;

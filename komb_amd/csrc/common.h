@@ -468,6 +468,25 @@ struct komb_ctx {
         bool done = false;
     } btw;
 
+    // ---- distance analysis from chosen sources (distances.hip): a snapshot in arrays of its own, dropped with the graph
+    // (graph_free) and by nothing else
+    struct Distances {
+        DevArr<int64_t> n_reached, sum_dist; // [nv] sources that reach the vertex | sum of their distances, ORIGINAL ids (pool blocks)
+        DevArr<int32_t> ecc;                 // [nv] the largest of those distances, -1 where no source reaches the vertex
+        DevArr<double> harmonic;             // [nv] the harmonic sum in the order of the definition
+        std::vector<int32_t> source;         // [n_sources] the sources of the last run, in the order given
+        std::vector<int64_t> s_reached, s_sum_dist;   // [n_sources] vertices reached (the source included) | sum of their distances
+        std::vector<int32_t> s_ecc;          // [n_sources] the largest distance
+        std::vector<int64_t> pairs;          // [depth_max + 1] (source, vertex) pairs at every distance
+        int32_t flags = 0, depth_max = 0, depth_min = 0;   // KOMB_DISTANCES_ALL | the largest | the smallest per-source ecc
+        int64_t n_pairs = 0, sum_all = 0;    // the sum of pairs[] | of L * pairs[L]
+        int64_t n_batches = 0, n_level_steps = 0;
+        int64_t visits = 0, rows = 0;        // row entries the level steps looked at | the lengths of the rows they walked (option DIST_DEBUG prints them)
+        int32_t words = 0;                   // 64-bit words per vertex and mask of the run (option DIST_WORDS)
+        double ms = 0.0;                     // device time of the last run (HIP events)
+        bool done = false;
+    } dist;
+
     // ---- (3,4)-nucleus decomposition (nucleus.hip): arrays of their own (pool blocks), indexed like the k-truss result they were
     // computed from and dropped with it (truss_free)
     struct Nucleus {
@@ -775,6 +794,7 @@ int structural_run(komb_ctx *ctx, int32_t eps_num, int32_t eps_den, int32_t mu);
 int structural_fetch_edges(komb_ctx *ctx, int32_t *similar);  // structural.hip: similar[] of the last run as 0 | 1 words (host output)
 int graphlets_run(komb_ctx *ctx);                             // graphlets.hip: the k-truss result it needs checked by the caller
 int betweenness_run(komb_ctx *ctx, int64_t n_sources, const int32_t *sources);   // betweenness.hip: sources null = every vertex; checks its arguments itself
+int distances_run(komb_ctx *ctx, int64_t n_sources, const int32_t *sources);     // distances.hip: sources null = every vertex; checks its arguments itself
 int nucleus_run(komb_ctx *ctx);                               // nucleus.hip: the k-truss result it needs checked by the caller
 int nucleus_hierarchy_run(komb_ctx *ctx);                     // nucleus_hierarchy.hip: the nucleus result it needs checked by the caller
 int nucleus_hierarchy_labels(komb_ctx *ctx, int32_t k, int32_t *label, int32_t *size);   // k checked and resolved by the caller; host outputs, either may be null

@@ -289,7 +289,7 @@ void graph_free(komb_ctx *ctx)
     truss_free(ctx);
     prep_free(ctx, &ctx->prep);
     // the results with the graph's lifetime (those of a k-truss result went with truss_free)
-    ctx->core = {}; ctx->onion = {}; ctx->comp = {}; ctx->hier = {}; ctx->dens = {}; ctx->btw = {};
+    ctx->core = {}; ctx->onion = {}; ctx->comp = {}; ctx->hier = {}; ctx->dens = {}; ctx->btw = {}; ctx->dist = {};
     if (ctx->d_o_rowptr) (void)hipFree(ctx->d_o_rowptr);
     if (ctx->d_o_col) (void)hipFree(ctx->d_o_col);
     ctx->d_o_rowptr = nullptr; ctx->d_o_col = nullptr;

@@ -93,6 +93,14 @@
 //                       reads back to the same binary64.  betweenness_sources.tsv: #VID, Name, Reached, SumDist, Ecc -- one
 //                       row per source in the order passed: the unitigs it reaches (itself included), the sum of their
 //                       distances and the largest.  Any other value is a usage error.  Nothing else changes.
+//   KOMB_DISTANCES=all|<n>[:<seed>]  also write the distance analysis (komb_distances_run) of the whole graph from every
+//                       unitig, or from the sample that the same value of KOMB_BETWEENNESS names.  distances.tsv: #VID, Name,
+//                       Reached, SumDist, Ecc, Harmonic -- one row per unitig in VID order: the sources that reach it, the sum
+//                       of their distances, the largest (-1 when none reaches it) and the harmonic sum, printed with %.17g,
+//                       which reads back to the same binary64.  distance_sources.tsv: #VID, Name, Reached, SumDist, Ecc -- one
+//                       row per source in the order passed, as in betweenness_sources.tsv.  distance_histogram.tsv: #Distance,
+//                       Pairs -- the (source, unitig) pairs at every distance from 0 to the largest.  Any other value is a
+//                       usage error.  Nothing else changes.
 //   KOMB_NUCLEUS=1      with KOMB_TRUSS=1: also write, after the truss stage, the (3,4)-nucleus decomposition of its result
 //                       (komb_nucleus_run: triangles peeled by the 4-cliques they lie in).  nucleus_triangles.tsv:
 //                       #Name_A, Name_B, Name_C, Cliques, Theta -- one row per triangle in triangle order (ascending VIDs),
@@ -802,8 +810,8 @@ void write_graphlets(komb_ctx *ctx, bool with_edges, const std::string &outdir, 
     fclose(fp);
 }
 
-// KOMB_BETWEENNESS: komb_betweenness_run on the resident graph from every vertex (n < 0 or n >= nv) or from the n vertices with
-// the smallest splitmix64(seed ^ vid), as two tables: one row per vertex in VID order, one row per source in the order passed
+// KOMB_BETWEENNESS and KOMB_DISTANCES name their sources the same way: every vertex (n < 0 or n >= nv), or the n vertices with the
+// smallest splitmix64(seed ^ vid), ties by id, passed in ascending id -- so the same value analyses the same sources
 uint64_t splitmix64(uint64_t x)
 {
     x += 0x9E3779B97F4A7C15ull;
@@ -812,24 +820,79 @@ uint64_t splitmix64(uint64_t x)
     return x ^ (x >> 31);
 }
 
-void write_betweenness(komb_ctx *ctx, int64_t n, uint64_t seed, const std::string &outdir, const Names &names, int64_t nv, int threads)
+struct SourceChoice {
+    int64_t n = -1;                          // < 0: all
+    uint64_t seed = 1;
+};
+
+// all | <n>[:<seed>]; anything else ends the program with the usage line of switch `name`
+SourceChoice parse_source_choice(const char *name, const char *value)
+{
+    SourceChoice c;
+    long long n = -1;
+    unsigned long long seed = 1;
+    bool ok = !strcmp(value, "all");
+    if (!ok && *value >= '0' && *value <= '9') {
+        char *end = nullptr;
+        errno = 0;
+        n = strtoll(value, &end, 10);
+        ok = errno == 0 && n >= 0;
+        if (ok && *end == ':' && end[1] >= '0' && end[1] <= '9') {
+            seed = strtoull(end + 1, &end, 10);
+            ok = errno == 0;
+        }
+        ok = ok && *end == 0;
+    }
+    if (!ok) {
+        fprintf(stderr, "komb2: %s=%s: expected all or <n>[:<seed>]\n", name, value);
+        leave(EXIT_FAILURE);
+    }
+    c.n = (int64_t)n; c.seed = (uint64_t)seed;
+    return c;
+}
+
+// the list a run is given: false = every vertex (pass NULL), true = src (which may be empty)
+bool sample_sources(const SourceChoice &c, int64_t nv, std::vector<int32_t> &src)
+{
+    if (c.n < 0 || c.n >= nv) return false;
+    std::vector<std::pair<uint64_t, int32_t>> key((size_t)nv);
+    for (int64_t v = 0; v < nv; ++v) key[(size_t)v] = {splitmix64(c.seed ^ (uint64_t)v), (int32_t)v};
+    std::partial_sort(key.begin(), key.begin() + c.n, key.end());
+    for (int64_t i = 0; i < c.n; ++i) src.push_back(key[(size_t)i].second);
+    std::sort(src.begin(), src.end());
+    return true;
+}
+
+// #VID, Name, Reached, SumDist, Ecc: one row per source in the order passed
+void write_source_table(const std::string &path, const Names &names, int threads, const std::vector<int32_t> &source,
+                        const std::vector<int64_t> &reached, const std::vector<int64_t> &sumd, const std::vector<int32_t> &ecc)
+{
+    FILE *fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#VID\tName\tReached\tSumDist\tEcc\n");
+    write_rows(fp, (int64_t)source.size(), threads, [&](int64_t i, std::string &buf) {
+        char tmp[96];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)source[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+        buf.append(names.name[(size_t)source[(size_t)i]]);
+        len = snprintf(tmp, sizeof(tmp), "\t%lld\t%lld\t%d\n", (long long)reached[(size_t)i], (long long)sumd[(size_t)i], (int)ecc[(size_t)i]);
+        buf.append(tmp, (size_t)len);
+    });
+    fclose(fp);
+}
+
+// KOMB_BETWEENNESS: komb_betweenness_run on the resident graph, as two tables: one row per vertex in VID order, one row per source
+void write_betweenness(komb_ctx *ctx, const SourceChoice &choice, const std::string &outdir, const Names &names, int64_t nv, int threads)
 {
     std::vector<int32_t> src;
-    const bool all = n < 0 || n >= nv;
-    if (!all) {
-        std::vector<std::pair<uint64_t, int32_t>> key((size_t)nv);
-        for (int64_t v = 0; v < nv; ++v) key[(size_t)v] = {splitmix64(seed ^ (uint64_t)v), (int32_t)v};
-        std::partial_sort(key.begin(), key.begin() + n, key.end());
-        for (int64_t i = 0; i < n; ++i) src.push_back(key[(size_t)i].second);
-        std::sort(src.begin(), src.end());
-    }
+    const bool all = !sample_sources(choice, nv, src);
     int64_t n_src = 0;
     std::vector<double> bc((size_t)nv);
     std::vector<int32_t> source, ecc;
     std::vector<int64_t> reached, sumd;
     if (nv > 0) {
         int32_t none = 0;
-        int rc = komb_betweenness_run(ctx, all ? 0 : n, all ? nullptr : (src.empty() ? &none : src.data()));
+        int rc = komb_betweenness_run(ctx, all ? 0 : (int64_t)src.size(), all ? nullptr : (src.empty() ? &none : src.data()));
         if (rc != KOMB_OK) die_accel(ctx, "komb_betweenness_run", rc);
         rc = komb_betweenness_info(ctx, &n_src, nullptr, nullptr, nullptr, nullptr, nullptr);
         if (rc != KOMB_OK) die_accel(ctx, "komb_betweenness_info", rc);
@@ -852,18 +915,55 @@ void write_betweenness(komb_ctx *ctx, int64_t n, uint64_t seed, const std::strin
         buf.append(tmp, (size_t)len);
     });
     fclose(fp);
-    path = outdir + "/betweenness_sources.tsv";
-    fp = fopen(path.c_str(), "w+");
+    write_source_table(outdir + "/betweenness_sources.tsv", names, threads, source, reached, sumd, ecc);
+}
+
+// KOMB_DISTANCES: komb_distances_run on the resident graph, as three tables: one row per vertex in VID order, one row per source,
+// one row per distance
+void write_distances(komb_ctx *ctx, const SourceChoice &choice, const std::string &outdir, const Names &names, int64_t nv, int threads)
+{
+    std::vector<int32_t> src;
+    const bool all = !sample_sources(choice, nv, src);
+    int64_t n_src = 0;
+    int32_t depth = 0;
+    std::vector<double> harmonic((size_t)nv);
+    std::vector<int32_t> v_ecc((size_t)nv), source, ecc;
+    std::vector<int64_t> v_reached((size_t)nv), v_sumd((size_t)nv), reached, sumd, pairs(1, 0);
+    if (nv > 0) {
+        int32_t none = 0;
+        int rc = komb_distances_run(ctx, all ? 0 : (int64_t)src.size(), all ? nullptr : (src.empty() ? &none : src.data()));
+        if (rc != KOMB_OK) die_accel(ctx, "komb_distances_run", rc);
+        rc = komb_distances_info(ctx, &n_src, nullptr, &depth, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc != KOMB_OK) die_accel(ctx, "komb_distances_info", rc);
+        source.resize((size_t)n_src); ecc.resize((size_t)n_src); reached.resize((size_t)n_src); sumd.resize((size_t)n_src);
+        pairs.resize((size_t)depth + 1);
+        rc = komb_distances_fetch(ctx, v_reached.data(), v_sumd.data(), v_ecc.data(), harmonic.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_distances_fetch", rc);
+        rc = komb_distances_fetch_sources(ctx, source.data(), reached.data(), sumd.data(), ecc.data());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_distances_fetch_sources", rc);
+        rc = komb_distances_histogram(ctx, pairs.data(), (int64_t)pairs.size());
+        if (rc != KOMB_OK) die_accel(ctx, "komb_distances_histogram", rc);
+    }
+    std::string path = outdir + "/distances.tsv";
+    FILE *fp = fopen(path.c_str(), "w+");
     if (!fp) file_not_found(path);
-    fprintf(fp, "#VID\tName\tReached\tSumDist\tEcc\n");
-    write_rows(fp, n_src, threads, [&](int64_t i, std::string &buf) {
-        char tmp[96];
-        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)source[(size_t)i]);
+    fprintf(fp, "#VID\tName\tReached\tSumDist\tEcc\tHarmonic\n");
+    write_rows(fp, nv, threads, [&](int64_t i, std::string &buf) {
+        char tmp[128];
+        int len = snprintf(tmp, sizeof(tmp), "%d\t", (int)i);
         buf.append(tmp, (size_t)len);
-        buf.append(names.name[(size_t)source[(size_t)i]]);
-        len = snprintf(tmp, sizeof(tmp), "\t%lld\t%lld\t%d\n", (long long)reached[(size_t)i], (long long)sumd[(size_t)i], (int)ecc[(size_t)i]);
+        buf.append(names.name[(size_t)i]);
+        len = snprintf(tmp, sizeof(tmp), "\t%lld\t%lld\t%d\t%.17g\n", (long long)v_reached[(size_t)i], (long long)v_sumd[(size_t)i],
+                       (int)v_ecc[(size_t)i], harmonic[(size_t)i]);
         buf.append(tmp, (size_t)len);
     });
+    fclose(fp);
+    write_source_table(outdir + "/distance_sources.tsv", names, threads, source, reached, sumd, ecc);
+    path = outdir + "/distance_histogram.tsv";
+    fp = fopen(path.c_str(), "w+");
+    if (!fp) file_not_found(path);
+    fprintf(fp, "#Distance\tPairs\n");
+    for (size_t L = 0; L < pairs.size(); ++L) fprintf(fp, "%d\t%lld\n", (int)L, (long long)pairs[L]);
     fclose(fp);
 }
 
@@ -1824,27 +1924,11 @@ int main(int argc, const char **argv)
 
     // betweenness centrality of the whole graph (no counterpart in the reference; opt-in): KOMB_BETWEENNESS=all | <n>[:<seed>]
     const char *btw_env = getenv("KOMB_BETWEENNESS");
-    if (btw_env && *btw_env) {
-        long long btw_n = -1;
-        unsigned long long btw_seed = 1;
-        bool ok = !strcmp(btw_env, "all");
-        if (!ok && *btw_env >= '0' && *btw_env <= '9') {
-            char *end = nullptr;
-            errno = 0;
-            btw_n = strtoll(btw_env, &end, 10);
-            ok = errno == 0 && btw_n >= 0;
-            if (ok && *end == ':' && end[1] >= '0' && end[1] <= '9') {
-                btw_seed = strtoull(end + 1, &end, 10);
-                ok = errno == 0;
-            }
-            ok = ok && *end == 0;
-        }
-        if (!ok) {
-            fprintf(stderr, "komb2: KOMB_BETWEENNESS=%s: expected all or <n>[:<seed>]\n", btw_env);
-            leave(EXIT_FAILURE);
-        }
-        write_betweenness(ctx, (int64_t)btw_n, (uint64_t)btw_seed, args.outdir, names, nv, args.threads);
-    }
+    if (btw_env && *btw_env) write_betweenness(ctx, parse_source_choice("KOMB_BETWEENNESS", btw_env), args.outdir, names, nv, args.threads);
+
+    // distance analysis of the whole graph (no counterpart in the reference; opt-in): KOMB_DISTANCES=all | <n>[:<seed>]
+    const char *dist_env = getenv("KOMB_DISTANCES");
+    if (dist_env && *dist_env) write_distances(ctx, parse_source_choice("KOMB_DISTANCES", dist_env), args.outdir, names, nv, args.threads);
 
     // runTruss (src/graph.cpp:486-563) -- disabled in the reference at :478, opt-in here
     if (env_on("KOMB_TRUSS") && nv > 0) {
