@@ -74,24 +74,30 @@ def one_source(rows, s, fused=False, descending=False):
     return dist, sigma, delta, levels
 
 
-def betweenness(rows, sources=None, fused=False, descending=False):
+def betweenness(rows, sources=None, fused=False, descending=False, cache=None):
     """What komb_betweenness_run / _fetch / _fetch_sources / _info give for the rows (ascending adjacency lists) and the sources
     (None: all): {"bc", "source", "n_reached", "sum_dist", "ecc", "flags", "depth_max", "n_sources", "n_batches",
-    "n_level_steps"}.  Raises Limit where the library answers KOMB_ERR_LIMIT."""
+    "n_level_steps"}.  Raises Limit where the library answers KOMB_ERR_LIMIT.  cache: a dict that keeps the search of every
+    source vertex between calls on the same rows (bc is still summed entry by entry in the order given)."""
     nv = len(rows)
     src = list(range(nv)) if sources is None else [int(s) for s in sources]
     assert all(0 <= s < nv for s in src)
+    cache = {} if cache is None else cache
     bc = [0.0] * nv
     reached, sumd, ecc, flags = [], [], [], 0
     for s in src:
-        dist, sigma, delta, levels = one_source(rows, s, fused, descending)
+        if (s, fused, descending) not in cache:
+            dist, sigma, delta, levels = one_source(rows, s, fused, descending)
+            cache[s, fused, descending] = (delta, sum(len(l) for l in levels), sum(L * len(l) for L, l in enumerate(levels)), len(levels) - 1,
+                                           any(sigma[v] >= TWO53 for l in levels for v in l))
+        delta, n, total, depth, rounded = cache[s, fused, descending]
         for v in range(nv):
             if v != s:
                 bc[v] = bc[v] + delta[v]
-        reached.append(sum(len(l) for l in levels))
-        sumd.append(sum(L * len(l) for L, l in enumerate(levels)))
-        ecc.append(len(levels) - 1)
-        if any(sigma[v] >= TWO53 for l in levels for v in l):
+        reached.append(n)
+        sumd.append(total)
+        ecc.append(depth)
+        if rounded:
             flags |= ROUNDED
     batches = [ecc[i:i + 64] for i in range(0, len(src), 64)]
     steps = sum((max(b) + 1) + max(max(b) - 1, 0) for b in batches) if nv > 0 else 0

@@ -5,7 +5,8 @@ brute(nv, edges)      every 3- and 4-subset of the vertices, classified by (edge
 census(nv, eu, ev)    the counting scheme of the library with none of its machinery: 4-cycles per edge by the dense identity
                       cycles4(u, v) = (A^3)[u, v] - d(u) - d(v) + 1 in float64 (exact below 2^53: nv <= 3000), 4-cliques per
                       edge by common-neighbour sets, the orbits by the closed forms.  Neither the (d, id) order nor a hash
-                      table takes part in a count.
+                      table takes part in a count.  Above 3000 vertices (or as census_sparse) the 4-cycles per edge are
+                      the sum over x in N(u) without v of |N(x) & N(v)| - 1 with plain sets; everything else is shared.
 ordered_items(...)    the work formula of the degree-ordered 4-cycle pass.
 
 Both return {"orbit": uint64[15, nv], "cycles4": uint64[m], "cliques4": uint64[m], "sup": int64[m], "total": {name: int}}
@@ -114,29 +115,38 @@ def _comb2(x):
     return x * (x - 1) // 2
 
 
-def census(nv, eu, ev):
-    assert nv <= 3000, "the dense identity is exact in float64 only while A^3 stays below 2^53"
-    eu = np.asarray(eu, dtype=np.int64)
-    ev = np.asarray(ev, dtype=np.int64)
-    m = len(eu)
-    adj = _adj(nv, eu, ev)
-    d = np.array([len(a) for a in adj], dtype=np.int64)
-    orbit = np.zeros((ORBITS, nv), dtype=np.uint64)
-    if m == 0:
-        z = np.zeros(0, dtype=np.uint64)
-        return {"orbit": orbit, "cycles4": z, "cliques4": z.copy(), "sup": np.zeros(0, dtype=np.int64), "total": totals(orbit)}
+DENSE_MAX_NV = 3000
 
-    # per edge (u, v): triangles, 4-cliques (the edges inside the common neighbourhood), 4-cycles: the walks u-x-y-v of
-    # length 3 less those with x = v (d(v) of them) or y = u (d(u)), the walk u-v-u-v being in both
+
+def _per_edge_dense(nv, eu, ev, adj, d):
+    """(cycles4, sup, cliques4, common) per edge; the 4-cycles by the dense identity: the walks u-x-y-v of length 3 less those
+    with x = v (d(v) of them) or y = u (d(u)), the walk u-v-u-v being in both."""
+    assert nv <= DENSE_MAX_NV, "the dense identity is exact in float64 only while A^3 stays below 2^53"
     A = np.zeros((nv, nv), dtype=np.float64)
     A[eu, ev] = 1.0
     A[ev, eu] = 1.0
     A3 = A @ A @ A
     assert A3.max() < 2.0 ** 53
     cyc = np.rint(A3[eu, ev]).astype(np.int64) - d[eu] - d[ev] + 1
+    return (cyc,) + _triangles_and_cliques(eu, ev, adj)
+
+
+def _per_edge_sparse(nv, eu, ev, adj, d):
+    """The same four with plain sets and no matrix: a 4-cycle through (u, v) is u-x-y-v with x a neighbour of u other than v and
+    y a common neighbour of x and v other than u (u is always one of them): sum over x in N(u) without v of |N(x) & N(v)| - 1."""
+    cyc = np.zeros(len(eu), dtype=np.int64)
+    for i in range(len(eu)):
+        u, v = int(eu[i]), int(ev[i])
+        nv_set = adj[v]
+        cyc[i] = sum(len(adj[x] & nv_set) - 1 for x in adj[u] if x != v)
+    return (cyc,) + _triangles_and_cliques(eu, ev, adj)
+
+
+def _triangles_and_cliques(eu, ev, adj):
+    """(sup, cliques4, common): per edge its common neighbourhood, its size, and the edges inside it."""
+    m = len(eu)
     sup = np.zeros(m, dtype=np.int64)
     clq = np.zeros(m, dtype=np.int64)
-    D2 = np.zeros(nv, dtype=np.int64)
     common = []
     for i in range(m):
         c = adj[int(eu[i])] & adj[int(ev[i])]
@@ -145,6 +155,30 @@ def census(nv, eu, ev):
         inside = sum(len(adj[w] & c) for w in c)
         assert inside % 2 == 0
         clq[i] = inside // 2
+    return sup, clq, common
+
+
+def census_sparse(nv, eu, ev):
+    """census() without the dense A^3: any number of vertices, time in the sum of d(u) d(x) over the 2-paths."""
+    return census(nv, eu, ev, dense=False)
+
+
+def census(nv, eu, ev, dense=None):
+    """dense: the 4-cycles per edge by A^3 (None: up to DENSE_MAX_NV vertices) or by common-neighbour sets."""
+    eu = np.asarray(eu, dtype=np.int64)
+    ev = np.asarray(ev, dtype=np.int64)
+    m = len(eu)
+    adj = _adj(nv, eu, ev)
+    d = np.fromiter((len(a) for a in adj), dtype=np.int64, count=nv)
+    orbit = np.zeros((ORBITS, nv), dtype=np.uint64)
+    if m == 0:
+        z = np.zeros(0, dtype=np.uint64)
+        return {"orbit": orbit, "cycles4": z, "cliques4": z.copy(), "sup": np.zeros(0, dtype=np.int64), "total": totals(orbit)}
+
+    # per edge (u, v): 4-cycles, triangles, 4-cliques (the edges inside the common neighbourhood)
+    dense = nv <= DENSE_MAX_NV if dense is None else dense
+    cyc, sup, clq, common = (_per_edge_dense if dense else _per_edge_sparse)(nv, eu, ev, adj, d)
+    D2 = np.zeros(nv, dtype=np.int64)
     for i in range(m):
         for w in common[i]:                                                 # a triangle (w, eu, ev): its edge opposite w
             D2[w] += sup[i] - 1

@@ -3,7 +3,7 @@
 Three parts, none of which touches a GPU:
   * the catalogue: one plan tuple per public call of komb_amd/api.py (OPS below says what each tuple means);
   * Model: one method per operation; it answers the status code the header promises and keeps which graph is loaded, which of
-    the sixteen results are held (with the parameters of their runs), what kind of k-truss result is current and which of
+    the nineteen results are held (with the parameters of their runs), what kind of k-truss result is current and which of
     the lazily made arrays exist.  Its drop / keep table is TABLE: one line per sentence of the header, the header's line
     number beside it;
   * make_plan(seed) / coverage(plans): the plans tests/test_gpu_analysis_sequences.py drives through one context, and what
@@ -14,11 +14,13 @@ import numpy as np
 
 OK, ARG, STATE = 0, -1, -5
 
-RESULTS = ("core", "onion", "comp", "hier", "dens", "truss", "comm", "bic", "chier", "sc", "nuc", "nhier", "mclq", "cens", "mxl", "perc")
-TRUSS_DERIVED = ("comm", "bic", "chier", "sc", "nuc", "nhier", "mclq", "cens", "mxl", "perc")
+RESULTS = ("core", "onion", "comp", "hier", "dens", "truss", "comm", "bic", "chier", "sc", "nuc", "nhier", "mclq", "cens", "mxl", "perc", "gl",
+           "btw", "dist")
+TRUSS_DERIVED = ("comm", "bic", "chier", "sc", "nuc", "nhier", "mclq", "cens", "mxl", "perc", "gl")
 BASE = ("core", "onion", "comp", "hier", "dens")
+GRAPH_OWNED = ("btw", "dist")                    # only a graph load drops them
 _ALL = RESULTS
-_TEN = TRUSS_DERIVED
+_ELEVEN = TRUSS_DERIVED
 
 # ---- the drop / keep table: (row, the result the row computes, the results it drops, header line, the sentence)
 # A row keeps every result that it neither drops nor computes.  Written from include/komb_accel.h alone.
@@ -31,12 +33,12 @@ TABLE = (
     ("comp", "comp", (), 228, "The result is a snapshot in arrays of its own ... a call changes no k-core, k-truss, onion or CoreA result"),
     ("hier", "hier", (), 261, "The result is a snapshot in arrays of its own ... a run changes none of their results"),
     ("dens", "dens", (), 422, "loading a graph drops it, no other call changes it, a run changes no other result"),
-    ("truss", "truss", _TEN, 800, "A run drops the previous k-truss result, and every analysis that indexes it"),
-    ("truss_vmask", "truss", _TEN, 800, "... (a run under a vmask alike: a new k-truss run of any kind)"),
-    ("slice", "truss", _TEN, 831, "komb_truss_run_slice: a new k-truss run of any kind"),
-    ("truss_sharded", "truss", _TEN, 823, "komb_truss_run_sharded: world == 1 is komb_truss_run"),
+    ("truss", "truss", _ELEVEN, 800, "A run drops the previous k-truss result, and every analysis that indexes it"),
+    ("truss_vmask", "truss", _ELEVEN, 800, "... (a run under a vmask alike: a new k-truss run of any kind)"),
+    ("slice", "truss", _ELEVEN, 831, "komb_truss_run_slice: a new k-truss run of any kind"),
+    ("truss_sharded", "truss", _ELEVEN, 823, "komb_truss_run_sharded: world == 1 is komb_truss_run"),
     ("prepare", None, (), 811, "komb_truss_prepare makes it ahead of time (a no-op when it exists)"),
-    ("unprepare", None, ("truss",) + _TEN, 812, "komb_truss_unprepare drops it together with the last k-truss result"),
+    ("unprepare", None, ("truss",) + _ELEVEN, 812, "komb_truss_unprepare drops it together with the last k-truss result"),
     ("comm", "comm", (), 295, "A communities run changes no k-core, k-truss, onion, components or CoreA result"),
     ("bic", "bic", (), 335, "k-core, onion, components, communities and CoreA calls neither change nor drop it; a run changes none of their results"),
     ("chier", "chier", (), 381, "k-core, onion, components, hierarchy, communities and CoreA calls neither change nor drop them; a run changes none of their results"),
@@ -47,6 +49,9 @@ TABLE = (
     ("cens", "cens", (), 663, "No other call changes or drops it; a run changes no other result"),
     ("mxl", "mxl", ("perc",), 771, "It describes one maximal-cliques result and goes with it: a komb_maximal_cliques_run that succeeds ... drop it"),
     ("perc", "perc", (), 772, "No other call changes or drops it; a run changes no other result"),
+    ("gl", "gl", (), 907, "It indexes one k-truss result ... No other call changes or drops it; a run changes no other result"),
+    ("btw", "btw", (), 953, "It belongs to the graph: a graph load drops it.  No k-core, k-truss or other analysis call changes or drops it"),
+    ("dist", "dist", (), 1002, "It belongs to the graph: a graph load drops it.  No k-core, k-truss, betweenness or other analysis call changes or drops it"),
     ("corea", None, (), 294, "k-core, onion, components and CoreA calls neither change nor drop it (CoreA works on host arrays)"),
     ("densest_block", None, (), 870, "A refusal leaves the resident graph and its results as they were (a peel over copies of the graph)"),
     ("moments", None, (), 877, "Measurement only: fills komb_stats ... makes the k-truss preparation if absent"),
@@ -59,16 +64,16 @@ KEEPS = {t[0]: frozenset(RESULTS) - DROPS[t[0]] - {t[1]} for t in TABLE}
 HEADER_LINE = {t[0]: t[3] for t in TABLE}
 
 # the runs of which the header says "changes ... no komb_stats field"
-STATS_FROZEN = ("onion", "comp", "hier", "dens", "comm", "bic", "chier", "sc", "nuc", "nhier", "mclq", "cens", "mxl", "perc")
+STATS_FROZEN = ("onion", "comp", "hier", "dens", "comm", "bic", "chier", "sc", "nuc", "nhier", "mclq", "cens", "mxl", "perc", "gl", "btw", "dist")
 # who makes the canonical edge list of a whole-graph k-truss result (the header says so with each of them)
-CEU_CONSUMERS = ("fetch", "sc", "cens", "comm", "bic", "comp", "hier", "chier", "mclq", "mxl", "nuc")
-SUP_CONSUMERS = ("fetch_support", "sc")
+CEU_CONSUMERS = ("fetch", "sc", "cens", "comm", "bic", "comp", "hier", "chier", "mclq", "mxl", "nuc", "gl")
+SUP_CONSUMERS = ("fetch_support", "sc", "gl")
 COMM_V_CONSUMERS = ("vertices", "info")
 # the runs that the contract can refuse while a result of their own kind is held: an argument, or (hier, comp) a partial
-# k-truss result under a snapshot that does not index it.  onion has no argument; nuc, chier and nhier have none either, and
+# k-truss result under a snapshot that does not index it.  onion has no argument; nuc, chier, nhier and gl have none either, and
 # whatever makes them KOMB_ERR_STATE has dropped their result before.
-REFUSABLE = ("core", "comp", "hier", "dens", "truss", "comm", "bic", "sc", "mclq", "cens", "mxl", "perc")
-PARAMLESS = ("onion", "chier", "nuc", "nhier")
+REFUSABLE = ("core", "comp", "hier", "dens", "truss", "comm", "bic", "sc", "mclq", "cens", "mxl", "perc", "btw", "dist")
+PARAMLESS = ("onion", "chier", "nuc", "nhier", "gl")
 
 # ---- menus (every value is one the per-analysis tests use)
 KS = (2, 3, 4, -1, "above")                       # thresholds; "above" = one above the largest (the driver resolves it)
@@ -86,6 +91,8 @@ OPTIONS = {
     "DENSEST_LOCAL": ("0", "1", None), "BICONN_HEAVY": ("0", "1", None),
     "CENSUS_LDS": ("0", "64", None), "CENSUS_PIVOT": ("first", None), "MAXCLQ_LDS": ("0", "64", None), "MAXCLQ_SEED": ("0", None),
     "MAXIMAL_LDS": ("0", "64", None), "MAXIMAL_PIVOT": ("first", None), "PERC_GROUP": ("4", "16", "64", None),
+    "GRAPHLET_SHORT": ("0", "100000", None), "GRAPHLET_LDS": ("0", "64", None), "BTW_GRID": ("2", None),
+    "DIST_WORDS": ("1", "2", None), "DIST_GRID": ("2", "3", None),
 }
 MERGE_MAX_NV = 6000
 # The restatement of the clique communities tests all pairs of member cliques: its time is quadratic in the number of maximal
@@ -93,6 +100,21 @@ MERGE_MAX_NV = 6000
 # these four graphs k is therefore drawn from the values that leave at most about 2000 member cliques (measured: A 1733 at
 # k = 5, B 1923 at k = 8, D 1851 at k = 6, C none at k = 4); every other graph takes the menu KS.
 PERC_KS = {"A": (5, 6, "above"), "B": (8, 9, "above"), "C": (4, "above"), "D": (6, 8, "above")}
+# The source lists of betweenness and distances are prefixes of one master list per graph (Graph.master: MASTER_LEN entries
+# drawn with repeats from at most MASTER_POOL vertices), so one search per distinct vertex serves every list; "all" is
+# sources == NULL.  65 entries cross a batch of betweenness and of DIST_WORDS=1, 257 one of DIST_WORDS=4.  Both references
+# cost O(nv) per entry, and a run costs a few launches and a host sync per level of every batch.  The strip C is about 4500
+# levels deep: as measured on the MI355X, a distance run from any vertex of it takes 0.17 s and a betweenness run 0.73 s (about
+# 9000 level steps), where a whole poisoned test took 0.39 s before -- so C gets the empty list only (the measurements behind
+# WALL_SECONDS of tests/test_gpu_analysis_sequences.py; tests/test_gpu_distances.py and tests/test_gpu_betweenness.py have a
+# path of 3000 vertices).  The 524 549 vertices of the strided graph get three entries; every vertex is a source only up to
+# SMALL_NV vertices.  On the graph without a vertex any id is KOMB_ERR_ARG.
+MASTER_LEN, MASTER_POOL = 257, 40
+SMALL_NV = 300
+SOURCE_LENGTHS = {"A": (0, 1, 65, 257), "B": (0, 1, 65, 257), "C": (0,), "D": (0, 1, 65), "E": (0, 1, 65), "E2": (0, 1, 65),
+                  "strided": (0, 1, 3), "nv0": (0, "all")}
+SOURCE_LENGTHS_SMALL = (0, 1, 65, 257, "all")
+BAD_SOURCES = ("id_high", "id_negative", "count")
 
 # ---- what the plan tuples mean
 OPS = {
@@ -108,6 +130,12 @@ OPS = {
     "prepare": "(): komb_truss_prepare", "unprepare": "(): komb_truss_unprepare",
     "comm": "(k,)", "bic": "(k,)", "chier": "()", "sc": "(eps_num, eps_den, mu)", "nuc": "()", "nhier": "()", "mclq": "(budget,)",
     "cens": "(k_lo, k_hi, k_local)", "mxl": "(k_min,)", "perc": "(k,)",
+    "gl": "(): komb_graphlets_run; no graph: KOMB_ERR_ARG, no complete k-truss result: KOMB_ERR_STATE; it asks for the canonical edge "
+          "list and the canonical supports as the fetches do; held: (mask of the k-truss result,)",
+    "btw": "(spec,): komb_betweenness_run; spec ('prefix', n): the first n entries of the graph's master list | 'all': sources == NULL | "
+           "('bad', 'id_high' | 'id_negative' | 'count'): an id == nv, an id == -1, n_sources == -1: KOMB_ERR_ARG, as is a run without "
+           "a graph; a refused run keeps the held result; it needs no other result; held: the spec",
+    "dist": "(spec,): komb_distances_run, as btw",
     "read": "(result, arg): every count / fetch / info / list / labels / nuclei / profile call of the result; held: compared with "
             "the references, else every call must be refused.  arg: truss -- the order of _fetch_varied (0..2); comm -- which "
             "of 'vertices' | 'info' comes first; chier, nhier -- the k of _labels / _nuclei",
@@ -132,6 +160,17 @@ ORDERS = (("B", "A", "C", "hand_sc", "D", "iso7", "E", "E2"),
           ("strided", "hand_nuc", "B", "A", "C", "edge", "D", "book257"))
 SEEDS = (11, 23, 37, 41)
 REUSE_TRANSITIONS = (("B", "A"), ("A", "B"), ("A|B", "C"), ("E", "E2"))
+
+
+def source_lengths():
+    """Every length of the menus."""
+    return {n for menu in list(SOURCE_LENGTHS.values()) + [SOURCE_LENGTHS_SMALL] for n in menu}
+
+
+def source_menu(g):
+    """The specs a plan may give komb_betweenness_run / komb_distances_run on graph g."""
+    assert g in SOURCE_LENGTHS or FACTS[g][0] <= SMALL_NV, g
+    return tuple("all" if n == "all" else ("prefix", n) for n in SOURCE_LENGTHS.get(g, SOURCE_LENGTHS_SMALL))
 
 
 def _clique(ids):
@@ -349,7 +388,7 @@ class Model:
         self.prepared = False
         return OK
 
-    # ---- the ten analyses of a k-truss result
+    # ---- the eleven analyses of a k-truss result
     def _derived(self, rec, result, params, bad_arg=False, consumes=True, extra_state=False):
         if self.graph is None or bad_arg:
             return self._refused(rec, result, ARG)
@@ -399,6 +438,25 @@ class Model:
         if self.graph is not None and not bad and self.complete() and not no_list:
             return self._ran(rec, "perc", (k, self.held["mxl"][0], self.truss_key()))
         return self._derived(rec, "perc", (k,), bad_arg=bad, consumes=False, extra_state=True)
+
+    def op_gl(self, rec):
+        code = self._derived(rec, "gl", ())
+        if code == OK:
+            self._consume_sup(rec, "gl")
+        return code
+
+    # ---- the two analyses that belong to the graph
+    def _graph_owned(self, rec, result, spec):
+        if self.graph is None or (spec != "all" and spec[0] == "bad"):
+            return self._refused(rec, result, ARG)
+        assert spec in source_menu(self.graph), (self.graph, spec)
+        return self._ran(rec, result, spec)
+
+    def op_btw(self, rec, spec):
+        return self._graph_owned(rec, "btw", spec)
+
+    def op_dist(self, rec, spec):
+        return self._graph_owned(rec, "dist", spec)
 
     # ---- readers
     def op_read(self, rec, result, arg=None):
@@ -457,6 +515,17 @@ class _Gen:
         self.rng = np.random.default_rng([seed, 7])
         self.m = Model()
         self.plan = []
+        self.turn = {}
+
+    def spec(self, r):
+        """The source lists of a menu in turn, over all the graphs of the plan that share the menu: every vertex (where the
+        menu has it), the longest prefix, the empty one, the others from long to short, and round again -- so a menu that
+        only one graph has meets its longest list, whatever else the plan does on that graph."""
+        menu = source_menu(self.m.graph)
+        prefixes = sorted((s for s in menu if s != "all"), reverse=True)
+        menu = tuple(s for s in menu if s == "all") + tuple(prefixes[:1] + prefixes[-1:] + prefixes[1:-1])
+        self.turn[r, menu] = self.turn.get((r, menu), -1) + 1
+        return menu[self.turn[r, menu] % len(menu)]
 
     def pick(self, menu):
         return menu[int(self.rng.integers(0, len(menu)))]
@@ -493,6 +562,7 @@ class _Gen:
         if r == "perc":
             menu = PERC_KS.get(self.m.graph, (2, 3, 4, "above"))
             return ("perc", self.pick(tuple(k for k in menu if k == "above" or k >= self.m.held["mxl"][0])))
+        if r in GRAPH_OWNED: return (r, self.spec(r))
         return (r,)
 
     def run(self, r):
@@ -562,14 +632,15 @@ class _Gen:
     def bad_run(self, r):
         bad = {"core": ("core", "bad"), "comp": ("comp", self.pick(("core", "truss", 7)), -2), "hier": ("hier", 7), "dens": ("dens", -1),
                "truss": ("slice", 2, 2, None), "comm": ("comm", -2), "bic": ("bic", -3), "sc": ("sc",) + self.pick(((0, 10, 2), (11, 10, 2), (1, 2, 1))),
-               "mclq": ("mclq", -1), "cens": ("cens",) + self.pick(((1, -1, 0), (4, 3, 0))), "mxl": ("mxl", 1), "perc": ("perc", 1)}[r]
+               "mclq": ("mclq", -1), "cens": ("cens",) + self.pick(((1, -1, 0), (4, 3, 0))), "mxl": ("mxl", 1), "perc": ("perc", 1),
+               "btw": ("btw", ("bad", self.pick(BAD_SOURCES))), "dist": ("dist", ("bad", self.pick(BAD_SOURCES)))}[r]
         if r == "comp" and bad[1] == 7:
             bad = ("comp", 7, 2)
         assert self.emit(*bad) in (ARG, STATE)
 
     def state_refusals(self):
         """A partial slice: every truss-derived run and the truss kinds of comp and hier answer KOMB_ERR_STATE, while the
-        snapshots of the core kind stay readable."""
+        snapshots of the core kind stay readable and the analyses that belong to the graph run as ever."""
         if FACTS[self.m.graph][1] < 2:
             return
         if "core" not in self.m.held: self.emit("core", "plain")
@@ -579,17 +650,26 @@ class _Gen:
         self.emit("slice", int(self.rng.integers(0, world)), world, None)
         self.read("truss")
         for op in (("comp", "truss", 3), ("hier", "truss"), ("comm", 3), ("bic", 2), ("chier",), ("sc", 1, 2, 3), ("nuc",), ("nhier",), ("mclq", 0),
-                   ("cens", 2, -1, 0), ("mxl", 2), ("perc", 3)):
+                   ("cens", 2, -1, 0), ("mxl", 2), ("perc", 3), ("gl",)):
             assert self.emit(*op) == STATE
         self.read("comp"); self.read("hier")
+        for r in GRAPH_OWNED:
+            self.run(r)
+            assert self.read(r) == OK
         self.emit("slice", 0, 1, None)                                       # the whole range is a whole result
         self.run(self.pick(TRUSS_DERIVED))
 
     def after_unprepare(self, consumer):
-        """unprepare + truss_run, then straight away a run that has to make (or find) the canonical edge list."""
+        """unprepare + truss_run, then straight away a run that has to make (or find) the canonical edge list; what belongs to
+        the graph is held across the three and read after them."""
+        for r in GRAPH_OWNED:
+            if r not in self.m.held:
+                self.run(r)
         self.emit("unprepare")
         self.emit("truss", self.pick(("plain", "plain", "sharded")), None)
         self.consumer(consumer)
+        for r in GRAPH_OWNED:
+            assert self.read(r) == OK
 
     def consumer(self, c):
         if c == "fetch": self.emit("read", "truss", 2)
@@ -600,7 +680,7 @@ class _Gen:
             self.read(c)
 
     def sweep(self, mask):
-        """A k-truss result under a mask (or of a graph without edges), then each of the ten analyses on it."""
+        """A k-truss result under a mask (or of a graph without edges), then each of the eleven analyses on it."""
         self.emit("truss", self.pick(("plain", "sharded")), mask) if mask else self.emit("truss", "plain", None)
         order = list(TRUSS_DERIVED)
         self.rng.shuffle(order)
@@ -609,6 +689,16 @@ class _Gen:
             if r not in ("nuc", "mxl"):
                 self.read(r)
         self.read("nuc"); self.read("mxl"); self.read("truss")
+
+    def graph_owned(self):
+        """Betweenness and distances, in either order, a refused run of the first one, then both read."""
+        order = list(GRAPH_OWNED)
+        self.rng.shuffle(order)
+        for r in order:
+            self.run(r)
+        self.bad_run(order[0])
+        for r in order:
+            assert self.read(r) == OK
 
     def noise(self):
         x = self.rng.random()
@@ -652,6 +742,9 @@ def make_plan(seed):
             gen.read(gen.pick(RESULTS))
         gen.emit("load", g, "csr" if (sec + index) % 3 == 1 else "edges")
         edges = FACTS[g][1] > 0
+        # what belongs to the graph: on the blocks the graph before left (even sections), or on those of the opening (odd)
+        if sec % 2 == 0:
+            gen.graph_owned()
         if edges:
             # the opening: a whole result and a designated first consumer of the canonical edge list
             n = index * 6 + n_sec
@@ -662,6 +755,8 @@ def make_plan(seed):
             gen.consumer(first)
             gen.read("truss")                                               # (the whole result itself, while it is the current one)
             gen.noise()
+        if sec % 2 == 1:
+            gen.graph_owned()
         if edges:
             gen.noise()
             if n % 3 == 0:
@@ -712,7 +807,7 @@ def sections(plan):
 
 
 def coverage(plans, facts=FACTS):
-    """What the plans exercise, from the plans and the model alone: a dict of the counts behind conditions a-i."""
+    """What the plans exercise, from the plans and the model alone: a dict of the counts behind conditions a-k."""
     runs = {r: 0 for r in RESULTS}
     values = {r: set() for r in RESULTS}
     kinds = {r: set() for r in TRUSS_DERIVED}
@@ -723,6 +818,8 @@ def coverage(plans, facts=FACTS):
     refused = {r: 0 for r in REFUSABLE}
     after_unprep = {c: 0 for c in CEU_CONSUMERS}
     transitions = {t: 0 for t in REUSE_TRANSITIONS}
+    specs = {(r, n): 0 for r in GRAPH_OWNED for n in source_lengths()}
+    owned_across = {r: 0 for r in GRAPH_OWNED}
     n_ops, per_graph = [], []
     for plan in plans:
         log = replay(plan, facts).log
@@ -766,9 +863,16 @@ def coverage(plans, facts=FACTS):
                 sup[rec["sup_first"]] += 1
             if "comm_v_first" in rec:
                 comm_v[rec["comm_v_first"]] += 1
+        for rec in log:
+            if rec.get("ran") in GRAPH_OWNED:
+                specs[rec["ran"], rec["op"][1] if rec["op"][1] == "all" else rec["op"][1][1]] += 1
         for i in range(2, len(log)):
             if log[i - 2]["op"][0] == "unprepare" and log[i - 1].get("truss_after") == "whole" and "ceu" in log[i]:
                 after_unprep[log[i]["ceu"][0]] += 1
+                for r in GRAPH_OWNED:                    # held before the unprepare, read before it is run again
+                    later = next((x for x in log[i + 1:] if x.get("ran") == r or x.get("read") == r), None)
+                    if r in log[i - 2]["held_before"] and later is not None and later.get("verified") == r:
+                        owned_across[r] += 1
         secs = sections(plan)
         ran_in = [{log[i]["ran"] for i in range(lo, hi) if log[i].get("ran")} for _, lo, hi in secs]
         per_graph += [hi - lo for _, lo, hi in secs]
@@ -783,7 +887,7 @@ def coverage(plans, facts=FACTS):
             "drop_cells": (len(drop_cells & all_drop), len(all_drop)), "drop_missing": sorted(all_drop - drop_cells),
             "keep_cells": (len(keep_cells & all_keep), len(all_keep)), "keep_missing": sorted(all_keep - keep_cells),
             "ceu": ceu, "sup_first": sup, "comm_v_first": comm_v, "refused": refused, "after_unprepare": after_unprep,
-            "transitions": transitions}
+            "transitions": transitions, "source_lists": specs, "owned_across_unprepare": owned_across}
 
 
 # ---- expected values: base inputs from the oracle, results from the restatements of tests/*_ref.py
@@ -791,6 +895,22 @@ def coverage(plans, facts=FACTS):
 def hand_graphs():
     import hierarchy_ref, nucleus_ref, structural_ref
     return {"hand_sc": structural_ref.hand_graph(), "hand_nuc": nucleus_ref.hand_graph(), "strided": hierarchy_ref.strided_claim_graph()}
+
+
+def master_sources(name, nv, deg):
+    """The master source list of a graph (in the ids the plan loads it with): MASTER_LEN entries drawn with repeats, in no
+    order, from at most MASTER_POOL distinct vertices; it starts at the vertex of largest degree and has an isolated vertex
+    among its first five entries where the graph has one.  Seeded from the graph's name and nv; none on the empty graph."""
+    if nv == 0:
+        return []
+    rng = np.random.default_rng([nv] + [ord(c) for c in name])
+    hub, isolated = int(np.argmax(deg)), np.flatnonzero(np.asarray(deg) == 0)[:1].tolist()
+    pool = np.unique(np.concatenate([rng.permutation(nv)[:MASTER_POOL - 2], [hub], isolated]).astype(np.int64))
+    master = rng.choice(pool, size=MASTER_LEN).tolist()
+    master[0] = hub
+    if isolated:
+        master[3] = isolated[0]
+    return [int(v) for v in master]
 
 
 class Graph:
@@ -814,7 +934,13 @@ class Graph:
         self.rk = O.fractional_rank_fast(self.core.astype(np.int64) * nv + self.deg)
         self.score = O.corea_scores(self.deg, self.core)
         self.merge = O.run_merge(self.rowptr, self.col) if 0 < nv <= MERGE_MAX_NV else None
+        self.master = master_sources(name, nv, self.deg)
+        self.searches = {"btw": {}, "dist": {}}            # the cache= of the two references: one search per distinct vertex
         self.refs, self.seconds = {}, 0.0
+
+    def sources(self, spec):
+        """The source list of a plan's spec: None for every vertex, else a prefix of the master list."""
+        return None if spec == "all" else self.master[:spec[1]]
 
     def ne(self, mask=None):
         return len(self.base[mask][0])

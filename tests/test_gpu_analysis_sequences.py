@@ -1,36 +1,45 @@
-"""One context under seeded random plans over every entry point: all sixteen results of a komb_ctx in one sequence.
+"""One context under seeded random plans over every entry point: all nineteen results of a komb_ctx in one sequence.
 
 The per-analysis files test each analysis in depth, in its own file and in a fixed order.  Here the plans of
 tests/sequence_model.py (make_plan: 8 graphs per plan, larger and smaller in turn, graphs whose arrays land in each other's
 pool blocks) are driven through ONE KombAccel, so that analysis A's block, with A's plausible leftovers of another graph of
-similar size in it, is handed to analysis B; every lazily made array is first asked for by each of its consumers; and every
-cell of the header's drop / keep table is exercised.  After every operation: the status code is the model's (the model is
-written from include/komb_accel.h); a refused call has written nothing (every output starts as 0xA5 bytes); komb_stats is
-unchanged where the header says so; what is held equals the references -- base inputs from the oracle, results from the
-restatements tests/*_ref.py through the comparers of the per-analysis files -- exactly, every array and every integer of
-info.  "stale" sets no POISON: a reused block holds real leftovers; "poisoned" starts at 0xFFFFFFFF and changes the word
-between steps.  No call here fails an allocation or faults: every refusal is an ordinary error return.
+similar size in it, is handed to analysis B -- the [nv][64] doubles of betweenness and the all-ones masks of distances to the
+peel, union-find and clique kernels, and theirs to seen[], front[], hpart[], sigma and delta; every lazily made array is first
+asked for by each of its consumers; and every cell of the header's drop / keep table is exercised.  After every operation: the
+status code is the model's (the model is written from include/komb_accel.h); a refused call has written nothing (every output
+starts as 0xA5 bytes, with room for the largest output any reader writes); komb_stats is unchanged where the header says so;
+what is held equals the references -- base inputs from the oracle, results from the restatements tests/*_ref.py through the
+comparers of the per-analysis files -- exactly, every array and every integer of info, bc[] and harmonic[] as raw 64-bit
+patterns.  The graphlet census, betweenness and distances are fed the oracle's CSR and canonical edges here, never the
+library's own.  "stale" sets no POISON: a reused block holds real leftovers; "poisoned" starts at 0xFFFFFFFF and changes the
+word between steps.  No call here fails an allocation or faults: every refusal is an ordinary error return.
 
 A failure names the seed, the index of the operation and the plan up to it as a Python literal; replay it with
     run_plan(K, O, monkeypatch, seed, prefix, poisoned)
-(seed: the ids of every graph but A-D are permuted by it).
+(seed: the ids of every graph but A-D are permuted by it, and the source lists follow the ids).
 
 Figures, as measured:
-  operations per plan: 496 / 497 / 498 / 509 (seeds 11, 23, 37, 41), 8 graphs each, 51 .. 73 per graph;
-  coverage() of the four plans (tests/test_sequence_model_ref.py asserts the conditions): every run 29 .. 87 times; 85 / 85 drop
-  cells probed, 343 / 343 keep cells verified; each of the eleven consumers of the canonical edge list first 2 .. 4 times and
-  later 3 .. 67 times; the canonical supports first by komb_truss_fetch_support 47 times, by a structural run 18 times; the
-  communities' vertex pass first by fetch_vertices 17 times, by info 14 times; each refusable run refused with its result held
-  and verified afterwards 2 .. 16 times; each consumer straight after unprepare + truss_run 1 .. 2 times; the reuse
-  transitions B->A 2, A->B 1, A|B->C 3, E->E' 2 times;
+  operations per plan: 591 / 585 / 587 / 577 (seeds 11, 23, 37, 41), 8 graphs each, 60 .. 85 per graph;
+  coverage() of the four plans (tests/test_sequence_model_ref.py asserts the conditions): every run 32 .. 86 times (the census
+  36, betweenness and distances 45 each); 96 / 96 drop cells probed, 470 / 470 keep cells verified; each of the twelve consumers
+  of the canonical edge list first 2 .. 4 times and later 4 .. 68 times (the census 2 and 22); the canonical supports first by
+  komb_truss_fetch_support 47 times, by a structural run 15 times, by the census 5 times; the communities' vertex pass first by
+  fetch_vertices 19 times, by info 9 times; each refusable run refused with its result held and verified afterwards 2 .. 18
+  times (betweenness and distances 18 each); each consumer straight after unprepare + truss_run 1 .. 2 times, betweenness and
+  distances held across the pair and read after it 16 times each; source lists of 0 / 1 / 3 / 65 / 257 entries and every
+  vertex: betweenness 16 / 3 / 1 / 11 / 8 / 6 runs, distances 17 / 3 / 1 / 11 / 8 / 5; the reuse transitions B->A 2, A->B 1,
+  A|B->C 3, E->E' 2 times;
   reference CPU seconds per graph (one thread, the restatements alone, summed over what one plan asks of the graph; the
-  oracle's base inputs of all 15 graphs take 0.3 .. 0.5 s per plan): A 0.02 .. 0.93, B 0.01 .. 1.33, C 0.28 .. 1.41,
-  D 0.73 .. 3.38, E (K_60: the nucleus hierarchy of its 487 635 4-cliques alone takes 3.8 s) 4.7 .. 5.0, the strided-claim
-  graph (524 549 vertices) 1.9, every other graph under 0.06; per plan 6.6 / 1.4 / 9.2 / 9.0 s, paid once per seed by the
-  module's cache, so by the "stale" test of the seed;
+  oracle's base inputs of all 15 graphs take 0.3 .. 0.7 s per plan): A 0.09 .. 0.72, B 0.13 .. 0.54, C 0.14 .. 0.95,
+  D 0.77 .. 2.27, E (K_60, 487 635 4-cliques) 2.2 .. 2.5, the strided-claim graph (524 549 vertices: its adjacency lists, the
+  sparse census and three searches) 4.3, every other graph under 0.1; per plan 3.9 / 1.4 / 6.6 / 7.4 s, paid once per seed by
+  the module's cache, so by the "stale" test of the seed;
+  a run from any vertex of the strip C (about 4500 levels) takes 0.17 s (distances) and 0.73 s (betweenness) on the MI355X, with
+  which the poisoned tests took 1.4 .. 1.5 s: C has the empty source list only (sequence_model.SOURCE_LENGTHS);
   wall time per test on the MI355X: see WALL_SECONDS below.
 """
 import ctypes
+import os
 import time
 
 import numpy as np
@@ -38,12 +47,15 @@ import pytest
 
 import sequence_model as SM
 
+import betweenness_ref
 import biconnected_ref
 import clique_census_ref
 import clique_communities_ref
 import community_hierarchy_ref
 import components_ref
 import densest_ref
+import distances_ref
+import graphlets_ref
 import hierarchy_ref
 import max_clique_ref
 import maximal_cliques_ref
@@ -53,6 +65,7 @@ import onion_ref
 import structural_ref
 import truss_communities_ref
 
+import test_gpu_betweenness as T_btw
 import test_gpu_biconnected as T_bic
 import test_gpu_clique_census as T_cens
 import test_gpu_clique_communities as T_perc
@@ -60,6 +73,8 @@ import test_gpu_community_hierarchy as T_chier
 import test_gpu_components as T_comp
 import test_gpu_densest as T_dens
 import test_gpu_dirty_memory as T_dirty
+import test_gpu_distances as T_dist
+import test_gpu_graphlets as T_gl
 import test_gpu_hierarchy as T_hier
 import test_gpu_max_clique as T_mclq
 import test_gpu_maximal_cliques as T_mxl
@@ -73,8 +88,8 @@ pytestmark = pytest.mark.gpu
 OK, ARG, STATE = SM.OK, SM.ARG, SM.STATE
 
 # wall seconds of test_sequence[seed-mode] on the MI355X, as measured (the stale test of a seed computes the seed's references)
-WALL_SECONDS = {(11, "stale"): 3.97, (11, "poisoned"): 0.39, (23, "stale"): 1.55, (23, "poisoned"): 0.59, (37, "stale"): 5.38, (37, "poisoned"): 0.53,
-                (41, "stale"): 6.57, (41, "poisoned"): 0.52, "test_full_caps_reserves_the_bounds_at_once": 0.17}
+WALL_SECONDS = {(11, "stale"): 5.00, (11, "poisoned"): 0.58, (23, "stale"): 2.00, (23, "poisoned"): 0.47, (37, "stale"): 7.19, (37, "poisoned"): 0.49,
+                (41, "stale"): 8.02, (41, "poisoned"): 0.51, "test_full_caps_reserves_the_bounds_at_once": 0.19}
 REFERENCE_SECONDS = {}
 
 
@@ -124,7 +139,22 @@ READERS = {
     "mxl": (("komb_maximal_cliques_fetch", ()), ("komb_maximal_cliques_list", (BIG, BIG)), ("komb_maximal_cliques_info", ())),
     "perc": (("komb_clique_communities_count", ()), ("komb_clique_communities_fetch", ()), ("komb_clique_communities_fetch_communities", ()),
              ("komb_clique_communities_fetch_vertices", ()), ("komb_clique_communities_info", ())),
+    "gl": (("komb_graphlets_fetch_vertices", ()), ("komb_graphlets_fetch_edges", ()), ("komb_graphlets_info", ())),
+    "btw": (("komb_betweenness_fetch", ()), ("komb_betweenness_fetch_sources", ()), ("komb_betweenness_info", ())),
+    "dist": (("komb_distances_fetch", ()), ("komb_distances_fetch_sources", ()), ("komb_distances_histogram", (BIG,)), ("komb_distances_info", ())),
 }
+assert set(READERS) == set(SM.RESULTS) and set(SM.STATS_FROZEN) >= {"gl", "btw", "dist"}
+
+
+class _Held:
+    """The context for a comparer that runs the analysis before it fetches: here the run is the one the plan made."""
+
+    def __init__(self, a):
+        self.a, self.nv = a, a.nv
+
+    def run_graphlets(self):
+        cycles4, cliques4 = self.a.graphlets_fetch_edges()
+        return self.a.graphlets_fetch_vertices(), cycles4, cliques4, self.a.graphlets_info()
 
 
 def _probe(K, a, fname, byval, nbytes):
@@ -136,14 +166,14 @@ def _probe(K, a, fname, byval, nbytes):
             arrays.append(np.full(nbytes, 0xA5, np.uint8))
             call.append(K._lib.ptr(arrays[-1]))
         elif isinstance(t, type) and issubclass(t, ctypes._Pointer):
-            x = t._type_()
-            ctypes.memset(ctypes.byref(x), 0xA5, ctypes.sizeof(x))
+            x = (t._type_ * 16)()                        # (one value, or the nine totals of komb_graphlets_info)
+            ctypes.memset(x, 0xA5, ctypes.sizeof(x))
             scalars.append(x)
-            call.append(ctypes.byref(x))
+            call.append(x)
         else:
             call.append(byval.pop(0))
     rc = getattr(K._lib.load(), fname)(*call)
-    clean = all(bool((b == 0xA5).all()) for b in arrays) and all(bytes(x) == b"\xa5" * ctypes.sizeof(x) for x in scalars)
+    clean = all(bool((b.view(np.uint64) == 0xA5A5A5A5A5A5A5A5).all()) for b in arrays) and all(bytes(x) == b"\xa5" * ctypes.sizeof(x) for x in scalars)
     return rc, clean
 
 
@@ -172,6 +202,7 @@ class Driver:
             monkeypatch.setenv("KOMB_POISON", SM.POISON_WORDS[0])
         self.a = K.KombAccel()
         self.checkpoints, self.after_load = {}, {}
+        self.dist_words = None                           # the DIST_WORDS in force when the held distance result was made
 
     def close(self):
         self.a.close()
@@ -195,8 +226,9 @@ class Driver:
         return top + 1 if k == "above" else k
 
     def _nbytes(self):
+        """Room for the largest output any reader can write: the fifteen orbits of every vertex."""
         g = self.graphs.get(self.model.graph)
-        return 64 + 8 * (max(g.nv, 4 * g.ne(), 1024) if g is not None else 1 << 16)
+        return 64 + 8 * (max(15 * g.nv, 4 * g.ne(), 1024) if g is not None else 1 << 16)
 
     # ---- one operation: the status code it answered (verification of what it read inside)
     def execute(self, op, want):
@@ -291,6 +323,32 @@ class Driver:
 
     def x_perc(self, a, want, k):
         return self._code(lambda: a.clique_communities_run(self._t_above(k, 4)))
+
+    def x_gl(self, a, want):
+        return self._code(a.graphlets_run)
+
+    def _sources_run(self, a, spec, run, raw):
+        """A good spec through the wrapper; a bad one through the raw call, as the per-analysis error tests make it."""
+        g = self.graphs.get(self.model_before_graph)
+        if spec == "all" or spec[0] == "prefix":
+            return self._code(lambda: run(None if g is None else g.sources(spec)))
+        nv = 0 if g is None else g.nv
+        n, ids = {"id_high": (3, [0, nv, 1]), "id_negative": (2, [0, -1]), "count": (-1, [0, 0])}[spec[1]]
+        src = np.asarray(ids, np.int32)
+        a._sync_env_options()
+        rc = raw(a._ctx, n, self.K._lib.ptr(src))
+        assert src.tolist() == ids
+        return rc
+
+    def x_btw(self, a, want, spec):
+        return self._sources_run(a, spec, a.betweenness_run, self.lib.komb_betweenness_run)
+
+    def x_dist(self, a, want, spec):
+        words = {"1": 1, "2": 2}.get(os.environ.get("KOMB_DIST_WORDS"), T_dist.DEFAULT_WORDS)
+        rc = self._sources_run(a, spec, a.distances_run, self.lib.komb_distances_run)
+        if rc == OK:
+            self.dist_words = words
+        return rc
 
     def x_option(self, a, want, name, value):
         names = name.split("+")
@@ -479,6 +537,27 @@ class Driver:
         want, tests = g.ref(("perc", k, k_min, mask), lambda: (clique_communities_ref.solve(g.nv, cliques, k),
                                                                clique_communities_ref.pair_tests(cliques, k)))
         T_perc._compare(a, want, tests)
+
+    def v_gl(self, a, g, params, arg):
+        mask, = params
+        eu, ev, _, sup = g.base[mask]
+        want, items = g.ref(("gl", mask), lambda: (graphlets_ref.census(g.nv, eu, ev), graphlets_ref.ordered_items(g.nv, eu, ev)))
+        T_gl._compare(_Held(a), eu, ev, sup, want, items)
+
+    def _rows(self, g):
+        """The adjacency lists of the oracle's CSR (never the library's own)."""
+        return g.ref(("rows",), lambda: betweenness_ref.rows_of_csr(g.rowptr.tolist(), g.col.tolist()))
+
+    def v_btw(self, a, g, spec, arg):
+        rows = self._rows(g)
+        want = g.ref(("btw", spec), lambda: betweenness_ref.betweenness(rows, g.sources(spec), cache=g.searches["btw"]))
+        T_btw._same((a.betweenness_fetch(), a.betweenness_fetch_sources(), a.betweenness_info()), want)
+
+    def v_dist(self, a, g, spec, arg):
+        words = self.dist_words                          # (n_batches and n_level_steps follow it; harmonic[] must not)
+        rows = self._rows(g)
+        want = g.ref(("dist", spec, words), lambda: distances_ref.distances(rows, g.sources(spec), words, cache=g.searches["dist"]))
+        T_dist._same((a.distances_fetch(), a.distances_fetch_sources(), a.distances_histogram(), a.distances_info()), want)
 
     # ---- one step
     def step(self, op):

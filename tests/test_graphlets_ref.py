@@ -1,11 +1,12 @@
 """CPU tests of the two graphlet references (tests/graphlets_ref.py) against each other: the closed forms of census() and
-the subset enumeration of brute() share nothing but the orbit numbering."""
+the subset enumeration of brute() share nothing but the orbit numbering.  The sparse path of census() (above 3000 vertices) is
+held against the dense one and against brute()."""
 from itertools import combinations
 
 import numpy as np
 import pytest
 
-from graphlets_ref import IDENTITIES, ORBITS, TYPES, brute, census, check_identities, ordered_items
+from graphlets_ref import DENSE_MAX_NV, IDENTITIES, ORBITS, TYPES, brute, census, census_sparse, check_identities, ordered_items
 
 # the six connected graphs of 4 vertices: edges and, per vertex, the one 4-vertex orbit it holds
 FOUR = {
@@ -80,3 +81,79 @@ def test_identities_are_not_vacuous():
     with pytest.raises(AssertionError):
         check_identities(bad)
     assert len(IDENTITIES) == 6
+
+
+# ---- the sparse path of census(): the graphs above 3000 vertices of tests/sequence_model.py
+
+def _simple(nv, uv):
+    """(eu, ev): the canonical edges of the raw pairs -- u < v, ascending, loops and repeats dropped"""
+    uv = np.asarray(uv, dtype=np.int64).reshape(-1, 2)
+    uv = np.unique(np.sort(uv[uv[:, 0] != uv[:, 1]], axis=1), axis=0)
+    return uv[:, 0], uv[:, 1]
+
+
+def _equal(x, y):
+    for key in ("orbit", "cycles4", "cliques4", "sup"):
+        assert x[key].dtype == y[key].dtype and np.array_equal(x[key], y[key]), key
+    assert x["total"] == y["total"]
+
+
+@pytest.fixture(scope="module")
+def sequence_graphs(built):
+    import komb_amd
+    import sequence_model as SM
+    return SM.raw_graphs(komb_amd.gen_hug_edges, SM.hand_graphs())
+
+
+@pytest.mark.parametrize("name", ["A", "B", "D", "hand_sc", "hand_nuc"])
+def test_sparse_path_equals_the_dense_one(sequence_graphs, name):
+    nv, uv = sequence_graphs[name]
+    eu, ev = _simple(nv, uv)
+    assert nv <= DENSE_MAX_NV and len(eu) > 0
+    dense, sparse = census(nv, eu, ev, dense=True), census_sparse(nv, eu, ev)
+    _equal(dense, sparse)
+    assert dense["cycles4"].any() and dense["sup"].any()
+
+
+def test_sparse_path_on_the_strided_graph_equals_the_dense_one_on_its_vertices_with_edges(sequence_graphs):
+    """524 549 vertices, far past the dense identity: the default is the sparse path; the dense one sees the four vertices that
+    have edges, renumbered, and every other vertex has fifteen zeros."""
+    nv, uv = sequence_graphs["strided"]
+    eu, ev = _simple(nv, uv)
+    assert nv > DENSE_MAX_NV
+    got = census(nv, eu, ev)                                                # (the dense one would assert)
+    ids = np.unique(np.concatenate([eu, ev]))
+    small = census(len(ids), np.searchsorted(ids, eu), np.searchsorted(ids, ev), dense=True)
+    for key in ("cycles4", "cliques4", "sup"):
+        assert np.array_equal(got[key], small[key]), key
+    assert np.array_equal(got["orbit"][:, ids], small["orbit"]) and got["total"] == small["total"] and got["total"]["clique4"] == 1
+    rest = np.ones(nv, dtype=bool)
+    rest[ids] = False
+    assert not got["orbit"][:, rest].any()
+
+
+@pytest.mark.parametrize("seed", range(20))
+def test_sparse_path_equals_brute_on_small_permuted_graphs(seed):
+    """The random graphs of test_random_graphs, their ids permuted."""
+    rng = np.random.default_rng(1000 + seed)
+    nv = int(rng.integers(5, 29))
+    p = float(rng.choice([0.1, 0.2, 0.35, 0.5, 0.8, 1.0]))
+    alive = rng.random(nv) < 0.85
+    edges = [(u, v) for u, v in combinations(range(nv), 2) if alive[u] and alive[v] and rng.random() < p]
+    ids = np.random.default_rng(2000 + seed).permutation(nv)
+    edges = sorted((int(min(ids[u], ids[v])), int(max(ids[u], ids[v]))) for u, v in edges)
+    s, b = census_sparse(nv, [e[0] for e in edges], [e[1] for e in edges]), brute(nv, edges)
+    _equal(s, b)
+    check_identities(s["orbit"])
+
+
+def test_sparse_path_on_the_strip_of_triangles(sequence_graphs):
+    """Graph C, 9000 vertices: the identities hold, and the counts are the strip's -- 2 n - 3 edges, n - 2 triangles, a diamond
+    on every four consecutive vertices, no 4-cycle without a chord and no 4-clique."""
+    nv, uv = sequence_graphs["C"]
+    eu, ev = _simple(nv, uv)
+    c = census(nv, eu, ev)
+    check_identities(c["orbit"])
+    assert c["total"]["edge"] == 2 * nv - 3 and c["total"]["triangle"] == nv - 2 and c["total"]["diamond"] == nv - 3
+    assert c["total"]["cycle4"] == 0 and c["total"]["clique4"] == 0 and not c["cliques4"].any()
+    assert int(c["cycles4"].sum()) == 4 * c["total"]["diamond"]
