@@ -1009,3 +1009,320 @@ int32_t orc_nucleus(int64_t nv, const int64_t *rowptr, const int32_t *col, int64
     nuc_free(&N);
     return tmax;
 }
+
+/* ============================================================ traversals and graphlets
+ * References for the distance analysis, the betweenness centrality and the graphlet census (include/komb_accel.h has the
+ * definitions).  Each starts at a VERTEX and walks the sorted CSR rows: one queue BFS per source, one source at a time -- no
+ * bit-parallel masks, no batches of 64 sources, no (d, id) order, no hash tables, no canonical-edge roots.  This file is
+ * built with -ffp-contract=off (oracle/Makefile): every +, * and / below is one IEEE-754 binary64 operation that rounds once,
+ * in the order written.  tests/test_oracle_traversals.py ties them to the Python restatements under tests/ and to the stored
+ * fixtures bit for bit. */
+
+/* one queue BFS from s: dist[] (-1: unreached; the caller hands it in all -1 and gets it back so), queue[] = the reached
+ * vertices in the order found (distances never descend along it).  Returns how many. */
+static int64_t bfs_queue(const int64_t *rowptr, const int32_t *col, int32_t s, int32_t *dist, int32_t *queue)
+{
+    int64_t head = 0, tail = 0;
+    dist[s] = 0;
+    queue[tail++] = s;
+    while (head < tail) {
+        const int32_t v = queue[head++], d = dist[v] + 1;
+        for (int64_t j = rowptr[v]; j < rowptr[v + 1]; ++j) {
+            const int32_t w = col[j];
+            if (dist[w] < 0) { dist[w] = d; queue[tail++] = w; }
+        }
+    }
+    return tail;
+}
+
+static int sources_ok(int64_t nv, int64_t n_sources, const int32_t *sources)
+{
+    if (nv < 0 || n_sources < 0 || (n_sources > 0 && !sources)) return 0;
+    for (int64_t i = 0; i < n_sources; ++i) if (sources[i] < 0 || sources[i] >= nv) return 0;
+    return 1;
+}
+
+int32_t orc_bfs_sources(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t n_sources, const int32_t *sources,
+                        int64_t *src_reached, int64_t *src_sum, int32_t *src_ecc,
+                        int64_t *n_reached, int64_t *sum_dist, int32_t *ecc, double *harmonic, int64_t *pairs)
+{
+    if (!sources_ok(nv, n_sources, sources)) return -1;
+    for (int64_t v = 0; v < nv; ++v) { n_reached[v] = 0; sum_dist[v] = 0; ecc[v] = -1; harmonic[v] = 0.0; pairs[v] = 0; }
+    if (nv == 0) return 0;
+    int32_t *block = (int32_t *)malloc((size_t)64 * (size_t)nv * sizeof(int32_t));      /* block[k * nv + v] = d(entry k of the block, v) */
+    int32_t *queue = (int32_t *)malloc((size_t)nv * sizeof(int32_t));
+    int64_t *count = (int64_t *)calloc((size_t)nv, sizeof(int64_t));                  /* count[L]: the block's sources at distance L from one vertex */
+    int32_t depth_max = 0;
+    for (int64_t first = 0; first < n_sources; first += 64) {
+        const int64_t in_block = n_sources - first < 64 ? n_sources - first : 64;
+        memset(block, 0xFF, (size_t)in_block * (size_t)nv * sizeof(int32_t));
+        for (int64_t k = 0; k < in_block; ++k) {
+            int32_t *dist = block + k * nv;
+            const int64_t n = bfs_queue(rowptr, col, sources[first + k], dist, queue);
+            int64_t total = 0;
+            for (int64_t i = 0; i < n; ++i) {
+                const int32_t v = queue[i], d = dist[v];
+                total += d;
+                n_reached[v]++;
+                sum_dist[v] += d;
+                if (d > ecc[v]) ecc[v] = d;
+                pairs[d]++;
+            }
+            src_reached[first + k] = n;
+            src_sum[first + k] = total;
+            src_ecc[first + k] = dist[queue[n - 1]];
+            if (src_ecc[first + k] > depth_max) depth_max = src_ecc[first + k];
+        }
+        for (int64_t v = 0; v < nv; ++v) {
+            int32_t top = 0;
+            for (int64_t k = 0; k < in_block; ++k) {
+                const int32_t d = block[k * nv + v];
+                if (d > 0) { count[d]++; if (d > top) top = d; }
+            }
+            double h = 0.0;
+            for (int32_t L = 1; L <= top; ++L)
+                if (count[L] > 0) {
+                    const double q = (double)count[L] / (double)L;
+                    h = h + q;
+                    count[L] = 0;
+                }
+            harmonic[v] = harmonic[v] + h;
+        }
+    }
+    free(block); free(queue); free(count);
+    return depth_max;
+}
+
+int32_t orc_betweenness(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t n_sources, const int32_t *sources,
+                        double *bc, int64_t *src_reached, int64_t *src_sum, int32_t *src_ecc, int32_t *flags)
+{
+    if (!sources_ok(nv, n_sources, sources)) return -1;
+    for (int64_t v = 0; v < nv; ++v) bc[v] = 0.0;
+    *flags = 0;
+    if (nv == 0) return 0;
+    int32_t *dist = (int32_t *)malloc((size_t)nv * sizeof(int32_t));
+    int32_t *queue = (int32_t *)malloc((size_t)nv * sizeof(int32_t));
+    double *sigma = (double *)malloc((size_t)nv * sizeof(double));
+    double *delta = (double *)malloc((size_t)nv * sizeof(double));
+    memset(dist, 0xFF, (size_t)nv * sizeof(int32_t));
+    int32_t rc = 0;
+    for (int64_t i = 0; i < n_sources && rc == 0; ++i) {
+        const int32_t s = sources[i];
+        /* the queue BFS; a vertex sums its sigma when it leaves the queue: the queue ascends by level, so every vertex of the
+         * level below has left it before and its sigma is final */
+        int64_t head = 0, n = 0, total = 0;
+        dist[s] = 0;
+        queue[n++] = s;
+        while (head < n) {
+            const int32_t w = queue[head++], level = dist[w];
+            double acc = 0.0;
+            for (int64_t j = rowptr[w]; j < rowptr[w + 1]; ++j) {
+                const int32_t x = col[j];
+                if (dist[x] < 0) { dist[x] = level + 1; queue[n++] = x; }
+                else if (dist[x] == level - 1) acc = acc + sigma[x];
+            }
+            sigma[w] = w == s ? 1.0 : acc;
+            total += level;
+            if (sigma[w] >= 9007199254740992.0) *flags |= 1;
+            if (sigma[w] == INFINITY) rc = -2;
+        }
+        src_reached[i] = n;
+        src_sum[i] = total;
+        src_ecc[i] = dist[queue[n - 1]];
+        for (int64_t k = n - 1; k >= 0 && rc == 0; --k) {
+            const int32_t v = queue[k], above = dist[v] + 1;
+            double acc = 0.0;
+            for (int64_t j = rowptr[v]; j < rowptr[v + 1]; ++j) {
+                const int32_t w = col[j];
+                if (dist[w] == above) {
+                    const double c = (1.0 + delta[w]) / sigma[w];
+                    const double p = sigma[v] * c;
+                    acc = acc + p;
+                }
+            }
+            delta[v] = acc;
+        }
+        for (int64_t k = 0; k < n; ++k) {
+            const int32_t v = queue[k];
+            if (rc == 0 && v != s) bc[v] = bc[v] + delta[v];
+            dist[v] = -1;
+        }
+    }
+    free(dist); free(queue); free(sigma); free(delta);
+    return rc;
+}
+
+static inline uint64_t comb2_u64(uint64_t x) { return x * (x - 1) / 2; }       /* (0 for x = 0: the product is 0) */
+
+int32_t orc_graphlets(int64_t nv, const int64_t *rowptr, const int32_t *col, uint64_t *orbit, uint64_t *cycles4, uint64_t *cliques4,
+                      int64_t *sup_out)
+{
+    if (nv < 0) return -1;
+    if (nv == 0) return 0;
+    const int64_t ne = rowptr[nv] / 2;
+    const size_t nz = (size_t)nv;
+    int64_t *ustart = (int64_t *)malloc((nz + 1) * sizeof(int64_t)), *ebase = (int64_t *)malloc((nz + 1) * sizeof(int64_t));
+    upper_index(nv, rowptr, col, ustart, ebase);
+    uint64_t *sup = (uint64_t *)calloc((size_t)(ne > 0 ? ne : 1), sizeof(uint64_t));
+    uint64_t *p = (uint64_t *)calloc(nz, sizeof(uint64_t));
+    uint64_t *acc = (uint64_t *)calloc(11 * nz, sizeof(uint64_t));
+    uint64_t *d = acc, *t = acc + nz, *K4 = acc + 2 * nz, *C4 = acc + 3 * nz, *D2 = acc + 4 * nz, *D3 = acc + 5 * nz, *S = acc + 6 * nz,
+             *W10 = acc + 7 * nz, *N9 = acc + 8 * nz, *B6 = acc + 9 * nz, *SS = acc + 10 * nz;
+    int64_t dmax = 0;
+    for (int64_t v = 0; v < nv; ++v) { d[v] = (uint64_t)(rowptr[v + 1] - rowptr[v]); if ((int64_t)d[v] > dmax) dmax = (int64_t)d[v]; }
+    int32_t *common = (int32_t *)malloc((size_t)(dmax > 0 ? dmax : 1) * sizeof(int32_t)), *inner = (int32_t *)malloc((size_t)(dmax > 0 ? dmax : 1) * sizeof(int32_t));
+
+    /* per canonical edge (u, v): the 4-cycles u - x - y - v from p[y] = |N(u) & N(y)| (v is always one of those x); the common
+     * neighbourhood, its size and the edges inside it */
+    for (int64_t u = 0; u < nv; ++u) {
+        for (int64_t j = rowptr[u]; j < rowptr[u + 1]; ++j) {
+            const int32_t x = col[j];
+            for (int64_t i = rowptr[x]; i < rowptr[x + 1]; ++i) p[col[i]]++;
+        }
+        for (int64_t j = ustart[u]; j < rowptr[u + 1]; ++j) {
+            const int32_t v = col[j];
+            const int64_t e = ebase[u] + (j - ustart[u]);
+            uint64_t cyc = 0;
+            for (int64_t i = rowptr[v]; i < rowptr[v + 1]; ++i) if (col[i] != (int32_t)u) cyc += p[col[i]] - 1;
+            cycles4[e] = cyc;
+            const int32_t nc = isect(col + rowptr[u], rowptr[u + 1] - rowptr[u], col + rowptr[v], rowptr[v + 1] - rowptr[v], common);
+            uint64_t inside = 0;
+            for (int32_t a = 0; a < nc; ++a) {
+                const int32_t w = common[a];
+                inside += (uint64_t)isect(col + ustart[w], rowptr[w + 1] - ustart[w], common + a + 1, nc - a - 1, inner);
+                D2[w] += (uint64_t)nc - 1;                                       /* the triangle (w, u, v): its edge opposite w */
+            }
+            sup[e] = (uint64_t)nc;
+            cliques4[e] = inside;
+            if (sup_out) sup_out[e] = nc;
+        }
+        for (int64_t j = rowptr[u]; j < rowptr[u + 1]; ++j) {
+            const int32_t x = col[j];
+            for (int64_t i = rowptr[x]; i < rowptr[x + 1]; ++i) p[col[i]] = 0;
+        }
+    }
+
+    /* the sums over the edges at a vertex, then the closed forms (tests/graphlets_ref.py census(); unsigned 64-bit throughout:
+     * every final value is below 2^63 for degrees below 2^20, and an intermediate that wraps wraps back) */
+    for (int64_t u = 0; u < nv; ++u)
+        for (int64_t j = ustart[u]; j < rowptr[u + 1]; ++j) {
+            const int32_t v = col[j];
+            const int64_t e = ebase[u] + (j - ustart[u]);
+            t[u] += sup[e]; t[v] += sup[e];
+            K4[u] += cliques4[e]; K4[v] += cliques4[e];
+            C4[u] += cycles4[e]; C4[v] += cycles4[e];
+            D3[u] += comb2_u64(sup[e]); D3[v] += comb2_u64(sup[e]);
+            S[u] += d[v] - 1; S[v] += d[u] - 1;
+            W10[u] += sup[e] * (d[v] - 2); W10[v] += sup[e] * (d[u] - 2);
+            B6[u] += comb2_u64(d[v] - 1); B6[v] += comb2_u64(d[u] - 1);
+        }
+    int32_t rc = 0;
+    for (int64_t v = 0; v < nv; ++v) {                  /* a triangle has two edges at v, a 4-clique three, a 4-cycle two */
+        if (t[v] % 2 || K4[v] % 3 || C4[v] % 2) rc = -2;
+        t[v] /= 2; K4[v] /= 3; C4[v] /= 2;
+    }
+    for (int64_t u = 0; u < nv; ++u)
+        for (int64_t j = ustart[u]; j < rowptr[u + 1]; ++j) {
+            const int32_t v = col[j];
+            const int64_t e = ebase[u] + (j - ustart[u]);
+            N9[u] += t[v] - sup[e]; N9[v] += t[u] - sup[e];
+            SS[u] += S[v]; SS[v] += S[u];
+        }
+    for (int64_t v = 0; v < nv; ++v) {
+        uint64_t o[15];
+        const uint64_t dv = d[v], tv = t[v], k4 = K4[v];
+        o[0] = dv;
+        o[3] = tv;
+        o[2] = comb2_u64(dv) - tv;
+        o[1] = S[v] - 2 * tv;
+        o[14] = k4;
+        o[13] = D3[v] - 3 * k4;
+        o[12] = D2[v] - 3 * k4;
+        o[8] = C4[v] - o[12] - o[13] - 3 * k4;
+        o[11] = tv * (dv - 2) - 2 * o[13] - 3 * k4;
+        o[10] = W10[v] - 2 * o[13] - 2 * o[12] - 6 * k4;
+        o[9] = N9[v] - 2 * o[12] - 3 * k4;
+        o[7] = dv * (dv - 1) * (dv - 2) / 6 - o[11] - o[13] - k4;              /* (a product with a factor 0 below three) */
+        o[6] = B6[v] - o[9] - o[10] - o[13] - 2 * o[12] - 3 * k4;
+        o[4] = SS[v] - dv * (dv - 1) - 2 * tv - 2 * o[8] - 2 * o[9] - o[10] - 2 * o[13] - 4 * o[12] - 6 * k4;
+        o[5] = (dv - 1) * S[v] - 2 * tv - 2 * o[8] - o[10] - 2 * o[11] - 4 * o[13] - 2 * o[12] - 6 * k4;
+        for (int k = 0; k < 15; ++k) orbit[(size_t)k * nz + (size_t)v] = o[k];
+    }
+    free(ustart); free(ebase); free(sup); free(p); free(acc); free(common); free(inner);
+    return rc;
+}
+
+/* the orbit of v in the induced subgraph on set[0 .. n) (n = 3 or 4, connected, set[0] = v): by the number of edges and the
+ * degrees inside the set, which tell the connected 3- and 4-vertex graphs and their orbits apart */
+static int orbit_in_set(const int64_t *rowptr, const int32_t *col, const int32_t *set, int n)
+{
+    int deg[4] = { 0, 0, 0, 0 }, edges = 0, top = 0;
+    for (int a = 0; a < n; ++a)
+        for (int b = a + 1; b < n; ++b)
+            if (find_sorted(col, rowptr[set[a]], rowptr[set[a] + 1], set[b]) >= 0) { deg[a]++; deg[b]++; edges++; }
+    for (int a = 0; a < n; ++a) if (deg[a] > top) top = deg[a];
+    const int mine = deg[0];
+    if (n == 3) return edges == 3 ? 3 : (mine == 1 ? 1 : 2);
+    switch (edges) {
+    case 3: return top == 3 ? (mine == 3 ? 7 : 6) : (mine == 1 ? 4 : 5);
+    case 4: return top == 3 ? (mine == 1 ? 9 : mine == 2 ? 10 : 11) : 8;
+    case 5: return mine == 2 ? 12 : 13;
+    default: return 14;
+    }
+}
+
+/* every connected set of up to four vertices that holds set[0], each once: the set grows by one vertex of ext[] at a time;
+ * a vertex enters ext[] when the set first touches it (near[] counts the members of the set it is, or is adjacent to), and a
+ * vertex taken from ext[] stays out of the branches of the vertices taken after it. */
+struct byd { const int64_t *rowptr; const int32_t *col; int32_t *near; uint64_t *out; int32_t set[4]; };
+
+static void byd_grow(struct byd *B, int n, const int32_t *ext, int64_t n_ext)
+{
+    for (int64_t i = n_ext - 1; i >= 0; --i) {
+        const int32_t w = ext[i];
+        B->set[n] = w;
+        if (n + 1 >= 3) B->out[orbit_in_set(B->rowptr, B->col, B->set, n + 1)]++;
+        if (n + 1 == 4) continue;
+        int64_t room = i;
+        for (int64_t j = B->rowptr[w]; j < B->rowptr[w + 1]; ++j) if (B->near[B->col[j]] == 0) room++;
+        int32_t *next = (int32_t *)malloc((size_t)(room > 0 ? room : 1) * sizeof(int32_t));
+        memcpy(next, ext, (size_t)i * sizeof(int32_t));
+        int64_t n_next = i;
+        for (int64_t j = B->rowptr[w]; j < B->rowptr[w + 1]; ++j) {
+            const int32_t x = B->col[j];
+            if (B->near[x]++ == 0) next[n_next++] = x;
+        }
+        byd_grow(B, n + 1, next, n_next);
+        for (int64_t j = B->rowptr[w]; j < B->rowptr[w + 1]; ++j) B->near[B->col[j]]--;
+        free(next);
+    }
+}
+
+int64_t orc_orbits_by_definition(int64_t nv, const int64_t *rowptr, const int32_t *col, int32_t v, int64_t ball_limit, uint64_t *out)
+{
+    if (nv <= 0 || v < 0 || v >= nv) return -2;
+    int32_t *near = (int32_t *)calloc((size_t)nv, sizeof(int32_t));
+    int32_t *queue = (int32_t *)malloc((size_t)nv * sizeof(int32_t));
+    /* the ball: the vertices within three hops (near[] is the distance + 1 while it is measured) */
+    int64_t head = 0, tail = 0;
+    near[v] = 1;
+    queue[tail++] = v;
+    while (head < tail && !(ball_limit > 0 && tail > ball_limit)) {
+        const int32_t x = queue[head++];
+        if (near[x] == 4) break;
+        for (int64_t j = rowptr[x]; j < rowptr[x + 1]; ++j)
+            if (near[col[j]] == 0) { near[col[j]] = near[x] + 1; queue[tail++] = col[j]; }
+    }
+    const int64_t ball = tail;
+    for (int64_t i = 0; i < tail; ++i) near[queue[i]] = 0;
+    free(queue);
+    if (ball_limit > 0 && ball > ball_limit) { free(near); return -1; }
+    for (int k = 0; k < 15; ++k) out[k] = 0;
+    out[0] = (uint64_t)(rowptr[v + 1] - rowptr[v]);
+    struct byd B = { rowptr, col, near, out, { v, 0, 0, 0 } };
+    near[v] = 1;
+    for (int64_t j = rowptr[v]; j < rowptr[v + 1]; ++j) near[col[j]]++;
+    byd_grow(&B, 1, col + rowptr[v], rowptr[v + 1] - rowptr[v]);
+    free(near);
+    return ball;
+}

@@ -137,6 +137,42 @@ int32_t orc_nucleus(int64_t nv, const int64_t *rowptr, const int32_t *col, int64
                     int32_t *a, int32_t *b, int32_t *c, int32_t *key0, int32_t *theta,
                     int32_t *edge_theta, int32_t *vertex_theta, int32_t *quads);
 
+/* ---- references for the distance analysis, the betweenness centrality and the graphlet census (include/komb_accel.h has the
+ * definitions).  One queue BFS per list entry from a VERTEX over the sorted CSR rows, one source at a time: no bit-parallel
+ * masks, no 64-source batches, no (d, id) order, no hash tables, no canonical-edge roots.  The floating-point results follow
+ * the operation order of the definitions with every operation rounded on its own (the build sets -ffp-contract=off).  PINNED
+ * by tests/test_oracle_traversals.py against the Python restatements under tests/ and the stored fixtures, bit for bit. */
+
+/* komb_distances_run without its info: per list entry src_reached, src_sum, src_ecc [n_sources]; per vertex n_reached,
+ * sum_dist, ecc (-1 where no source reaches it) and harmonic [nv]; pairs [nv] (pairs[L] = the (entry, vertex) pairs at
+ * distance L; a distance is below nv).  harmonic[v] literally: per block of 64 consecutive entries the distances of the
+ * block's sources are kept, every vertex counts them level by level and adds (double)c / (double)L in ascending L to the
+ * block's partial sum; the partial sums are added in block order.  Returns the largest distance, -1 for bad arguments. */
+int32_t orc_bfs_sources(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t n_sources, const int32_t *sources,
+                        int64_t *src_reached, int64_t *src_sum, int32_t *src_ecc,
+                        int64_t *n_reached, int64_t *sum_dist, int32_t *ecc, double *harmonic, int64_t *pairs);
+
+/* komb_betweenness_run: Brandes from the listed sources in the order given -- sigma[w] summed over w's row in ascending id,
+ * delta[v] summed over v's row in ascending id with the division, the product and the addition rounded one after the other,
+ * bc [nv] summed over the sources in list order without the source itself.  src_* [n_sources] as above; *flags has bit 0
+ * when a sigma reached 2^53.  Returns 0, -1 for bad arguments, -2 when a sigma reached +inf (the outputs then mean nothing). */
+int32_t orc_betweenness(int64_t nv, const int64_t *rowptr, const int32_t *col, int64_t n_sources, const int32_t *sources,
+                        double *bc, int64_t *src_reached, int64_t *src_sum, int32_t *src_ecc, int32_t *flags);
+
+/* komb_graphlets_run on the graph given: orbit [15 * nv] orbit-major, cycles4, cliques4 and (unless NULL) sup [ne] in
+ * canonical edge order.  4-cycles per edge (u, v) from a dense p[y] = |N(u) & N(y)| filled by walking N(x) for x in N(u):
+ * the sum over y in N(v) without u of p[y] - 1; 4-cliques per edge by intersecting sorted rows inside the common
+ * neighbourhood; the orbits by the closed forms of tests/graphlets_ref.py census().  Unsigned 64-bit arithmetic.  Returns 0,
+ * -1 for bad arguments, -2 when a per-vertex sum that must divide does not. */
+int32_t orc_graphlets(int64_t nv, const int64_t *rowptr, const int32_t *col, uint64_t *orbit, uint64_t *cycles4, uint64_t *cliques4,
+                      int64_t *sup);
+
+/* The orbit vector out[15] of ONE vertex straight from the definition: every connected set of three and of four vertices
+ * that holds v is formed once (they lie within three hops) and classified by its edges and the degrees inside it.  Returns
+ * the number of vertices within three hops of v; with ball_limit > 0 and more than that many, -1 and out is left alone
+ * (the sets of a vertex near a hub are too many to list).  -2 for bad arguments. */
+int64_t orc_orbits_by_definition(int64_t nv, const int64_t *rowptr, const int32_t *col, int32_t v, int64_t ball_limit, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,14 @@ def lib():
         L.orc_nucleus_count.argtypes = [_i64, _i64p, _i32p, ctypes.POINTER(_i64)]
         L.orc_nucleus.restype = ctypes.c_int32
         L.orc_nucleus.argtypes = [_i64, _i64p, _i32p, _i64, _i64] + [_i32p] * 8
+        L.orc_bfs_sources.restype = ctypes.c_int32
+        L.orc_bfs_sources.argtypes = [_i64, _i64p, _i32p, _i64, _i32p, _i64p, _i64p, _i32p, _i64p, _i64p, _i32p, _f64p, _i64p]
+        L.orc_betweenness.restype = ctypes.c_int32
+        L.orc_betweenness.argtypes = [_i64, _i64p, _i32p, _i64, _i32p, _f64p, _i64p, _i64p, _i32p, ctypes.POINTER(ctypes.c_int32)]
+        L.orc_graphlets.restype = ctypes.c_int32
+        L.orc_graphlets.argtypes = [_i64, _i64p, _i32p, _u64p, _u64p, _u64p, _i64p]
+        L.orc_orbits_by_definition.restype = _i64
+        L.orc_orbits_by_definition.argtypes = [_i64, _i64p, _i32p, ctypes.c_int32, _i64, _u64p]
         _LIB = L
     return _LIB
 
@@ -547,3 +555,122 @@ def percolation_pair_tests(nv, offset, verts, k):
         pivots = np.argsort(load[v] * max(nv, 1) + v, axis=1, kind="stable")[:, :s - k + 2]
         total += int(np.take_along_axis(above[idx], pivots, axis=1).sum())
     return total
+
+
+# ------------------------------------------------ traversals and graphlets (komb_oracle.h: one queue BFS per source, dense arrays)
+class Limit(Exception):
+    """orc_betweenness: a sigma reached +inf, where the library answers KOMB_ERR_LIMIT"""
+
+
+def _sources(nv, sources):
+    return np.ascontiguousarray(np.arange(nv) if sources is None else np.asarray(sources).reshape(-1), dtype=np.int32)
+
+
+def distances(rowptr, col, sources=None, words=4):
+    """What komb_distances_run / _fetch / _fetch_sources / _histogram / _info give, in the layout of tests/distances_ref.py
+    distances(): the arrays are orc_bfs_sources', the info fields are derived here from the per-source arrays and `words`
+    (DIST_WORDS) exactly as that function derives them.  "seconds" is the time of the C call."""
+    import time
+    rowptr, col = _csr(rowptr, col)
+    nv = len(rowptr) - 1
+    src = _sources(nv, sources)
+    n = len(src)
+    if words not in (1, 2, 4) or (n and (src.min() < 0 or src.max() >= nv)):
+        raise ValueError("bad sources or words")
+    per = {"source": src.copy(), "n_reached": np.zeros(n, np.int64), "sum_dist": np.zeros(n, np.int64), "ecc": np.zeros(n, np.int32)}
+    room = max(nv, 1)
+    out = {"n_reached": np.zeros(room, np.int64), "sum_dist": np.zeros(room, np.int64), "ecc": np.full(room, -1, np.int32),
+           "harmonic": np.zeros(room, np.float64)}
+    pairs = np.zeros(room, np.int64)
+    pad = lambda x: x if len(x) else np.zeros(1, x.dtype)
+    t0 = time.perf_counter()
+    deepest = lib().orc_bfs_sources(nv, rowptr, col, n, pad(src), pad(per["n_reached"]), pad(per["sum_dist"]), pad(per["ecc"]),
+                                    out["n_reached"], out["sum_dist"], out["ecc"], out["harmonic"], pairs)
+    seconds = time.perf_counter() - t0
+    if deepest < 0:
+        raise ValueError("orc_bfs_sources: bad arguments")
+    out = {name: x[:nv] for name, x in out.items()}
+    depth_max = int(per["ecc"].max()) if n else 0
+    assert depth_max == deepest
+    out.update(sources=per, pairs=pairs[:depth_max + 1].copy(), seconds=seconds, all=sources is None)
+    out["info"] = distances_info(out, words)
+    return out
+
+
+def distances_info(out, words):
+    """info of a distances() result at DIST_WORDS = words: only the batch and step counts depend on it."""
+    ecc, pairs, nv = out["sources"]["ecc"], out["pairs"], len(out["ecc"])
+    n = len(ecc)
+    group = 64 * words
+    batches = [ecc[i:i + group] for i in range(0, n, group)]
+    return {"n_sources": n, "flags": 1 if out["all"] else 0, "depth_max": int(ecc.max()) if n else 0, "depth_min": int(ecc.min()) if n else 0,
+            "n_pairs": int(pairs.sum()), "sum_all": int((pairs * np.arange(len(pairs))).sum()), "n_batches": len(batches),
+            "n_level_steps": sum(int(b.max()) + 1 for b in batches) if nv else 0}
+
+
+def betweenness(rowptr, col, sources=None):
+    """What komb_betweenness_run / _fetch / _fetch_sources / _info give, in the layout of tests/betweenness_ref.py
+    betweenness(), from orc_betweenness; the batch and step counts are derived here as that function derives them.  Raises
+    Limit where the library answers KOMB_ERR_LIMIT."""
+    import time
+    rowptr, col = _csr(rowptr, col)
+    nv = len(rowptr) - 1
+    src = _sources(nv, sources)
+    n = len(src)
+    if n and (src.min() < 0 or src.max() >= nv):
+        raise ValueError("bad sources")
+    bc = np.zeros(max(nv, 1), np.float64)
+    reached, sumd, ecc = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32)
+    flags = ctypes.c_int32()
+    t0 = time.perf_counter()
+    rc = lib().orc_betweenness(nv, rowptr, col, n, src if n else np.zeros(1, np.int32), bc, reached, sumd, ecc, ctypes.byref(flags))
+    seconds = time.perf_counter() - t0
+    if rc == -2:
+        raise Limit()
+    if rc != 0:
+        raise ValueError("orc_betweenness: bad arguments")
+    ecc = ecc[:n]
+    batches = [ecc[i:i + 64] for i in range(0, n, 64)]
+    steps = sum((int(b.max()) + 1) + max(int(b.max()) - 1, 0) for b in batches) if nv > 0 else 0
+    return {"bc": bc[:nv], "source": src.copy(), "n_reached": reached[:n], "sum_dist": sumd[:n], "ecc": ecc, "flags": int(flags.value),
+            "depth_max": int(ecc.max()) if n else 0, "n_sources": n, "n_batches": len(batches), "n_level_steps": steps, "seconds": seconds}
+
+
+GRAPHLET_TOTAL_OF = {"edge": (0, 2), "wedge": (2, 1), "triangle": (3, 3), "path4": (5, 2), "claw": (7, 1), "cycle4": (8, 4),
+                     "paw": (11, 1), "diamond": (13, 2), "clique4": (14, 4)}       # total = the sum of orbit o over the vertices / divisor
+
+
+def graphlets(rowptr, col):
+    """orc_graphlets in the layout of tests/graphlets_ref.py census(): {"orbit": uint64[15, nv], "cycles4", "cliques4": uint64[ne],
+    "sup": int64[ne], "total": {name: int}, "seconds"}, the per-edge arrays in canonical order."""
+    import time
+    rowptr, col = _csr(rowptr, col)
+    nv = len(rowptr) - 1
+    ne = int(rowptr[nv]) // 2
+    orbit = np.zeros(15 * max(nv, 1), np.uint64)
+    cyc, clq, sup = np.zeros(max(ne, 1), np.uint64), np.zeros(max(ne, 1), np.uint64), np.zeros(max(ne, 1), np.int64)
+    t0 = time.perf_counter()
+    rc = lib().orc_graphlets(nv, rowptr, col, orbit, cyc, clq, sup)
+    seconds = time.perf_counter() - t0
+    if rc != 0:
+        raise RuntimeError("orc_graphlets: %d" % rc)
+    orbit = orbit[:15 * nv].reshape(15, nv)
+    total = {}
+    for name, (o, div) in GRAPHLET_TOTAL_OF.items():
+        s = sum(int(x) for x in orbit[o])
+        assert s % div == 0, (name, s, div)
+        total[name] = s // div
+    return {"orbit": orbit, "cycles4": cyc[:ne], "cliques4": clq[:ne], "sup": sup[:ne], "total": total, "seconds": seconds}
+
+
+def orbits_by_definition(rowptr, col, v, ball_limit=0):
+    """(orbit vector uint64[15] of vertex v from orc_orbits_by_definition, the vertices within three hops of v); (None, None)
+    when ball_limit > 0 and the ball is larger."""
+    rowptr, col = _csr(rowptr, col)
+    out = np.zeros(15, np.uint64)
+    ball = lib().orc_orbits_by_definition(len(rowptr) - 1, rowptr, col, int(v), int(ball_limit), out)
+    if ball == -1:
+        return None, None
+    if ball < 0:
+        raise ValueError("orc_orbits_by_definition: bad arguments")
+    return out, int(ball)
